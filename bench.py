@@ -13,6 +13,10 @@ g_lr 8e-5, d_lr 1e-3, mse_lambda 10, clip 15, noise std 0 (run_gan_rnn_placehold
 A step = disc_updates=1 D-run + gen_updates=1 G-run through the C ABI (the G-run reuses the D-run's
 generator forward: G does not change in between).  Inputs are resident in HBM when the timed region
 starts.  One JSON line on rank 0.
+
+A plain run prints the headline alone (metric, value, ms_per_step, the roofline of the timed steps); --full adds everything
+else this script measures (CPU baseline, network variants, kernel timing, memory activity): up to a few minutes more.
+--dump-outputs DIR writes what the last timed step computed, so that two builds can be compared on the same seeded inputs.
 """
 from __future__ import annotations
 
@@ -80,6 +84,30 @@ def synthetic(B, T, din, dout, seed=1234):
     lab = rng.standard_normal((B, T, dout)).astype(np.float32)
     ln = np.full(B, T, np.int32)
     return x, lab, ln
+
+
+DUMP_BYTES = 60 * 10 ** 6          # --dump-outputs writes at most this much (under 64 MB with room for the .npy headers)
+
+
+def net_variables(engine):
+    """the variables a step left behind, one flat array per net: the generator's, and the discriminator's where there is one"""
+    return {name: engine.get_params(net, "variables") for net, name in ((0, "g_variables"), (1, "d_variables")) if engine.param_count(net)}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32 (float64 stays float64).  When the arrays hold more than DUMP_BYTES,
+    each one above its even share of that is replaced by the elements at fixed positions (drawn from a seed-0 generator, so the same
+    positions in every run with the same arguments), written as <name>_sample.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    over = sum(v.nbytes for v in arrays.values()) > DUMP_BYTES
+    share = DUMP_BYTES // len(arrays)
+    for k, v in arrays.items():
+        if over and v.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, share // v.itemsize, replace=False))
+            k, v = k + "_sample", v.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def _usable_cpus():
@@ -188,9 +216,10 @@ def hbm_activity(step, ms_per_step, seconds=4.0):
             "how": "mean rocm-smi memory read/write activity over %d samples while %d un-profiled steps ran, x 8 TB/s x ms/step" % (len(mid), n)}
 
 
-def measure_sequence(a, net, d_type, B, T, steps, warmup, rank, local, world, dev):
+def measure_sequence(a, net, d_type, B, T, steps, warmup, rank, local, world, dev, dump=None):
     """One timed run of the sequence-level GAN step: W untimed steps, then exactly `steps` steps between
-    barrier + synchronize on both sides; MAX over ranks."""
+    barrier + synchronize on both sides; MAX over ranks.  dump: directory for what the last timed step returned and left
+    (rank 0's loss rows and the variables), written before anything else runs on the model."""
     from types import SimpleNamespace
     from rsrgan_amd import GAN_RNN, dist as rdist
     g_type = "res_lstm_base" if net == "baseline_named" else net
@@ -211,11 +240,11 @@ def measure_sequence(a, net, d_type, B, T, steps, warmup, rank, local, world, de
 
     def step():
         # gather=False: like train_one_iteration, the tower mean of the loss scalars is taken once per iteration, not per step
-        model.d_step(x, lab, ln, sync=False, gather=False)
+        d = model.d_step(x, lab, ln, sync=False, gather=False)
         out = None
         for i in range(a.gen_updates):
             out = model.g_step(x, lab, ln, reuse_g_forward=(i == 0), sync=False, gather=False)
-        return out
+        return d, out
 
     with model.engine.on_stream():             # one real stream for the whole loop (hipGraph replay; no null-stream hops)
         for _ in range(warmup):
@@ -225,7 +254,7 @@ def measure_sequence(a, net, d_type, B, T, steps, warmup, rank, local, world, de
         t0 = time.perf_counter()
         ev[0].record()
         for i in range(steps):
-            last = step()
+            last_d, last = step()
             ev[i + 1].record()
         torch.cuda.synchronize(); rdist.barrier()
         dt = time.perf_counter() - t0
@@ -239,6 +268,8 @@ def measure_sequence(a, net, d_type, B, T, steps, warmup, rank, local, world, de
         losses = last.mean(0).cpu().numpy()
         if not np.all(np.isfinite(losses)):
             raise SystemExit("non-finite losses: %s" % losses)
+        if dump and rank == 0:
+            dump_outputs(dump, dict(d_losses=last_d, g_losses=last, **net_variables(model.engine)))
         # one more (untimed) step with every launch of the dominant kernel bracketed by HIP events on its stream
         prof = ("k_fwd_gates", 0, 0.0, 0.0)
         if not a.no_kernel_timing:
@@ -255,7 +286,7 @@ def measure_sequence(a, net, d_type, B, T, steps, warmup, rank, local, world, de
         if not a.no_kernel_timing and world == 1 and net == "lstm" and not a.no_hbm_activity:
             hbm = hbm_activity(step, dt * 1e3 / steps)
         buckets = None
-        if world > 1:                       # one more untimed step with the bucketed gradient all-reduce timed on its communication stream
+        if world > 1 and a.full:            # one more untimed step with the bucketed gradient all-reduce timed on its communication stream
             model.engine.bucket_timing = True
             step()
             buckets = model.engine.bucket_report()
@@ -290,17 +321,17 @@ def bench_dnn_gan(a, rank, local, world, dev):
 
     def step():
         if trainer:
-            return model.step(x, lab, sync=False)
+            return {"g_losses": model.step(x, lab, sync=False)}
         # scripts/train_gan_dnn.py:50-96: the D-run and the G-run each dequeue their own batch -> no shared generator forward
-        model.d_step(x, lab, sync=False)
-        return model.g_step(x2, lab2, sync=False)
+        d = model.d_step(x, lab, sync=False)
+        return {"d_losses": d, "g_losses": model.g_step(x2, lab2, sync=False)}
     for _ in range(a.warmup):
         step()
     rdist.barrier(); torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter(); e0.record()
     for _ in range(a.steps):
-        last = step()
+        outs = step()
     e1.record(); torch.cuda.synchronize(); rdist.barrier()
     dt = time.perf_counter() - t0
     dev_ms = e0.elapsed_time(e1)
@@ -308,7 +339,10 @@ def bench_dnn_gan(a, rank, local, world, dev):
         t = torch.tensor([dt, dev_ms], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt, dev_ms = float(t[0]), float(t[1])
+    last = outs["g_losses"]
     if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, dict(outs, **net_variables(model.engine)))
         fg = 2 * (2827 * 1024 + 3 * 1024 * 1024 + 1024 * 40)
         fd = 2 * (297 * 1024 + 3 * 1024 * 1024 + 1024)
         fpf = (3 * fg) if trainer else (4 * fg + 8 * fd)   # trainer: G fwd + 2x bwd; GAN: + the D-run's own G fwd, D terms as SURVEY 8d
@@ -372,6 +406,8 @@ def bench_rced(a, rank, local, world, dev):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt, dev_ms = float(t[0]), float(t[1])
     if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, dict(g_losses=last, **net_variables(model.engine)))
         # Algorithmic FLOP per frame, two conventions.  VALID TAPS (the roofline fraction): a SAME convolution only multiplies the
         # taps that meet data -- output row h meets S - |h - (S-1)/2| of the S filter rows (91 of 121 at S = 11), output column w
         # meets the fw taps minus those beyond the frame edge (fw W - pl (pl + 1) summed over w, pl = (fw - 1) / 2) -- and the
@@ -451,15 +487,14 @@ def bench_segan(a, rank, local, world, dev):
     lab = torch.from_numpy(rng.standard_normal((B, U)).astype(np.float32)).to(dev)
 
     def step():
-        model.d_step(x, lab)
-        return model.g_step(x, lab)
+        return model.d_step(x, lab), model.g_step(x, lab)
     for _ in range(a.warmup):
         step()
     rdist.barrier(); torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter(); e0.record()
     for _ in range(a.steps):
-        last = step()
+        last_d, last = step()
     e1.record(); torch.cuda.synchronize(); rdist.barrier()
     dt = time.perf_counter() - t0
     dev_ms = e0.elapsed_time(e1)
@@ -468,6 +503,11 @@ def bench_segan(a, rank, local, world, dev):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt, dev_ms = float(t[0]), float(t[1])
     if rank == 0:
+        if a.dump_outputs:
+            g_vars, d_vars = model.get_vars()
+            dump_outputs(a.dump_outputs, {"d_losses": last_d, "g_losses": last,
+                                          "g_variables": np.concatenate([v.ravel() for v in g_vars.values()]),
+                                          "d_variables": np.concatenate([v.ravel() for v in d_vars.values()])})
         fg, fd = segan_flops(L, U, DEPTHS)
         # D-run: G forward, three discriminator calls forward and backward (data + weight gradients); G-run: G forward, reference +
         # fake calls forward, the fake call's data gradient, G backward (data + weight gradients)
@@ -599,17 +639,17 @@ def bench_plumbing(a, rank, world):
     x, lab, ln = synthetic(B, T, engine.cfg.input_dim, engine.cfg.output_dim, seed=1234 + rank)
 
     def step():
-        model.d_step(x, lab, ln, sync=False, gather=False)
+        d = model.d_step(x, lab, ln, sync=False, gather=False)
         out = None
         for i in range(a.gen_updates):
             out = model.g_step(x, lab, ln, reuse_g_forward=(i == 0), sync=False, gather=False)
-        return out
+        return d, out
     for _ in range(a.warmup):
         step()
     rdist.barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        last = step()
+        last_d, last = step()
     rdist.barrier()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -617,6 +657,8 @@ def bench_plumbing(a, rank, world):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t[0])
     if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, dict(d_losses=last_d, g_losses=last, **net_variables(engine)))
         print(json.dumps({"metric": "GAN train frames/sec (G+D step), 257-dim LPS->40-dim MFCC", "value": round(B * T * world * a.steps / dt, 1),
                           "unit": "frames/s", "n_gpus": world, "rccl_ranks": rdist.world_size(), "backend": "gloo", "steps": a.steps,
                           "warmup": a.warmup, "ms_per_step": round(dt * 1e3 / a.steps, 4), "higher_is_better": True, "scaling": "weak",
@@ -646,10 +688,17 @@ def main():
     ap.add_argument("--d-type", default="lstm", choices=["lstm", "dnn"],
                     help="dnn = models/discriminator_dnn.py as the D of the sequence model (BASELINE.json's wording)")
     ap.add_argument("--gen-updates", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the BASELINE.json-named network variant at N=1")
-    ap.add_argument("--no-hbm-activity", action="store_true", help="skip the ~4 s of extra steps under the rocm-smi memory-activity sampler")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="skip the extra event-bracketed step (PMC passes count bytes per step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, the network variants, the memory-activity "
+                         "sampler, the event-bracketed kernel-timing step with the launch-floor chains and, at N > 1, the per-bucket "
+                         "all-reduce timing (each can be skipped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's loss rows) and the variables it left "
+                         "as DIR/<name>.npy (float32; a fixed sample of each array when they exceed 60 MB together)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip the network variants at N=1")
+    ap.add_argument("--no-hbm-activity", action="store_true", help="--full: skip the ~4 s of extra steps under the rocm-smi memory-activity sampler")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full: skip the extra event-bracketed step (PMC passes count bytes per step)")
     ap.add_argument("--flags", type=int, default=int(os.environ.get("RSRGAN_FLAGS", "3")),
                     help="library schedule flags: 1 = wavefront, 2 = hipGraph replay, 4 = side-stream GEMM overlap (include/rsrgan.h)")
     ap.add_argument("--batch-norm", action="store_true", help="--net dnn_gan / dnn_trainer / rced: batch_norm(renorm=True) on the hidden layers "
@@ -666,6 +715,8 @@ def main():
                          "barriers, MAX over ranks, the one JSON line) runs, on an engine the CALLER injects through "
                          "RSRGAN_BENCH_ENGINE=module:factory -- the tests' CPU stand-in; nothing is measured that means anything")
     a = ap.parse_args()
+    if not a.full:         # a plain run sets up, warms up, times the steps and prints the headline: nothing else runs
+        a.no_cpu_baseline = a.no_variants = a.no_hbm_activity = a.no_kernel_timing = True
     if a.cpu_worker:
         net, B, T, th = a.cpu_worker.split(",")
         n, dt = _cpu_run(net, int(B), int(T), int(th), 5.0, 2)
@@ -701,7 +752,7 @@ def main():
         return bench_rced(a, rank, local, world, dev)
     if a.net == "segan":
         return bench_segan(a, rank, local, world, dev)
-    res = measure_sequence(a, a.net, a.d_type, a.batch, a.frames, a.steps, a.warmup, rank, local, world, dev)
+    res = measure_sequence(a, a.net, a.d_type, a.batch, a.frames, a.steps, a.warmup, rank, local, world, dev, dump=a.dump_outputs)
     model, g_type, dt, dev_ms, losses, B, T = res["model"], res["g_type"], res["dt"], res["dev_ms"], res["losses"], a.batch, a.frames
     if a.net == "baseline_named":
         a.d_type = "dnn"
@@ -883,7 +934,7 @@ def main():
             torch.cuda.empty_cache()
         try:           # BASELINE.json configs[3]: R-CED (257 x 11) + discriminator_dnn, N = 6400 frames (bench.py --net rced --rced-gan)
             import contextlib, io
-            a3 = argparse.Namespace(**vars(a)); a3.net = "rced"; a3.rced_gan = True; a3.rced_width = 257; a3.batch = 6400; a3.steps = 5; a3.warmup = 2
+            a3 = argparse.Namespace(**vars(a)); a3.net = "rced"; a3.rced_gan = True; a3.rced_width = 257; a3.batch = 6400; a3.steps = 5; a3.warmup = 2; a3.dump_outputs = None
             buf = io.StringIO()
             with contextlib.redirect_stdout(buf):
                 bench_rced(a3, rank, local, world, dev)
@@ -895,7 +946,7 @@ def main():
             out["variants"].append({"workload": "R-CED + discriminator_dnn (configs[3])", "error": str(e)[:200]})
         try:           # BASELINE.json configs[4]: SEGAN-style conv G/D, 16384-sample chunks, B = 32 (bench.py --net segan --batch 32)
             import contextlib, io
-            a4 = argparse.Namespace(**vars(a)); a4.net = "segan"; a4.batch = 32; a4.segan_len = 16384; a4.steps = 10; a4.warmup = 3
+            a4 = argparse.Namespace(**vars(a)); a4.net = "segan"; a4.batch = 32; a4.segan_len = 16384; a4.steps = 10; a4.warmup = 3; a4.dump_outputs = None
             buf = io.StringIO()
             with contextlib.redirect_stdout(buf):
                 bench_segan(a4, rank, local, world, dev)

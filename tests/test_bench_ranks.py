@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -39,3 +41,20 @@ def test_bench_nccl_refuses_more_ranks_than_gpus():
     p = _bench(["--gpus", "8", "--steps", "1", "--warmup", "0"], env={"HIP_VISIBLE_DEVICES": "", "CUDA_VISIBLE_DEVICES": ""})
     assert p.returncode != 0 and "refusing" in p.stderr, (p.returncode, p.stderr[-500:])
     assert not [l for l in p.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: the last timed step's loss rows and the variables it left, as float32 / float64 .npy files, identical for two
+    runs with the same arguments (the seeded inputs do not change); --steps sets the number of timed steps."""
+    runs = []
+    for tag in ("a", "b"):
+        p = _bench(["--gpus", "1", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / tag)])
+        assert p.returncode == 0, p.stderr[-3000:]
+        out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0, out
+        runs.append({f: np.load(str(tmp_path / tag / f)) for f in sorted(os.listdir(str(tmp_path / tag)))})
+    assert sorted(runs[0]) == ["d_losses.npy", "d_variables.npy", "g_losses.npy", "g_variables.npy"], sorted(runs[0])
+    assert sum(v.nbytes for v in runs[0].values()) <= 64 << 20
+    for f, v in runs[0].items():
+        assert v.dtype in (np.float32, np.float64) and v.size and np.all(np.isfinite(v)), f
+        assert np.array_equal(v, runs[1][f]), f
