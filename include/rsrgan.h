@@ -46,7 +46,10 @@ typedef enum rsrgan_status {
 /* args.g_type (gan_rnn_placeholder.py:125-132) */
 enum { RSRGAN_G_LSTM = 0, RSRGAN_G_RES_LSTM_L = 1, RSRGAN_G_RES_LSTM_BASE = 2,
        RSRGAN_G_DNN = 3, /* models/gan.py:109-110 + models/dnn.py: frame-level FC generator */
-       RSRGAN_G_RCED = 4 /* models/rced.py: frame-level 9 x conv2d + FC generator (dnn_trainer.py:98-99), batch_norm=False */ };
+       RSRGAN_G_RCED = 4, /* models/rced.py: frame-level 9 x conv2d + FC generator (dnn_trainer.py:98-99), batch_norm=False */
+       RSRGAN_G_BNLSTM = 5 /* models/bnlstm.py: input FC + ReLU, BNLSTMCell(g_cells, num_proj=g_proj, peepholes) x g_layers with batch
+                              normalisation inside the recurrence, output FC; RSRGAN_FLAG_SUPERVISED only (models/rnn_trainer.py),
+                              batch_size <= 64, no RSRGAN_FLAG_BATCH_NORM, no dropout */ };
 /* self.discriminator (gan_rnn_placeholder.py:117; models/gan.py:104) */
 enum { RSRGAN_D_LSTM = 0, RSRGAN_D_DNN = 1 /* models/discriminator_dnn.py */ };
 /* which network a call addresses */

@@ -59,6 +59,7 @@ int rsrgan_default_cfg(int32_t g_type, rsrgan_cfg* c) {
   else if (g_type == RSRGAN_G_RES_LSTM_L || g_type == RSRGAN_G_RES_LSTM_BASE) { c->g_layers = 4; c->g_cells = 760; c->g_proj = 257; }  // models/res_lstm_l.py:43-45
   else if (g_type == RSRGAN_G_DNN) { c->g_layers = 4; c->g_cells = 1024; c->g_proj = 0; }        // models/dnn.py:34-35 (1+3 hidden layers)
   else if (g_type == RSRGAN_G_RCED) { c->g_layers = 9; c->g_cells = 32; c->g_proj = 0; c->g_splice = 11; }   // models/rced.py:92-93 (fixed filter table)
+  else if (g_type == RSRGAN_G_BNLSTM) { c->g_layers = 3; c->g_cells = 760; c->g_proj = 280; }    // models/bnlstm.py:41-43
   else { set_error("Unrecognized G type %d", g_type); return RSRGAN_ERR_INVALID; }
   c->d_type = RSRGAN_D_LSTM; c->d_layers = 2; c->d_cells = 256; c->d_proj = 40;                   // models/discriminator_lstm.py:26-28
   c->l2_scale = 0.f; c->clip_norm = 15.f;
@@ -67,6 +68,7 @@ int rsrgan_default_cfg(int32_t g_type, rsrgan_cfg* c) {
     c->d_joint_off = 257 * 5; c->d_joint_dim = 257; c->clip_norm = 0.f; c->batch_size = 1024; c->max_frames = 1;
   } c->adam_beta1 = 0.9f; c->adam_beta2 = 0.999f; c->adam_eps = 1e-8f;
   c->ema_decay = 0.9999f; c->lrelu_alpha = 0.3f; c->forget_bias = 1.0f; c->cross_validation = 0; c->flags = 0;
+  if (g_type == RSRGAN_G_BNLSTM) c->lrelu_alpha = 0.f;            // bnlstm.py:104: the input FC's activation is relu
   return RSRGAN_OK;
 }
 
@@ -314,6 +316,7 @@ int rsrgan_set_dropout(rsrgan_handle h, float keep_prob, uint64_t seed) {
   CHECK_H(h);
   if (!(keep_prob > 0.f && keep_prob <= 1.f)) { set_error("keep_prob=%g outside (0, 1]", (double)keep_prob); return RSRGAN_ERR_INVALID; }
   Model& m = h->m;
+  if (keep_prob < 1.f && m.g_bnl()) { set_error("g_type bnlstm: DropoutWrapper (keep_prob < 1) is not built"); return RSRGAN_ERR_INVALID; }
   if (keep_prob < 1.f && !m.g_dnn()) {
     for (const LstmLayer& L : m.gl)
       if (!L.has_proj) { set_error("DropoutWrapper is built for generator layers with a projection (num_proj) only"); return RSRGAN_ERR_INVALID; }

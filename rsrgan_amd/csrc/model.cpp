@@ -46,7 +46,7 @@ int ParamSet::add(const std::string& name, int rows, int cols, bool is_vector) {
 
 // ------------------------------------------------------------------------------------------ hipGraph segments
 static inline uint64_t seg_key(int seg, int T, unsigned bits) { return ((uint64_t)seg << 48) | ((uint64_t)(unsigned)T << 16) | (bits & 0xffffu); }
-enum { SEG_D = 1, SEG_G_MAIN = 2, SEG_G_FCIN = 3, SEG_G_LAYER0 = 4 /* .. + MAXJ */, SEG_G_L2 = 20, SEG_G_TAIL = 21, SEG_APPLY_D = 22, SEG_APPLY_G = 23, SEG_G_BATCH = 24 };
+enum { SEG_D = 1, SEG_G_MAIN = 2, SEG_G_FCIN = 3, SEG_G_LAYER0 = 4 /* .. + MAXJ */, SEG_G_L2 = 20, SEG_G_TAIL = 21, SEG_APPLY_D = 22, SEG_APPLY_G = 23, SEG_G_BATCH = 24, SEG_BNL = 25 };
 
 template <class F>
 void Model::run_seg(uint64_t key, hipStream_t s, F&& body) {
@@ -199,6 +199,7 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     }
     out.push_back(F);
   };
+  if (g_bnl()) { const int rc = bnl_check(c); if (rc) return rc; }
   if (bn_on() && !g_dnn()) {
     set_error("RSRGAN_FLAG_BATCH_NORM is built for the frame-level generators (dnn, rced) + discriminator_dnn only");
     return RSRGAN_ERR_INVALID;
@@ -255,6 +256,8 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     }
     g_fc_out_w = G.add("g_model/forward_out/fully_connected/weights", P, Dout, false);
     g_fc_out_b = G.add("g_model/forward_out/fully_connected/biases", 1, Dout, true);
+  } else if (g_bnl()) {                                                  // models/bnlstm.py:101-123
+    bnl_params();
   } else {
     set_error("Unrecognized G type %d", c.g_type);                       // gan_rnn_placeholder.py:131-132
     return RSRGAN_ERR_INVALID;
@@ -277,7 +280,7 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   {
     static const bool pad_env = [] { const char* e = getenv("RSRGAN_PAD_ROWS"); return !e || atoi(e) != 0; }();
     const int Bp = (Bt + GP_ROWS - 1) / GP_ROWS * GP_ROWS;
-    if (pad_env && gp_env && Bp != Bt && !g_dnn() && !d_dnn() && wavefront()) {
+    if (pad_env && gp_env && Bp != Bt && !g_dnn() && !g_bnl() && !d_dnn() && wavefront()) {
       B = Bp;
       GPersistArgs ga{};
       if (!gpersist_shape(ga, std::min(Tmax, (int)GP_TMAX))) B = Bt;     // (only where the padded batch does take the persistent path)
@@ -362,6 +365,9 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     g_act.push_back(x_tm);
     for (size_t l = 0; l + 1 < gfc.size(); ++l) g_act.push_back(alloc<float>(TB * gfc[l].ld_out));
     g_act.push_back(y_tm);
+  } else if (g_bnl()) {
+    const int rc = bnl_alloc();
+    if (rc) return rc;
   } else if (c.g_type == RSRGAN_G_LSTM) {
     g_h0 = alloc<float>(TB * ldP);
     g_ins[0] = g_h0;
@@ -470,7 +476,7 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
       else dw_ws = nullptr;
     }
   }
-  if (gp_env && !g_dnn()) {
+  if (gp_env && !g_dnn() && !g_bnl()) {
     GPersistArgs ga{};
     gp_Tcap = std::min(Tmax, (int)GP_TMAX);
     gp_noproj = !gl.empty() && !gl[0].has_proj;
@@ -586,7 +592,8 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   std::mt19937_64 rng(seed);
   for (ParamSet* ps : {&G, &D}) {
     std::vector<float> host((size_t)ps->padded, 0.f);
-    for (auto& t : ps->t) {
+    if (ps == &G && g_bnl()) bnl_init(host, seed);
+    else for (auto& t : ps->t) {
       if (!t.l2) {                                           // biases: zero, except R-CED's output FC (rced.py:116: 0.1)
         if (t.bias_init != 0.f)
           for (int cc = 0; cc < t.cols; ++cc) host[(size_t)t.off + cc] = t.bias_init;
@@ -1752,6 +1759,7 @@ void Model::g_forward_tail(int T, hipStream_t s) {   // y = outputs.W + b (model
 }
 void Model::g_forward(int T, hipStream_t s, Chain* extra) {
   if (g_dnn()) { bn_eval_call = false; g_frame_forward(T * B, s); g_fwd_valid = true; return; }
+  if (g_bnl()) { bnl_forward(T, false, s); return; }      // (rsrgan_forward_g: decode normalises with the moving statistics)
   g_forward_head(T, s);
   if (!extra && persist_forward_g(T, s)) { g_forward_tail(T, s); return; }
   std::vector<Chain> chains;
@@ -1956,6 +1964,7 @@ int Model::g_backward(const float* x, const float* labels, const int32_t* length
                       float* out_losses, bool want_grads, bool reuse, hipStream_t s) {
   if (!labels) { set_error("labels required"); return RSRGAN_ERR_INVALID; }
   if (g_dnn()) return dnn_g_backward(x, labels, T, out_losses, want_grads, reuse, s);
+  if (g_bnl()) return bnl_step(x, labels, lengths, T, out_losses, want_grads, s);
   bn_eval_call = !want_grads;                      // (is_training of this fetch)
   dfree_current = false;                           // this run reads and writes the discriminator's stash
   if (seq_drop_on()) { reuse = false; launch_drop_tick(drop_ctr, s); }     // a new sess.run: new DropoutWrapper masks, a new forward
@@ -2253,6 +2262,38 @@ int Model::g_backward(const float* x, const float* labels, const int32_t* length
     finish_buckets(RSRGAN_NET_G, s);
     g_grads_ready = true;
   }
+  if (out_losses) launch_copy_f(losses + 3, out_losses, 4, s);
+  HIPC(hipGetLastError());
+  return RSRGAN_OK;
+}
+
+// the bnlstm trainer's step (models/rnn_trainer.py:131-156 on models/bnlstm.py): g_loss = 0.5*Dout*mse + l2.  A training fetch
+// (gradients on a cross_validation=0 handle) normalises with each step's batch statistics and advances the moving statistics;
+// an evaluation fetch normalises with the moving statistics.  One graph segment per (T, kind of fetch).
+int Model::bnl_step(const float* x, const float* labels, const int32_t* lengths, int T, float* out_losses, bool want_grads, hipStream_t s) {
+  if (want_grads && cfg.cross_validation) {
+    set_error("g_type bnlstm: gradients of the cross_validation model (moving-statistics batch norm) are not built");
+    return RSRGAN_ERR_INVALID;
+  }
+  int rc = prepare_batch(x, labels, lengths, T, s);
+  if (rc) return rc;
+  const bool l2s = want_grads && scal[RSRGAN_L2_SCALE] > 0.0;
+  run_seg(seg_key(SEG_BNL, T, (want_grads ? 1u : 0u) | (l2s ? 2u : 0u)), s, [&]() {
+    bnl_forward(T, want_grads, s);
+    (void)hipMemsetAsync(losses + 3, 0, sizeof(float), s);
+    float* dy = want_grads ? g_dC : nullptr;
+    launch_mse(y_tm, lab_tm, ldDout, dy, T * B, Dout, dyn + DYN_LAMBDA, false, losses + 4, scratch, s, pad_Bp(), Bt);
+    if (want_grads) bnl_backward(T, dy, s);
+    if (l2s) {
+      launch_l2(G.w, G.g, G.ct, dyn + DYN_L2, G.partial, s);
+      launch_l2_total(G.partial, G.ct.n_chunks, dyn + DYN_L2, losses + 5, s);
+    } else {
+      (void)hipMemsetAsync(losses + 5, 0, sizeof(float), s);
+    }
+    launch_g_total(losses + 3, dyn + DYN_LAMBDA, s);
+  });
+  if (want_grads) { finish_buckets(RSRGAN_NET_G, s); g_grads_ready = true; }
+  g_fwd_valid = false;
   if (out_losses) launch_copy_f(losses + 3, out_losses, 4, s);
   HIPC(hipGetLastError());
   return RSRGAN_OK;

@@ -115,6 +115,38 @@ struct FcStage {
   bool accumulate = false;
 };
 
+// ---- recurrent batch-norm LSTMP generator (bnlstm.cpp / bnlstm.hip; models/bnlstm.py, models/BNLSTMCell.py) ----
+// Device view of one BNLSTMCell layer for the step kernels (by value: a captured graph holds it).  Row-major [t][b][...] buffers
+// over exactly the caller's B rows (never padded: every row enters every step's batch statistics).
+struct BnlLayer {
+  int B, H, P, ldP, ldH, nst;                 // nst = 9H: the statistics of one step, sites input [0, 4H) | state [4H, 8H) | cell [8H, 9H)
+  int train;                                  // batch statistics (and their stash) vs the moving statistics
+  float eps, fb;                              // 1e-3, forget_bias
+  const int* len;
+  const float *Whh, *Wp, *bias, *wf, *wi, *wo;                          // state_kernel [P][4H], projection/kernel [H][ldP], ...
+  const float *sc_in, *of_in, *sc_s, *of_s, *sc_c, *of_c;
+  float *mm_in, *mv_in, *mm_s, *mv_s, *mm_c, *mv_c;                     // moving_mean / moving_var of the three sites
+  float *xh_in, *yin, *xh_s, *act, *cnew, *chat, *ccar, *h, *mst, *out; // act: i j f o activations; ccar / mst: [T+1] carried states
+  float *mu, *var;                                                      // [T][nst] batch moments of each step
+  const float* dout;                                                    // [T][B][ldP] gradient of the masked outputs
+  float *dz, *dhh, *dyc, *dmn, *dcc, *dmc;                              // dz, d(hh) [T][B][4H]; d(BN_cell) [T][B][ldH]; dm_new [T][B][ldP];
+                                                                        // carried dc [B][ldH] / dm [B][ldP]
+};
+struct BnlCell {                 // parameter indices and buffers of one layer
+  int tWx, tWh, tin[4], tst[4], tb, twf, twi, two, tce[4], tWp;      // tin / tst / tce: scale offset moving_mean moving_var
+  float *zx = nullptr, *xh_in = nullptr, *yin = nullptr, *xh_s = nullptr, *act = nullptr, *cnew = nullptr, *chat = nullptr;
+  float *ccar = nullptr, *h = nullptr, *mst = nullptr, *out = nullptr, *mu = nullptr, *var = nullptr;
+  float *dz = nullptr, *dyc = nullptr, *dmn = nullptr, *dcc = nullptr, *dmc = nullptr;
+};
+bool bnl_supported(int B);                  // rows of a step fit one workgroup (B <= 64)
+void launch_bnl_bn_in(const BnlLayer& a, const float* zx, int T, hipStream_t s);
+void launch_bnl_cell_fwd(const BnlLayer& a, int t, hipStream_t s);
+void launch_bnl_proj(const BnlLayer& a, int t, hipStream_t s);
+void launch_bnl_ema(const BnlLayer& a, int T, float decay, hipStream_t s);
+void launch_bnl_cell_bwd(const BnlLayer& a, int t, hipStream_t s);
+void launch_bnl_dm(const BnlLayer& a, int t, hipStream_t s);
+void launch_bnl_bn_in_bwd(const BnlLayer& a, float* dzx, int T, hipStream_t s);
+
 struct Model {
   rsrgan_cfg cfg{};
   int B = 0, Tmax = 0, Din = 0, Dout = 0, ldDin = 0, ldDout = 0;
@@ -208,6 +240,17 @@ struct Model {
   int *adam_t_dev_d = nullptr;
   bool g_dnn() const { return cfg.g_type == RSRGAN_G_DNN || cfg.g_type == RSRGAN_G_RCED; }   // frame-level generator
   bool g_rced() const { return cfg.g_type == RSRGAN_G_RCED; }
+  // bnlstm generator (bnlstm.cpp): input FC + ReLU, BNLSTMCell layers, output FC; supervised trainer only
+  std::vector<BnlCell> bnl;
+  bool g_bnl() const { return cfg.g_type == RSRGAN_G_BNLSTM; }
+  int bnl_check(const rsrgan_cfg& c) const;                                // the configurations it is built for
+  void bnl_params();                                                       // the variable table (reference creation order)
+  int bnl_alloc();
+  void bnl_init(std::vector<float>& host, uint64_t seed) const;            // initial values of G
+  BnlLayer bnl_args(int l, bool train) const;
+  void bnl_forward(int T, bool train, hipStream_t s);
+  void bnl_backward(int T, float* dy, hipStream_t s);
+  int bnl_step(const float* x, const float* labels, const int32_t* lengths, int T, float* out_losses, bool want_grads, hipStream_t s);
   // R-CED generator (dnn.cpp): rc_act[l] = input of conv layer l as [M][ldCin] positions x channels, rc_act[L] = its output
   std::vector<ConvLayer> gconv;
   FcLayer rc_fc{};

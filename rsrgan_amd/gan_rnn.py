@@ -25,7 +25,12 @@ NET_G, NET_D = 0, 1
 
 
 def _bn_statistic(name):
-    return "/BatchNorm/" in name and name.rsplit("/", 1)[-1] not in ("beta", "gamma")
+    """batch-norm statistics (no trainable variables, so no EMA shadow): contrib BatchNorm's, and the moving statistics of the
+    BNLSTMCell sites (models/BNLSTMCell.py:29-32)"""
+    leaf = name.rsplit("/", 1)[-1]
+    if "/bnlstm_cell/" in name:
+        return leaf in ("moving_mean", "moving_var")
+    return "/BatchNorm/" in name and leaf not in ("beta", "gamma")
 
 
 class Model(object):
@@ -177,6 +182,7 @@ class GAN_RNN(Model):
     `sess` is accepted and ignored (there is no session); `devices` is the list the reference
     iterates over (:153) -- here exactly one entry per process.  Extra keyword-only arguments
     are the knobs the reference hard-codes or has no notion of."""
+    G_TYPES = ("lstm", "res_lstm_l", "res_lstm_base")        # generator types this model accepts (:125-132)
 
     def __init__(self, sess, args, devices, cross_validation=False, infer=False, name="GAN_RNN", *,
                  max_frames: Optional[int] = None, engine=None, process_group=None, seed: int = 4321,
@@ -205,7 +211,7 @@ class GAN_RNN(Model):
         self.gen_updates = getattr(args, "gen_updates", 1)
         self.d_clip_weights = False
         self.g_type = args.g_type
-        if self.g_type not in ("lstm", "res_lstm_l", "res_lstm_base"):
+        if self.g_type not in self.G_TYPES:
             raise ValueError("Unrecognized G type {}".format(self.g_type))      # :131-132
         self.process_group = process_group
         self.infer = infer

@@ -6,11 +6,17 @@ with RSRGAN_FLAG_SUPERVISED: no discriminator pass is launched and rsrgan_d_step
 
 The reference bakes tf.data tensors (`inputs, labels, lengths`) into the graph; here batches are passed to
 `step()`, which returns the three per-tower lists the caller fetches (g_mse_losses, g_l2_losses, g_losses:
-scripts/train_rnn.py / train_dnn.py fetch [model.g_opt, model.g_losses, ...])."""
+scripts/train_rnn.py / train_dnn.py fetch [model.g_opt, model.g_losses, ...]).
+
+RNNTrainer also takes the reference's g_type 'bnlstm' (models/bnlstm.py: input FC + ReLU, 3 x BNLSTMCell(760, num_proj=280) with
+batch normalisation inside the recurrence, output FC).  A training step normalises with each time step's batch statistics over
+the rows of the batch and advances the moving statistics; the cross_validation twin, a train=False fetch and forward() normalise
+with the moving statistics.  Without dropout, without the input FC's batch_norm, one process (the moving statistics are per rank)."""
 from __future__ import annotations
 
 from typing import Optional
 
+from . import dist as rdist
 from .gan import GAN
 from .gan_rnn import GAN_RNN
 
@@ -24,11 +30,19 @@ class _Args(object):
 
 
 class RNNTrainer(GAN_RNN):
-    """models/rnn_trainer.py:66 -- g_type in {lstm, res_lstm_l, res_lstm_base} (bnlstm / res_lstm_i are not built)."""
+    """models/rnn_trainer.py:66 -- g_type in {lstm, res_lstm_l, res_lstm_base, bnlstm} (res_lstm_i is not built)."""
+    G_TYPES = GAN_RNN.G_TYPES + ("bnlstm",)
 
     def __init__(self, sess, args, devices, inputs=None, labels=None, lengths=None, cross_validation=False,
                  name="RNNTrainer", *, max_frames: Optional[int] = None, engine=None, process_group=None, seed: int = 4321,
                  net_overrides: Optional[dict] = None, share_engine_from=None):
+        if getattr(args, "g_type", None) == "bnlstm":
+            if getattr(args, "batch_norm", False):
+                raise NotImplementedError("bnlstm: the input FC's batch_norm (renorm) is not built")
+            if not cross_validation and getattr(args, "keep_prob", 1.0) < 1.0:
+                raise NotImplementedError("bnlstm: DropoutWrapper (keep_prob < 1) is not built")
+            if rdist.world_size(process_group) > 1:
+                raise NotImplementedError("bnlstm: one process only (the moving statistics are not combined across ranks)")
         ov = dict(net_overrides or {})
         ov["flags"] = ov.get("flags", FLAG_WAVEFRONT) | FLAG_SUPERVISED
         super(RNNTrainer, self).__init__(sess, _Args(args, init_mse_weight=1.0), devices, cross_validation=cross_validation,
