@@ -228,7 +228,11 @@ int rsrgan_profile_read(rsrgan_handle h, int32_t* launches, double* total_us, do
  * above layer 0; in the G-run the launch is k_glstm_bwd_dt, which also carries the discriminator's BPTT in its trailing form,
  * csrc/dpersist_dev.h: that half's state- and input-gradient products, dh = dm . W_p^T and dy . W_out^T are counted too), kind 3 =
  * k_glstm_fwd_dt, the forward launch with D(G(x)) trailing inside it (the D-run under RSRGAN_DPIPE, every G-run that recomputes the
- * forward): the NUMBER of launches only (total_us and alg_flops come back 0).  Call before rsrgan_profile_read (which closes the window). */
+ * forward): the NUMBER of launches only (total_us and alg_flops come back 0).  Kinds 4..8 are counts only as well (counted on the host
+ * where the launch is enqueued): 4 = the stand-alone discriminator forward launches (k_dlstm_fwd, k_dlstm_fwd_t, D(real) under
+ * RSRGAN_DPIPE), 5 = the stand-alone discriminator BPTT launches (k_dlstm_bwd), 6 = those of kind 5 that carry the weight-gradient
+ * workgroups inside the launch, 7 = k_glstm_np_fwd and 8 = k_glstm_np_bwd (the unprojected generator's forward and BPTT launches).
+ * Call before rsrgan_profile_read (which closes the window). */
 int rsrgan_profile_read_kind(rsrgan_handle h, int32_t kind, int32_t* launches, double* total_us, double* alg_flops);
 
 /* Health of the persistent recurrence kernels (csrc/dpersist.hip, csrc/gpersist.hip): synchronises the handle's stream and returns in

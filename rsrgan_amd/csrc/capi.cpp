@@ -309,6 +309,7 @@ int rsrgan_grad_bucket_wait(rsrgan_handle h, int32_t net, int32_t i, void* strea
 int rsrgan_profile_begin(rsrgan_handle h) {
   CHECK_H(h);
   h->m.prof_on = true; h->m.prof_n = 0; h->m.prof_flops = 0.0; h->m.prof_gp_n = 0; h->m.prof_gp_flops = 0.0; h->m.prof_gb_n = 0; h->m.prof_gb_flops = 0.0; h->m.prof_fdt_n = 0;
+  for (int& c : h->m.prof_cnt) c = 0;
   g_chain_launches = 0;
   return RSRGAN_OK;
 }
@@ -385,6 +386,10 @@ int rsrgan_profile_read_kind(rsrgan_handle h, int32_t kind, int32_t* launches, d
   Model& m = h->m;
   if (kind == 3 && launches && total_us && alg_flops) {            // k_glstm_fwd_dt launches since profile_begin: a count only (not bracketed)
     *launches = m.prof_fdt_n; *total_us = 0.0; *alg_flops = 0.0;
+    return RSRGAN_OK;
+  }
+  if (kind >= 4 && kind <= 8 && launches && total_us && alg_flops) {   // count-only kinds (model.h prof_cnt)
+    *launches = m.prof_cnt[kind]; *total_us = 0.0; *alg_flops = 0.0;
     return RSRGAN_OK;
   }
   if ((kind != 1 && kind != 2) || !launches || !total_us || !alg_flops) { set_error("profile_read_kind: bad argument"); return RSRGAN_ERR_INVALID; }

@@ -512,7 +512,11 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
       gp_gran2_bytes = gpersist_gran2_bytes(ga);
       gp_gran2 = (unsigned long long*)alloc<float>(gp_gran2_bytes / sizeof(float));
       gp_ctl = (unsigned*)alloc<float>(16);
-      if (gp_env & 2) gp_gran3 = (unsigned long long*)alloc<float>(gpersist_gran3_bytes(ga) / sizeof(float));
+      // the BPTT launch's hand-offs time out when a layer's recurrent width is a single 16-column block (P <= 16: seen at H = 64 and
+      // 128, the bounded waits expire and the step is poisoned): such a stack keeps the persistent forward, its BPTT takes the launch path
+      bool bwd_ok = (gp_env & 2) != 0;
+      for (auto& L : gl) bwd_ok = bwd_ok && L.P > 16;
+      if (bwd_ok) gp_gran3 = (unsigned long long*)alloc<float>(gpersist_gran3_bytes(ga) / sizeof(float));
       if (gp_gran1 && gp_gran2 && gp_ctl) {
         const unsigned ctl0[DP_CTL_WORDS] = {1u, 0u, 0u, 0u};
         HIPC(hipMemcpy(gp_ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice));
@@ -1038,6 +1042,7 @@ bool Model::persist_forward(Chain& ch, int T, hipStream_t s) {
   if (!dpersist_supported(a) || dpersist_grid(a.nl, a.N) > dp_max_grid || dpersist_granule_bytes(a.nl, a.N, a.T) > dp_gran_bytes) return false;
   static const bool fwd_t_env = [] { const char* e = getenv("RSRGAN_DFWD_T"); return e && atoi(e) != 0; }();
   if (fwd_t_env && a.N % 32 == 0) launch_dlstm_fwd_t(a, s); else launch_dlstm_fwd(a, s);
+  if (prof_on) ++prof_cnt[4];
   return true;
 }
 
@@ -1156,6 +1161,7 @@ bool Model::persist_forward_g(int T, hipStream_t s) {
   if (gp_noproj) {                                     // num_proj=None: the single-hop form (no event bracket: bench.py's dominant-kernel timing is the projected form's)
     for (size_t l = 0; l < gl.size(); ++l) a.L[l].Wp = nullptr;
     launch_glstm_np_fwd(a, s);
+    if (prof_on) ++prof_cnt[7];
     return true;
   }
   if (prof_on) {
@@ -1199,6 +1205,7 @@ bool Model::persist_forward_real(int T, hipStream_t q, bool check_only) {
   if (!dpersist_supported(a) || dpersist_grid(a.nl, a.N) > dp_max_grid || T > Tmax) return false;
   if (check_only) return true;
   launch_dlstm_fwd(a, q);
+  if (prof_on) ++prof_cnt[4];
   return true;
 }
 
@@ -1255,6 +1262,7 @@ bool Model::persist_backward_g(Chain& ch, int T, hipStream_t s, bool check_only,
     if (!a.dout_top) return false;
     if (check_only) return true;
     launch_glstm_np_bwd(a, s);
+    if (prof_on) ++prof_cnt[8];
     if (!defer_wgrads) chain_wgrads(ch, T, s, nullptr, pre, post);
     else { if (pre) pre(s); if (post) post(s); }
     return true;
@@ -1343,6 +1351,7 @@ bool Model::persist_backward(Chain& ch, int T, hipStream_t s) {
   for (auto& R : ch) dw = dw && R.want_wgrads && R.in && R.ps == &D;
   if (dw) { a.dw_ws = dw_ws; a.dw_flag = dw_flag; a.dw_stride = dw_stride; }
   launch_dlstm_bwd(a, s);
+  if (prof_on) { ++prof_cnt[5]; if (dw) ++prof_cnt[6]; }
   if (dw) {
     launch_dw_reduce(dw_ws, dw_stride, a.N / 16, dw_src, D.g, D.ct, D.partial, s);
     d_partial_fresh = true;

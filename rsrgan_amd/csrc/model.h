@@ -377,6 +377,10 @@ struct Model {
   std::vector<hipEvent_t> prof_gb_ev;
   int prof_gb_n = 0;
   int prof_fdt_n = 0;               // fused forward launches (k_glstm_fwd_dt) since profile_begin
+  // count-only kinds 4..8 of rsrgan_profile_read_kind (launches since profile_begin, counted on the host at the launch sites): 4 = the
+  // stand-alone discriminator forward launches (k_dlstm_fwd, k_dlstm_fwd_t, D(real) under RSRGAN_DPIPE), 5 = stand-alone k_dlstm_bwd,
+  // 6 = those of 5 that carry the in-kernel weight-gradient workgroups (dw_ws), 7 = k_glstm_np_fwd, 8 = k_glstm_np_bwd
+  int prof_cnt[9] = {};
   double prof_gb_flops = 0.0;
   void gates_launch(const FwdGateJobs& gj, int blocks, int kb, hipStream_t s);
   int gates_blocks(int H, int N) const;

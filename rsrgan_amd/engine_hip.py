@@ -371,7 +371,10 @@ class HipEngine:
         check(self.lib.rsrgan_profile_begin(self.h))
 
     def profile_read_kind(self, kind):
-        """(launches, total_us, algorithmic_flops) of kernel class `kind` (1 = k_glstm_fwd) since profile_begin; call before profile_read"""
+        """(launches, total_us, algorithmic_flops) of kernel class `kind` since profile_begin; call before profile_read.
+        1 = k_glstm_fwd, 2 = k_glstm_bwd (timed); count only (total_us = alg_flops = 0): 3 = k_glstm_fwd_dt, 4 = stand-alone discriminator
+        forward launches (k_dlstm_fwd, k_dlstm_fwd_t, D(real) under RSRGAN_DPIPE), 5 = stand-alone k_dlstm_bwd, 6 = those of 5 with the
+        weight gradients inside the launch, 7 = k_glstm_np_fwd, 8 = k_glstm_np_bwd"""
         n, us, fl = C.c_int32(), C.c_double(), C.c_double()
         check(self.lib.rsrgan_profile_read_kind(self.h, kind, C.byref(n), C.byref(us), C.byref(fl)))
         return n.value, us.value, fl.value

@@ -58,12 +58,23 @@ def _check_vars(got, want, tol, names):
         assert _err(got[k], want[k]) < tol, (k, _err(got[k], want[k]))
 
 
-SMALL = [(1, 1, None), (5, 3, 5), (40, 1, None)]      # (B, flags, longest length): B=5 replays hipGraphs and ends before T
+# (B, flags, longest length): B=5 replays hipGraphs and ends before T; the kernels run ceil(B / 16) row tiles: 1 .. 4 (B = 64, the
+# largest batch the C ABI takes)
+SMALL = [(1, 1, None), (5, 3, 5), (40, 1, None), (24, 1, None), (64, 3, None)]
 
 
 @pytest.mark.parametrize("B,flags,tmax", SMALL)
 def test_small_against_oracle(B, flags, tmax):
-    L, H, P, din, dout, T = 2, 12, 7, 6, 5, 7
+    _small_case(B, flags, tmax, 2, 12, 7, 6, 5, 7)
+
+
+def test_wide_cell_partial_tiles_against_oracle():
+    """K > 128 (layer 1's input and every state kernel read P = 150 columns) and partial 16-column tiles (H = 100, P = 150), three
+    row tiles with a one-row last tile (B = 33)"""
+    _small_case(33, 1, None, 2, 100, 150, 24, 20, 6)
+
+
+def _small_case(B, flags, tmax, L, H, P, din, dout, T):
     specs = R.param_specs(din, dout, L, H, P)
     p0 = R.rand_params(specs, 11)
     m = _trainer(B, T, L, H, P, din, dout, flags, l2_scale=1e-3)
@@ -113,6 +124,24 @@ def test_full_size_against_oracle():
     m.set_vars(p0, None)
     o = R.BnlstmOracle(p0, L, output_dim=dout)
     x, lab, ln = _batch(B, T, din, dout, 9)
+    got = m.engine.g_backward(x, lab, ln, None, train=True, apply=False).cpu().numpy()
+    want, wg, mom = o.tower(x, lab, ln, train=True)
+    assert np.allclose(got[1:], want[1:], rtol=1e-4), (got, want)
+    gr = split_flat(m.engine.get_grads(NET_G).cpu().numpy(), m.engine.tensor_table(NET_G))
+    _check_vars(gr, wg, 2e-3, wg)
+    o.update_moving(mom)
+    _check_vars(_g(m), o.params(), 1e-4, o.moving)
+
+
+def test_full_size_four_row_tiles_against_oracle():
+    """the full-width cell (3 x BNLSTMCell(760, num_proj=280)) at B = 64 (four 16-row tiles), T = 12, ragged: gradients and moving statistics"""
+    L, H, P, din, dout, B, T = 3, 760, 280, 40, 40, 64, 12
+    specs = R.param_specs(din, dout, L, H, P)
+    p0 = R.rand_params(specs, 5)
+    m = _trainer(B, T, L, H, P, din, dout, FLAG_WAVEFRONT | FLAG_GRAPH)
+    m.set_vars(p0, None)
+    o = R.BnlstmOracle(p0, L, output_dim=dout)
+    x, lab, ln = _batch(B, T, din, dout, 13)
     got = m.engine.g_backward(x, lab, ln, None, train=True, apply=False).cpu().numpy()
     want, wg, mom = o.tower(x, lab, ln, train=True)
     assert np.allclose(got[1:], want[1:], rtol=1e-4), (got, want)

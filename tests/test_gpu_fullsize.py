@@ -140,6 +140,7 @@ def test_full_size_schedules_agree_and_padding_is_inert():
 # (gan_rnn_placeholder.py:207-213,244-260; train_gan_rnn_placeholder.py:72-101).  The ACHIEVED errors are written to
 # gpurun_out/parity_margin/<case>.json; tools/mk_parity_margin.py folds them into profiles/r6_parity_margin.json, which bench.py
 # quotes in its JSON line ("parity_margin").
+import hashlib
 import json
 import os
 import subprocess
@@ -247,10 +248,21 @@ print("RESULT " + json.dumps(res))
 """ % _ROOT
 
 
+def _oracle_cache_key(net, B, T, seed):
+    """the cached oracle results are those of this oracle: keyed on its source (and the helpers that feed it), the case and the seed"""
+    h = hashlib.sha256()
+    for rel in ("oracle/rsrgan_oracle.py", "tests/helpers.py"):
+        with open(os.path.join(_ROOT, rel), "rb") as f:
+            h.update(f.read())
+    h.update(("%s %d %d %d" % (net, B, T, seed)).encode())
+    return h.hexdigest()[:24]
+
+
 def _as_benched(net, B, T, dpipe, tags):
-    env = dict(os.environ, RSRGAN_TEST_NET=net, RSRGAN_TEST_B=str(B), RSRGAN_TEST_T=str(T), RSRGAN_TEST_SEED=str(500 + B),
-               RSRGAN_DPIPE=str(dpipe), RSRGAN_GP_TAGS=str(tags),
-               RSRGAN_TEST_ORACLE_CACHE=os.path.join(tempfile.gettempdir(), "rsrgan_oracle_asbenched2_%s_%d_%d.npz" % (net, B, T)))
+    seed = 500 + B
+    cache = os.path.join(tempfile.gettempdir(), "rsrgan_oracle_asbenched_%s_%d_%d_%s.npz" % (net, B, T, _oracle_cache_key(net, B, T, seed)))
+    env = dict(os.environ, RSRGAN_TEST_NET=net, RSRGAN_TEST_B=str(B), RSRGAN_TEST_T=str(T), RSRGAN_TEST_SEED=str(seed),
+               RSRGAN_DPIPE=str(dpipe), RSRGAN_GP_TAGS=str(tags), RSRGAN_TEST_ORACLE_CACHE=cache)
     p = subprocess.run([sys.executable, "-c", _AS_BENCHED], capture_output=True, text=True, env=env, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     res = json.loads([l for l in p.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
