@@ -305,8 +305,7 @@ __global__ __launch_bounds__(256) void k_bn_elem_narrow(const float* __restrict_
 }
 
 static bool bn_narrow(int rows, int cols, int l0, int l1, int l2) {
-  static int minrows = -1;                 // RSRGAN_BN_NARROW: least row count that takes this form (0 = never; tests set 1)
-  if (minrows < 0) { const char* e = getenv("RSRGAN_BN_NARROW"); minrows = e ? std::max(0, atoi(e)) : 4096; }
+  const int minrows = switches().bn_narrow;            // RSRGAN_BN_NARROW: least row count that takes this form (0 = never; tests set 1)
   const int ld = (cols + 3) & ~3;
   return minrows > 0 && ld <= 64 && rows >= minrows && l0 == ld && l1 == ld && l2 == ld;
 }
@@ -338,8 +337,7 @@ __global__ __launch_bounds__(256) void k_bn_commit(int cols, BnVars v, const flo
 // ---- few rows (the shipped frame-level batch: 256 frames): one launch per direction.  A workgroup owns 16 columns and all rows of
 // every call (the discriminator's real | fake halves are consecutive calls): 16 row lanes sum a column, LDS reduces them in a fixed
 // order, the column threads finish the moments / gradients, then the workgroup re-reads its (L2-resident) columns for the
-// elementwise pass. ----
-static int bn_small_rows() { static int v = -1; if (v < 0) { const char* e = getenv("RSRGAN_BN_SMALL_ROWS"); v = e ? atoi(e) : 384; } return v; }
+// elementwise pass.  RSRGAN_BN_SMALL_ROWS: the most rows that take it. ----
 
 constexpr int BNS_CW = 16, BNS_RL = 16;          // small path: 16 columns x 16 row lanes per workgroup (cols / 16 workgroups)
 
@@ -492,7 +490,7 @@ static int bn_slices(int rows, int cols, size_t scratch_floats, int* per) {
 // `calls` consecutive calls of `rows` rows each (statistics slots 0 .. calls-1 of `stat`)
 void launch_bn_forward(const float* z, int ldz, float* y, int ldy, int rows, int cols, const BnVars& v, float* stat, int ldc, bool training,
                        bool relu, float* scratch, size_t scratch_floats, hipStream_t s, int calls) {
-  if (rows <= bn_small_rows() && cols >= 64) {
+  if (rows <= switches().bn_small_rows && cols >= 64) {
     hipLaunchKernelGGL(k_bn_fwd_small, dim3((cols + BNS_CW - 1) / BNS_CW), dim3(256), 0, s, z, ldz, y, ldy, rows, cols, calls, v, stat, ldc,
                        training ? 1 : 0, relu ? 1 : 0);
     return;
@@ -527,7 +525,7 @@ void launch_bn_forward(const float* z, int ldz, float* y, int ldy, int rows, int
 void launch_bn_backward(float* dy, int ldd, const float* y, int ldy, const float* z, int ldz, int rows, int cols, const float* stat, int ldc,
                         float* dbeta, float* dgamma, bool accumulate, bool relu, float* sums, float* scratch, size_t scratch_floats,
                         hipStream_t s, int calls) {
-  if (rows <= bn_small_rows() && cols >= 64 && !accumulate) {
+  if (rows <= switches().bn_small_rows && cols >= 64 && !accumulate) {
     hipLaunchKernelGGL(k_bn_bwd_small, dim3((cols + BNS_CW - 1) / BNS_CW), dim3(256), 0, s, dy, ldd, y, ldy, z, ldz, rows, cols, calls, stat, ldc, dbeta,
                        dgamma, relu ? 1 : 0);
     return;

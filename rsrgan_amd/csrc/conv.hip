@@ -951,14 +951,11 @@ static void conv_fwd_range(int wbase, int wend, int TW, int RT, size_t lds, cons
   // RSRGAN_CONV4: 0 = never the 4x4x1 form, 1 (default) = every output width that is a multiple of 4 except 16 (12 / 20 / 24 waste
   // 16-wide MFMA columns; at 32 the 4x4x1 kernel is ahead since it walks only the real channel quads, 16.4 vs 18.0 ms per call;
   // at 16 -- layers whose input has no channel pads -- the 16x16x4 kernel is, 8.7 vs 9.3), 2 = every multiple of 4
-  static int conv4 = -1;
-  if (conv4 < 0) { const char* e = getenv("RSRGAN_CONV4"); conv4 = e ? atoi(e) : 1; }
+  const int conv4 = switches().conv4;
   if (conv4 && N % 4 == 0 && ldc_out % 4 == 0 && (conv4 > 1 || N != 16) && (!bias || ((size_t)bias & 15) == 0)) {
     // RSRGAN_CONV4_KS=4: two interleaved group sets x k' quarters for 512-position workgroups (0.86 of the MFMAs of the default
     // four sets x k' halves at S = 11, measured slower: 566 vs 558 ms per step of the R-CED variant)
-    static int ks4 = -1;
-    if (ks4 < 0) { const char* e = getenv("RSRGAN_CONV4_KS"); ks4 = e ? atoi(e) : 2; }
-    const int G = small ? (ks4 == 4 ? 4 : 2) : 3, ncg = N / 4;
+    const int G = small ? (switches().conv4_ks == 4 ? 4 : 2) : 3, ncg = N / 4;
     const size_t lds4 = std::max(lds, (size_t)8 * ncg * 1024 * (G == 3 ? 2 : G == 4 ? 2 : 1));      // the tree's widest round
     if (lds4 <= 160 * 1024 && launch_conv_fwd4(G, ncg, grid, lds4, s, in, ldc_in, C, Ft, bias, rl, out, ldc_out, N, S, W, fw, TW, mask, wbase, wend, FB, R)) return;
   }
@@ -977,10 +974,8 @@ void launch_conv_fwd(const float* in, int ldc_in, int C, const float* Ft, const 
   // image rows, so the rows a filter row does not touch are skipped exactly and every lane of a full strip is a real position
   // (a 257-wide frame cut into 6 x 43 columns used 69 % / 80 % of the position slots of the 4x4x1 / 16x16x4 kernel).  The W % 64
   // columns that are left take a second launch with their own plan.
-  static int rows = -1;
-  if (rows < 0) { const char* e = getenv("RSRGAN_CONV_ROWS"); rows = e ? atoi(e) : 1; }
   const size_t lds64 = ((size_t)(S + 1) * ((64 + fw - 1) * conv_cpad(C) + 16) + (size_t)32 * conv_ldf(fw, C)) * sizeof(float);
-  if (rows && W > 64 && S * 64 <= 8 * 6 * 16 && lds64 <= 160 * 1024) {
+  if (switches().conv_rows && W > 64 && S * 64 <= 8 * 6 * 16 && lds64 <= 160 * 1024) {
     const int wmain = W / 64 * 64;
     conv_fwd_range(0, wmain, 64, 6, lds64, in, ldc_in, C, Ft, bias, rl, out, ldc_out, N, R, S, W, fw, s, mask);
     if (wmain < W) {
@@ -1010,21 +1005,20 @@ static int wgrad_tw(int S, int W) {          // narrower strips than the forward
   const int ns = (W + 31) / 32;
   return (W + ns - 1) / ns;
 }
-static int g_wgrad_dhmax = -1;        // RSRGAN_WGRAD_DH: most filter rows per workgroup for multi-strip frames (3 = round 2's form)
 static void wgrad_plan(int R, int S, int nstrips, int KP, int& DH, int& fpg, int& groups) {
-  if (g_wgrad_dhmax < 0) { const char* e = getenv("RSRGAN_WGRAD_DH"); g_wgrad_dhmax = e ? atoi(e) : 6; }
+  const int dhmax = switches().wgrad_dh;
   int best = 1 << 30;
   DH = 1; fpg = R; groups = 1;
   // multi-strip frames with one k'-tile per wave (K' <= 256): 4 or 6 rows per workgroup in the rows-inside form (its accumulators
   // fit the 128 registers of a 16-wave workgroup); the measure is the LDS operand reads + staged frames per MFMA
-  if (nstrips > 1 && KP > 16 * 16 && g_wgrad_dhmax >= 3) {        // two k'-tile rounds: 3 rows (accumulators: 3 x 2 x NT tiles)
+  if (nstrips > 1 && KP > 16 * 16 && dhmax >= 3) {        // two k'-tile rounds: 3 rows (accumulators: 3 x 2 x NT tiles)
     const int ng = (S + 2) / 3, gmax = std::max(1, 256 / (ng * nstrips));
     DH = 3; fpg = std::max(1, (R + gmax - 1) / gmax); groups = (R + fpg - 1) / fpg;
     return;
   }
-  if (nstrips > 1 && KP <= 16 * 16 && g_wgrad_dhmax > 3) {
+  if (nstrips > 1 && KP <= 16 * 16 && dhmax > 3) {
     for (int dhc : {6, 4}) {
-      if (dhc > g_wgrad_dhmax) continue;
+      if (dhc > dhmax) continue;
       const int ng = (S + dhc - 1) / dhc;
       if (ng * dhc - S >= dhc / 2 + 1) continue;                  // (too many empty rows in the last group)
       const int gmax = std::max(1, 256 / (ng * nstrips));
@@ -1129,8 +1123,7 @@ void launch_conv_wgrad(const float* in, int ldc_in, int C, const float* d, int l
   // every output width that is a multiple of 4 goes to the 4x4x1 form (measured: 502 ms per R-CED step against 509 with only the
   // widths that waste 16-wide MFMA columns; unlike the forward kernel it has no padded positions to pay for).  RSRGAN_WGRAD4: 0 =
   // never, 1 = widths that are no multiple of 16, 2 = all (default); RSRGAN_CONV4=0 alone turns both directions off.
-  static int w4 = -1;
-  if (w4 < 0) { const char* e = getenv("RSRGAN_CONV4"); const char* e2 = getenv("RSRGAN_WGRAD4"); w4 = e2 ? atoi(e2) : ((e && !atoi(e)) ? 0 : 2); }
+  const int w4 = switches().wgrad4 >= 0 ? switches().wgrad4 : (switches().conv4 ? 2 : 0);
   int nkg = 1, PS = 1, nwv4 = 8;
   wgrad4_plan(C, R, S, nstrips, fw, DH, fpg, groups, nkg, PS, nwv4);
   const bool use4 = w4 && N % 4 == 0 && N <= 32 && (w4 > 1 || N % 16 != 0) && nkg * ((DH + 2) / 3) <= 12 &&

@@ -982,11 +982,9 @@ void launch_layout(GemmArgs& g, hipStream_t s, float* ws, size_t ws_floats) {
   // 256 x 32 / 256 x 64: the window-view products of the first SEGAN layers have 16..64 output channels and ~1e5..1e6 rows
   // 256 x 256 / 128 x 256 / 256 x 128: k_gemm_s (four self-loading waves); RSRGAN_GEMM_SELF=0 leaves them out
   static const int cfgs[][2] = {{128, 128}, {96, 128}, {128, 96}, {256, 64}, {256, 32}, {256, 256}, {128, 256}, {256, 128}};
-  static int self = -1;
-  if (self < 0) { const char* e = getenv("RSRGAN_GEMM_SELF"); self = e ? atoi(e) : 1; }
   int best = 0;
   Plan bp{};
-  for (int c = 0; c < (self ? 8 : 5); ++c) {
+  for (int c = 0; c < (switches().gemm_self ? 8 : 5); ++c) {
     // the 256-wide tiles pay off with at least two full rounds of whole tiles (measured: 4096^3 118-121 -> 131-133 TFLOP/s,
     // 32768 x 1024 x 1024 105-109 -> 116-118; 6400 x 1024 x 1024, 200 tiles of 128 x 256: 87 either way, the frame-level step 2 % slower)
     if (c >= 5 && (long long)((g.M + cfgs[c][0] - 1) / cfgs[c][0]) * ((g.N + cfgs[c][1] - 1) / cfgs[c][1]) < 2LL * g_gemm_workers) continue;
@@ -1120,8 +1118,8 @@ void launch_gemm_mapped(const float* A, int lda, const GemmRowMap& ma, const flo
 // false: not applicable (the caller launches the products one by one).
 bool launch_gemm_batch(int nb, const float* const* A, int lda, const float* const* A2, int lda2, int M1, const float* const* B, int ldb,
                        float* const* C, int ldc, int M, int N, int K, bool accumulate, hipStream_t s, float* ws, size_t ws_floats) {
-  static const bool on = [] { const char* e = getenv("RSRGAN_GEMM_BATCH"); return !e || atoi(e) != 0; }();
-  if (!on || nb < 2 || nb > GEMM_MAXB || M <= 0 || N <= 0 || K <= 0 || !ws) return false;
+  const int form = switches().gemm_batch;
+  if (!form || nb < 2 || nb > GEMM_MAXB || M <= 0 || N <= 0 || K <= 0 || !ws) return false;
   const double outs = (double)M * N;
   if (!(K >= 256 && outs >= 4.0e6) && !(K >= 2048 && outs >= 1.5e6)) return false;      // (k_gemm16's products: launch_gemm16_batch)
   GemmArgs g{};
@@ -1134,13 +1132,12 @@ bool launch_gemm_batch(int nb, const float* const* A, int lda, const float* cons
   for (int b = 0; b < nb; ++b) { bt.Ab[b] = A[b]; bt.A2b[b] = A2 ? A2[b] : nullptr; bt.Bb[b] = B[b]; bt.Cb[b] = C[b]; }
   // 192 x 256 tiles on the four self-loading waves of k_gemm_s (accumulators in AGPRs): 0.018 B/FLOP of operand ingest instead of
   // 0.031 at 128 x 128, and M = 560 is 2.9 tiles of 192 (2.8 % padding) against 4.4 of 128 (12.5 %).  RSRGAN_GEMM_BATCH=2: the 128 x 128 form.
-  static const int form = [] { const char* e = getenv("RSRGAN_GEMM_BATCH"); return e ? atoi(e) : 1; }();
   const int pad192 = (M + 191) / 192 * 192, pad128 = (M + 127) / 128 * 128;
   if (form == 1 && pad192 < pad128 && 2 * (size_t)g_gemm_workers * 192 * 256 <= ws_floats) {
     const int tn1 = (N + 255) / 256;
     // k_gemm_s fills a CU's register file: nothing of the side stream (dWp, column sums, the FCs' gradients) co-resides with it, and
     // behind the launch that work is exposed.  RSRGAN_GEMM_BATCH_W workers (a multiple of 8) leave the other CUs to the side stream.
-    static const int bw = [] { const char* e = getenv("RSRGAN_GEMM_BATCH_W"); const int v = e ? atoi(e) : 0; return v >= 64 && v <= 256 ? v & ~7 : 0; }();
+    const int bw = switches().gemm_batch_w;
     const Plan pl = plan_cfg(M, nb * tn1 * 256, K, 192, 256, bw ? std::min(bw, g_gemm_workers) : g_gemm_workers, ws, ws_floats);
     if (!pl.whole) { launch_cfg_s<false, false, 3, 4, 2, false, GemmBatch>(g, pl, s, ws, &bt); return true; }
   }

@@ -2315,10 +2315,10 @@ int device_cu_count() {
   return n;
 }
 bool resident_probe(int grid, int threads, size_t lds_bytes) {
-  static const bool off = [] { const char* e = getenv("RSRGAN_RESIDENT_PROBE"); return e && atoi(e) == 0; }();
+  const bool off = !switches().resident_probe;
   // RSRGAN_RESIDENT_CAP=n: the verdict of a device that can hold n workgroups (what a CU mask or a compute partition makes the probe
   // find; masks are not honoured in every environment, the cap always is -- tests/test_gpu_padrows.py)
-  static const int cap = [] { const char* e = getenv("RSRGAN_RESIDENT_CAP"); return e ? atoi(e) : 0; }();
+  const int cap = switches().resident_cap;
   if (grid < 1) return false;
   if (grid > device_cu_count() || (cap > 0 && grid > cap)) return false;      // (one workgroup per CU at these footprints)
   if (off) return true;
@@ -2414,7 +2414,7 @@ bool gpersist_np_plan(GPersistArgs& a, int nt_force) {
     if (l > 0 && L.I != a.H) return false;
   }
   // 8 cells per workgroup (every weight in registers) where that many workgroups are resident at once, else 16
-  static const int nt_env = [] { const char* e = getenv("RSRGAN_GP_NP_NT"); return e ? atoi(e) : 0; }();
+  const int nt_env = switches().gp_np_nt;
   for (int nt : {2, 4}) {
     if ((nt_env && nt != nt_env) || (nt_force && nt != nt_force)) continue;
     a.NT = nt; a.NC = a.H / (4 * nt);

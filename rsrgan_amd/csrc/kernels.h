@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "switches.h"
+
 namespace rsr {
 
 constexpr int MAXJ = 8;   // (layer, t) jobs fused into one launch of a step kernel

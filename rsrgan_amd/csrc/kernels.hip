@@ -847,16 +847,14 @@ __global__ __launch_bounds__(256) void k_bwd_b_red(const BwdBJobs jobs) {
 // ---------------------------------------------------------------------------------------
 // placement of the jobs of a launch (kernels.h Place)
 // ---------------------------------------------------------------------------------------
-static int g_xcd_groups = -1;          // RSRGAN_XCD_GROUPS=0: every job spans all 8 XCD slots (round 1's contiguous layout)
 // phase 1: XCD slots per job.  A job worth >= 12 % of the launch's work gets a group of slots of its own, sized by its share
 // (largest remainders, at least one, 8 in all); the others ("fillers") span all 8 slots after the groups' rounds.
 static void plan_groups(int n, const double* cost, int* nx, int* x0, bool* grouped, double balance_tol = 1.35) {
-  if (g_xcd_groups < 0) { const char* e = getenv("RSRGAN_XCD_GROUPS"); g_xcd_groups = e ? atoi(e) : 1; }
   double total = 0.0;
   for (int j = 0; j < n; ++j) total += cost[j];
   int ng = 0;
   double cg = 0.0;
-  for (int j = 0; j < n; ++j) { grouped[j] = g_xcd_groups && total > 0.0 && cost[j] >= 0.12 * total; ng += grouped[j]; cg += grouped[j] ? cost[j] : 0.0; }
+  for (int j = 0; j < n; ++j) { grouped[j] = switches().xcd_groups && total > 0.0 && cost[j] >= 0.12 * total; ng += grouped[j]; cg += grouped[j] ? cost[j] : 0.0; }
   if (ng < 2 || ng > 8) {
     for (int j = 0; j < n; ++j) { grouped[j] = false; nx[j] = 8; x0[j] = 0; }
     return;
@@ -950,9 +948,7 @@ size_t bwd_b_plan(BwdBJobs& jobs, float* ws_base) {
   plan_groups(n, cost, nx, x0, grouped);
   // a group's workgroups must fit ONE round at one per CU (32 CUs per XCD): three equal layers split 3 / 3 / 2 put 36 on the
   // 2-XCD group's CUs and the launch took 23 us instead of 14 -- then no groups (slice = block id % 8 keeps its K-slice affinity)
-  static int bp_groups = -1;
-  if (bp_groups < 0) { const char* e = getenv("RSRGAN_BP_GROUPS"); bp_groups = e ? atoi(e) : 1; }
-  if (!bp_groups) for (int i = 0; i < n; ++i) { grouped[i] = false; nx[i] = 8; x0[i] = 0; }
+  if (!switches().bp_groups) for (int i = 0; i < n; ++i) { grouped[i] = false; nx[i] = 8; x0[i] = 0; }
   constexpr int kpg_target = 24;     // k-blocks per K slice: 24 -> 99 KB LDS (1 WG/CU); 11 / 12 measured slower; round 3:
                                      // 22 / 20 / 19 (243-270 workgroups per generator diagonal) 8.02 / 8.24 / 8.24 ms per step, 27 / 32 7.48 / 7.50, 24 7.48
   for (int i = 0; i < n; ++i) {

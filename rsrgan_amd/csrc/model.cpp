@@ -61,7 +61,7 @@ void Model::run_seg(uint64_t key, hipStream_t s, F&& body) {
   hipGraph_t gr = nullptr;
   if (hipStreamEndCapture(s, &gr) != hipSuccess || !gr) {
     (void)hipGetLastError(); g.uses = -1;
-    if (getenv("RSRGAN_GRAPH_DEBUG")) fprintf(stderr, "rsrgan: capture of segment %llx failed, eager from here on\n", (unsigned long long)key);
+    if (switch_now_graph_debug()) fprintf(stderr, "rsrgan: capture of segment %llx failed, eager from here on\n", (unsigned long long)key);
     body(); return;
   }
   hipGraphExec_t ex = nullptr;
@@ -153,6 +153,12 @@ static void alloc_stash(Model& M, LstmStash& S, const LstmLayer& L, int N, int T
   S.dmt = M.alloc<float>((size_t)T * N * L.ldP);
   S.dc = M.alloc<float>((size_t)N * L.H);
   S.dmst = M.alloc<float>((size_t)N * L.ldP);
+}
+
+// the control block of a persistent launch (kernels.h DP_CTL_*) in its initial state: generation 1, no workgroup finished, no error
+static hipError_t ctl_reset(unsigned* ctl) {
+  const unsigned ctl0[DP_CTL_WORDS] = {1u, 0u, 0u, 0u};
+  return hipMemcpy(ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice);
 }
 
 int Model::init(const rsrgan_cfg& c, uint64_t seed) {
@@ -276,11 +282,9 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     d_fc_b = D.add("d_model/fully_connected/biases", 1, 1, true);
   }
   // ---- row padding for the persistent generator recurrences (model.h Bt) ----
-  if (const char* e = getenv("RSRGAN_GPERSIST")) gp_env = atoi(e);        // bit 0: the generator's forward recurrence, bit 1: its BPTT
   {
-    static const bool pad_env = [] { const char* e = getenv("RSRGAN_PAD_ROWS"); return !e || atoi(e) != 0; }();
     const int Bp = (Bt + GP_ROWS - 1) / GP_ROWS * GP_ROWS;
-    if (pad_env && gp_env && Bp != Bt && !g_dnn() && !g_bnl() && !d_dnn() && wavefront()) {
+    if (switches().pad_rows && gp_live && Bp != Bt && !g_dnn() && !g_bnl() && !d_dnn() && wavefront()) {
       B = Bp;
       GPersistArgs ga{};
       if (!gpersist_shape(ga, std::min(Tmax, (int)GP_TMAX))) B = Bt;     // (only where the padded batch does take the persistent path)
@@ -324,12 +328,11 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
       maxK = std::max(maxK, L.ldK); maxC = std::max(maxC, L.ldCout);
     }
     // implicit-GEMM convolution (conv.hip) for every layer it covers: forward and data gradient never build a patch matrix
-    if (const char* e = getenv("RSRGAN_RCED_IMPLICIT")) rc_implicit = atoi(e) != 0;
     rc_ft_fwd.assign(gconv.size(), nullptr); rc_ft_bwd.assign(gconv.size(), nullptr);
     rc_wgrad_implicit.assign(gconv.size(), 0);
     bool any_implicit = false;
     size_t wg_ws = 0;
-    for (size_t l = 0; l < gconv.size() && rc_implicit; ++l) {
+    for (size_t l = 0; l < gconv.size() && sw.rced_implicit; ++l) {
       const ConvLayer& L = gconv[l];
       if (conv_fwd_supported(L.Cin, L.Cout, rcS, rcW, L.fw)) { rc_ft_fwd[l] = alloc<float>(conv_prep_floats(rcS, L.fw, L.Cin)); any_implicit = true; }
       if (l > 0 && conv_fwd_supported(L.Cout, L.Cin, rcS, rcW, L.fw)) rc_ft_bwd[l] = alloc<float>(conv_prep_floats(rcS, L.fw, L.Cout));
@@ -411,9 +414,8 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   adam_t_dev_d = alloc<int>(1);
   d_st.resize(dl.size());
   for (size_t l = 0; l < dl.size(); ++l) alloc_stash(*this, d_st[l], dl[l], 2 * B, Tmax);
-  if (const char* e = getenv("RSRGAN_DFOLD")) fold_env = atoi(e) != 0;
   {   // folded views of the discriminator's cells (model.h): only for stacks of projected cells
-    bool ok = fold_env && !dl.empty();
+    bool ok = sw.dfold && !dl.empty();
     for (auto& L : dl) ok = ok && L.has_proj && L.H <= 288 && (L.ldH & 3) == 0;
     if (ok) {
       dl_fold.resize(dl.size()); dl_fold_K.resize(dl.size()); d_fold_st.resize(dl.size());
@@ -435,8 +437,7 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
       }
     }
   }
-  if (const char* e = getenv("RSRGAN_DPERSIST")) dp_env = atoi(e);        // bit 0: forward, bit 1: backward
-  if (dp_env && !dl.empty() && dl.size() <= (size_t)DP_MAXL && B % 16 == 0) {
+  if (dp_live && !dl.empty() && dl.size() <= (size_t)DP_MAXL && B % 16 == 0) {
     // every workgroup of a launch waits for the others: ask the device whether the stacked (2B rows) or at least the single (B rows)
     // launch is resident at once -- a CU mask, a partition or a neighbour can take CUs away without multiProcessorCount knowing
     const int nl_ = (int)dl.size();
@@ -449,14 +450,12 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     dp_gran_bytes = dpersist_granule_bytes((int)dl.size(), 2 * B, Tmax);
     dp_gran = (unsigned long long*)alloc<float>(dp_gran_bytes / sizeof(float));
     dp_ctl = (unsigned*)alloc<float>(16);
-    const unsigned ctl0[DP_CTL_WORDS] = {1u, 0u, 0u, 0u};
-    HIPC(hipMemcpy(dp_ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice));
+    HIPC(ctl_reset(dp_ctl));
     // the weight gradients inside the D-run's BPTT launch (the stacked call over 2B rows): shapes only here, pointers per call
-    static const bool dw_env = [] { const char* e = getenv("RSRGAN_DW_INKERNEL"); return !e || atoi(e) != 0; }();
     DPersistArgs pa{};
     pa.nl = (int)dl.size(); pa.N = 2 * B; pa.H = dl[0].H;
     for (size_t l = 0; l < dl.size(); ++l) { pa.L[l].I = dl[l].I; pa.L[l].P = dl[l].P; pa.L[l].ldP = dl[l].ldP; pa.L[l].ldI = dl[l].ldI; }
-    bool shapes = dw_env && (dp_env & 2) && dpersist_dw_supported(pa) && !d_adam();
+    bool shapes = switches().dw_inkernel && (dp_live & 2) && dpersist_dw_supported(pa) && !d_adam();
     for (auto& L : dl) shapes = shapes && L.has_proj && L.H == dl[0].H && L.ldH == dl[0].ldH;
     if (shapes && dpersist_grid(pa.nl, pa.N) == dp_max_grid) {
       const int nt = pa.N / 16;
@@ -476,7 +475,7 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
       else dw_ws = nullptr;
     }
   }
-  if (gp_env && !g_dnn() && !g_bnl()) {
+  if (gp_live && !g_dnn() && !g_bnl()) {
     GPersistArgs ga{};
     gp_Tcap = std::min(Tmax, (int)GP_TMAX);
     gp_noproj = !gl.empty() && !gl[0].has_proj;
@@ -494,16 +493,14 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
         gp_gran2 = (unsigned long long*)alloc<float>(gp_gran2_bytes / sizeof(float));
         gp_ctl = (unsigned*)alloc<float>(16);
         // the BPTT form exists for 8 cells per workgroup only: its two rings (state gradient, input gradient between layers)
-        static const bool npb_env = [] { const char* e = getenv("RSRGAN_GP_NP_BWD"); return !e || atoi(e) != 0; }();
-        if (gp_np_nt == 2 && (gp_env & 2) && npb_env) {
+        if (gp_np_nt == 2 && (gp_live & 2) && switches().gp_np_bwd) {
           gp_gran1 = (unsigned long long*)alloc<float>(gpersist_np_gran1_bytes(ga) / sizeof(float));
           gp_gran3 = (unsigned long long*)alloc<float>(gpersist_np_gran3_bytes(ga) / sizeof(float));
           if (!gp_gran1 || !gp_gran3) { gp_gran1 = gp_gran3 = nullptr; }
         }
         if (!gp_gran1) gp_gran1 = gp_gran2;                       // (forward only: the pointer just says "the forward path is on")
         if (gp_gran2 && gp_ctl) {
-          const unsigned ctl0[DP_CTL_WORDS] = {1u, 0u, 0u, 0u};
-          HIPC(hipMemcpy(gp_ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice));
+          HIPC(ctl_reset(gp_ctl));
           gpersist_rearm();
         } else { gp_gran1 = gp_gran2 = gp_gran3 = nullptr; gp_ctl = nullptr; }
       }
@@ -514,27 +511,24 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
       gp_ctl = (unsigned*)alloc<float>(16);
       // the BPTT launch's hand-offs time out when a layer's recurrent width is a single 16-column block (P <= 16: seen at H = 64 and
       // 128, the bounded waits expire and the step is poisoned): such a stack keeps the persistent forward, its BPTT takes the launch path
-      bool bwd_ok = (gp_env & 2) != 0;
+      bool bwd_ok = (gp_live & 2) != 0;
       for (auto& L : gl) bwd_ok = bwd_ok && L.P > 16;
       if (bwd_ok) gp_gran3 = (unsigned long long*)alloc<float>(gpersist_gran3_bytes(ga) / sizeof(float));
       if (gp_gran1 && gp_gran2 && gp_ctl) {
-        const unsigned ctl0[DP_CTL_WORDS] = {1u, 0u, 0u, 0u};
-        HIPC(hipMemcpy(gp_ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice));
+        HIPC(ctl_reset(gp_ctl));
         gpersist_rearm();
       } else { gp_gran1 = gp_gran2 = nullptr; gp_ctl = nullptr; }
     }
   }
   {
     // the trailing discriminator BPTT beside k_glstm_bwd (the G-run): both launches' workgroups resident at once -- ask the device
-    if (const char* e = getenv("RSRGAN_TRAIL")) trail_mode = atoi(e);
     GPersistArgs ga{};
-    if (trail_mode && dp_gran && (dp_env & 2) && gp_gran1 && gp_gran3 && !gp_noproj && (gp_env & 2) && B % 32 == 0 && gpersist_args(ga, gp_Tcap))
+    if (sw.trail && dp_gran && (dp_live & 2) && gp_gran1 && gp_gran3 && !gp_noproj && (gp_live & 2) && B % 32 == 0 && gpersist_args(ga, gp_Tcap))
       trail_fits = resident_probe(gpersist_grid(ga) + ((dpersist_trail_grid((int)dl.size(), B) + 7) & ~7), GP_THREADS,
                                   std::max(gpersist_lds_bytes(), dpersist_trail_lds_bytes()));
   }
   {
-    static const bool lazy_env = [] { const char* e = getenv("RSRGAN_LAZY_SWIZZLE"); return !e || atoi(e) != 0; }();
-    lazy_sw = lazy_env && wavefront() && gp_gran1 && gp_gran3 && (gp_env & 3) == 3 && dp_gran && (dp_env & 3) == 3;
+    lazy_sw = switches().lazy_swizzle && wavefront() && gp_gran1 && gp_gran3 && (gp_live & 3) == 3 && dp_gran && (dp_live & 3) == 3;
   }
   drop_ctr = (unsigned long long*)alloc<float>(4);
   HIPC(hipMemset(drop_ctr, 0, 16));
@@ -543,7 +537,6 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   len_dev = alloc<int>(2 * B);
   zeros = alloc<float>(64);
   noise_r_buf = alloc<float>((size_t)B * Dout); noise_f_buf = alloc<float>((size_t)B * Dout);
-  if (const char* e = getenv("RSRGAN_GRAPHS")) graphs_env = atoi(e) != 0;
   if (hipStreamCreateWithFlags(&main_s, hipStreamNonBlocking) != hipSuccess) main_s = nullptr;
   if (main_s && (hipEventCreateWithFlags(&ev_in, hipEventDisableTiming) != hipSuccess ||
                  hipEventCreateWithFlags(&ev_out, hipEventDisableTiming) != hipSuccess)) { (void)hipStreamDestroy(main_s); main_s = nullptr; }
@@ -559,15 +552,13 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   if (hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess) side = nullptr;
   if (hipEventCreateWithFlags(&ev_last, hipEventDisableTiming) != hipSuccess) ev_last = nullptr;
   {
-    const char* e = getenv("RSRGAN_DPIPE");
-    if (e && atoi(e) != 0 && trail_fits && side && !d_dnn() && dp_max_grid >= dpersist_grid((int)dl.size(), B)) {
+    if (sw.dpipe > 0 && trail_fits && side && !d_dnn() && dp_max_grid >= dpersist_grid((int)dl.size(), B)) {
       const size_t gb = dpersist_granule_bytes((int)dl.size(), B, Tmax) / 2;      // (a forward launch: one edge per layer)
       dp_gran2 = (unsigned long long*)alloc<float>(gb / sizeof(float));
       dp_ctl2 = (unsigned*)alloc<float>(16);
       if (dp_gran2 && dp_ctl2 && hipEventCreateWithFlags(&ev_dfree, hipEventDisableTiming) == hipSuccess &&
           hipEventCreateWithFlags(&ev_real, hipEventDisableTiming) == hipSuccess) {
-        const unsigned ctl0[DP_CTL_WORDS] = {1u, 0u, 0u, 0u};
-        HIPC(hipMemcpy(dp_ctl2, ctl0, sizeof(ctl0), hipMemcpyHostToDevice));
+        HIPC(ctl_reset(dp_ctl2));
         dpipe = true;
       }
     }
@@ -582,8 +573,7 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   bwdb_ws_floats = (size_t)8 << 20;
   bwdb_ws = alloc<float>(bwdb_ws_floats);
   gemm_ws2 = alloc<float>(gemm_ws_floats ? gemm_ws_floats : 1);
-  static const bool dk_pad = [] { const char* e = getenv("RSRGAN_DK_PAD"); return !e || atoi(e) != 0; }();
-  if (dk_pad && !gl.empty() && gl[0].has_proj && gl[0].I % 4 != 0 && gl[0].ldI % 4 == 0 && gl.size() <= (size_t)GEMM_MAXB) {
+  if (switches().dk_pad && !gl.empty() && gl[0].has_proj && gl[0].I % 4 != 0 && gl[0].ldI % 4 == 0 && gl.size() <= (size_t)GEMM_MAXB) {
     dk_tmp_per = (size_t)(gl[0].ldI + gl[0].P) * 4 * gl[0].H;
     dk_tmp = alloc<float>(dk_tmp_per * gl.size());
     if (!dk_tmp) dk_tmp_per = 0;
@@ -1025,7 +1015,7 @@ bool Model::fold_forward(Chain& ch, int T, hipStream_t s) {
 // The same chain as ONE persistent launch (dpersist.hip): layer 0's x-part batched over time first, everything else in the kernel.
 // Produces the complete stash (gates, c, h, mst, out), unlike fold_forward.
 bool Model::persist_forward(Chain& ch, int T, hipStream_t s) {
-  if (!dp_gran || !(dp_env & 1) || !wavefront() || ch.size() != dl.size()) return false;
+  if (!dp_gran || !(dp_live & 1) || !wavefront() || ch.size() != dl.size()) return false;
   DPersistArgs a{};
   a.nl = (int)ch.size(); a.N = ch[0].N; a.T = T; a.H = dl[0].H; a.len = ch[0].len;
   a.gran = dp_gran; a.ctl = dp_ctl; a.forget_bias = cfg.forget_bias;
@@ -1040,8 +1030,7 @@ bool Model::persist_forward(Chain& ch, int T, hipStream_t s) {
     D_.in = l == 0 ? R.in : nullptr;                   // (layer 0's input product runs inside the launch as well)
   }
   if (!dpersist_supported(a) || dpersist_grid(a.nl, a.N) > dp_max_grid || dpersist_granule_bytes(a.nl, a.N, a.T) > dp_gran_bytes) return false;
-  static const bool fwd_t_env = [] { const char* e = getenv("RSRGAN_DFWD_T"); return e && atoi(e) != 0; }();
-  if (fwd_t_env && a.N % 32 == 0) launch_dlstm_fwd_t(a, s); else launch_dlstm_fwd(a, s);
+  if (switches().dfwd_t && a.N % 32 == 0) launch_dlstm_fwd_t(a, s); else launch_dlstm_fwd(a, s);
   if (prof_on) ++prof_cnt[4];
   return true;
 }
@@ -1050,24 +1039,19 @@ bool Model::persist_forward(Chain& ch, int T, hipStream_t s) {
 // every layer), so the backward pass does not know which forward ran.
 // the discriminator's halves of the fused launches: the second tile of the (only) tile pair is padding (DPersistArgs::nrt; RSRGAN_DP_NRT=0: it runs)
 int Model::trail_nrt() const {
-  static const bool on = [] {
-    const char* e = getenv("RSRGAN_DP_NRT"); const char* g = getenv("RSRGAN_GP_NRT");
-    return (!e || atoi(e) != 0) && (!g || atoi(g) != 0);             // (only beside a generator that drops the tile as well)
-  }();
+  const bool on = switches().dp_nrt && switches().gp_nrt;             // (only beside a generator that drops the tile as well)
   // (and only when every recurrence of both nets runs persistent: see gpersist_shape's note on the padding rows of the stash)
-  return on && B == 32 && Bt <= 16 && (gp_env & 3) == 3 && (dp_env & 3) == 3 ? 1 : 0;
+  return on && B == 32 && Bt <= 16 && (gp_live & 3) == 3 && (dp_live & 3) == 3 ? 1 : 0;
 }
 bool Model::gpersist_shape(GPersistArgs& a, int T) const {              // (sizes only: usable before any buffer exists)
-  static const bool res_env = [] { const char* e = getenv("RSRGAN_GP_RES"); return !e || atoi(e) != 0; }();
-  const bool res = cfg.g_type == RSRGAN_G_RES_LSTM_L && res_env;          // the running residual sum rides the hand-offs (gpersist.hip RES)
+  const bool res = cfg.g_type == RSRGAN_G_RES_LSTM_L && switches().gp_res;          // the running residual sum rides the hand-offs (gpersist.hip RES)
   // (res_lstm_base, models/res_lstm_base.py:101-139: the same stack of projected cells fed the input frames directly, no sums)
-  if (!gp_env || gl.empty() || gl.size() > (size_t)GP_MAXL || (cfg.g_type != RSRGAN_G_LSTM && cfg.g_type != RSRGAN_G_RES_LSTM_BASE && !res)) return false;
+  if (!gp_live || gl.empty() || gl.size() > (size_t)GP_MAXL || (cfg.g_type != RSRGAN_G_LSTM && cfg.g_type != RSRGAN_G_RES_LSTM_BASE && !res)) return false;
   a = GPersistArgs{};
   a.nl = (int)gl.size(); a.N = B; a.T = T; a.H = gl[0].H; a.res = res ? 1 : 0;
   bool noproj = !gl[0].has_proj;
   // ring slots tagged with the parity of the ring pass instead of re-armed with sentinels (gpersist.hip gp_store_t); RSRGAN_GP_TAGS=0: the sentinel form
-  static const bool tags_env = [] { const char* e = getenv("RSRGAN_GP_TAGS"); return !e || atoi(e) != 0; }();
-  a.tags = tags_env && !noproj ? 1 : 0;
+  a.tags = switches().gp_tags && !noproj ? 1 : 0;
   for (size_t l = 0; l < gl.size(); ++l) {
     const LstmLayer& L = gl[l];
     if (L.has_proj == noproj || L.H != a.H) return false;
@@ -1075,19 +1059,17 @@ bool Model::gpersist_shape(GPersistArgs& a, int T) const {              // (size
     G_.I = L.I; G_.P = L.P; G_.ldI = L.ldI; G_.ldP = L.ldP; G_.ldH = L.ldH;
   }
   // num_proj=None (BASELINE.json's 2 x 512 generator): the single-hop form, forward only (gpersist.hip np_fwd_body)
-  static const bool np_env = [] { const char* e = getenv("RSRGAN_GP_NOPROJ"); return !e || atoi(e) != 0; }();
-  if (noproj) return np_env && !res && (gp_env & 1) && gpersist_np_plan(a, gp_np_nt);
+  if (noproj) return switches().gp_noproj && !res && (gp_live & 1) && gpersist_np_plan(a, gp_np_nt);
   if (!gpersist_plan(a)) return false;
   // a padded model whose real rows fit one 16-row tile (the shipped batch_size = 8, decode's single utterance): the other tile of the
   // row group holds padding rows only -- length 0 in every batch, zeros in every stash since the allocation -- and does not run
   // (GPersistArgs::nrt).  RSRGAN_GP_NRT=0: both tiles run.
-  static const bool nrt_env = [] { const char* e = getenv("RSRGAN_GP_NRT"); return !e || atoi(e) != 0; }();
   // (only when BOTH recurrences run persistent: a launch-path forward writes gate activations into the padding rows of the stash,
   // which a one-lane BPTT would never turn into dz = 0 -- the weight-gradient products would read them as dZ)
-  if (nrt_env && B == 32 && Bt <= 16 && (gp_env & 3) == 3) a.nrt = 1;
+  if (switches().gp_nrt && B == 32 && Bt <= 16 && (gp_live & 3) == 3) a.nrt = 1;
   // the forward launch's off-chain work (the X waves' products, the stash stores) behind the lane's publication instead of beside it
   // (GPersistArgs::sched; pays with two row groups on the fabric: 13.5 -> 13.0 us per step at 64 rows, nothing at 32).  RSRGAN_GP_SCHED=0..3
-  static const int sched_env = [] { const char* e = getenv("RSRGAN_GP_SCHED"); return e ? atoi(e) : -1; }();
+  const int sched_env = switches().gp_sched;
   a.sched = sched_env >= 0 ? sched_env : (B >= 64 ? 3 : 0);
   return true;
 }
@@ -1109,7 +1091,7 @@ bool Model::gpersist_args(GPersistArgs& a, int T) const {
 // work on the device, CUs taken away after rsrgan_create.  Another attempt would spin into the same time-out on every step: this
 // handle takes the launch-per-phase path from now on (the captured graphs hold the persistent launches: dropped).
 void Model::persist_disable(int which) {
-  if (which == 1) gp_env = 0; else dp_env = 0;
+  if (which == 1) gp_live = 0; else dp_live = 0;
   lazy_sw = false;
   trail_fits = false;
   dpipe = false;
@@ -1188,7 +1170,7 @@ bool Model::persist_forward_g(int T, hipStream_t s) {
 // (y + noise) and both stashes are complete behind it.  False: not applicable (the caller runs the launches one after the other).
 // D(real) of the D-run as a launch of its own over rows [0, B) of the stacked stash (RSRGAN_DPIPE), with granules and control block of its own
 bool Model::persist_forward_real(int T, hipStream_t q, bool check_only) {
-  if (!dpipe || !dp_gran2 || !(dp_env & 1) || !wavefront()) return false;
+  if (!dpipe || !dp_gran2 || !(dp_live & 1) || !wavefront()) return false;
   Chain ch = d_chain(B, 2 * B, 0);
   DPersistArgs a{};
   a.nl = (int)ch.size(); a.N = B; a.T = T; a.H = dl[0].H; a.len = ch[0].len; a.Ns = 2 * B; a.row0 = 0;
@@ -1210,8 +1192,7 @@ bool Model::persist_forward_real(int T, hipStream_t q, bool check_only) {
 }
 
 bool Model::persist_forward_g_trail(Chain& ch, int T, hipStream_t s, const float* nf, bool check_only) {
-  static const bool env = [] { const char* e = getenv("RSRGAN_TRAIL_FWD"); return !e || atoi(e) != 0; }();
-  if (!env || !trail_fits || !gp_fwd_on() || gp_noproj || !wavefront() || seq_drop_on() || !dp_gran || !(dp_env & 1) || ch.size() != dl.size()) return false;
+  if (!switches().trail_fwd || !trail_fits || !gp_fwd_on() || gp_noproj || !wavefront() || seq_drop_on() || !dp_gran || !(dp_live & 1) || ch.size() != dl.size()) return false;
   GPersistArgs a{};
   if (!gpersist_args(a, T) || gpersist_gran2_bytes(a) > gp_gran2_bytes) return false;
   a.L[0].in = g_ins[0];
@@ -1246,7 +1227,7 @@ bool Model::persist_forward_g_trail(Chain& ch, int T, hipStream_t s, const float
 // BPTT through the generator's stack as ONE persistent launch (gpersist.hip k_glstm_bwd): dz over the gate activations of every
 // layer's stash, dm per step in dmt.  Layer 0's input gradient (the input FC's d(h0)) is one GEMM over the dz stash afterwards.
 bool Model::persist_backward_g(Chain& ch, int T, hipStream_t s, bool check_only, const StreamFn& pre, const StreamFn& post) {
-  if (!gp_gran1 || !gp_gran3 || !(gp_env & 2) || !wavefront() || seq_drop_on() || ch.size() != gl.size()) return false;
+  if (!gp_gran1 || !gp_gran3 || !(gp_live & 2) || !wavefront() || seq_drop_on() || ch.size() != gl.size()) return false;
   GPersistArgs a{};
   if (!gpersist_args(a, T) || (gp_noproj ? gpersist_np_gran2_bytes(a) : gpersist_gran2_bytes(a)) > gp_gran2_bytes) return false;
   if (gp_noproj) {
@@ -1288,11 +1269,9 @@ bool Model::persist_backward_g(Chain& ch, int T, hipStream_t s, bool check_only,
   // (layer 0's X waves publish partials to ring 0 of gran3, its reducers sum them a step late): built, bit-stable, parity-green --
   // and 0.2 ms per step SLOWER (k_glstm_bwd 16.7 -> 19.4 us per step: a third more hand-off traffic and MFMA bursts on the layer
   // every other layer waits for), so it stays off.
-  static const bool din0_env = [] { const char* e = getenv("RSRGAN_GP_DIN0"); return e && atoi(e) != 0; }();
-  const bool din_inside = ch[0].din && din0_env && (gl[0].I + 15) / 16 <= (gl[0].P + 15) / 16 && gl[0].ldI % 4 == 0;
+  const bool din_inside = ch[0].din && switches().gp_din0 && (gl[0].I + 15) / 16 <= (gl[0].P + 15) / 16 && gl[0].ldI % 4 == 0;
   if (din_inside) { a.din0 = ch[0].din; a.ld_din0 = gl[0].ldI; }
-  a.dout_trail = gp_trail_next ? 1 : 0;
-  if (gp_trail_next && getenv("RSRGAN_TRAIL_DBG")) a.dout_trail = atoi(getenv("RSRGAN_TRAIL_DBG"));
+  a.dout_trail = gp_trail_next ? switch_now_trail_dbg() : 0;
   if (gp_phase == 2) {
   } else if (prof_on) {
     if ((size_t)(2 * prof_gb_n + 2) > prof_gb_ev.size()) {
@@ -1331,7 +1310,7 @@ bool Model::persist_backward_g(Chain& ch, int T, hipStream_t s, bool check_only,
 // BPTT through a discriminator chain running alone as ONE persistent launch (dpersist.hip k_dlstm_bwd), then the weight-gradient
 // GEMMs over the dz it leaves in the stash.  No input gradient for layer 0 (the D-run does not need one).
 bool Model::persist_backward(Chain& ch, int T, hipStream_t s) {
-  if (!dp_gran || !(dp_env & 2) || !wavefront() || ch.size() != dl.size() || ch[0].din) return false;
+  if (!dp_gran || !(dp_live & 2) || !wavefront() || ch.size() != dl.size() || ch[0].din) return false;
   DPersistArgs a{};
   a.nl = (int)ch.size(); a.N = ch[0].N; a.T = T; a.H = dl[0].H; a.len = ch[0].len;
   a.gran = dp_gran; a.ctl = dp_ctl; a.forget_bias = cfg.forget_bias;
@@ -1370,7 +1349,7 @@ bool Model::persist_backward(Chain& ch, int T, hipStream_t s) {
 }
 
 bool Model::persist_backward_trail(Chain& ch, int T, hipStream_t s, float* dy, int ld_dy, float* dtop, int ld_dtop, bool check_only) {
-  if (!trail_fits || !dp_gran || !(dp_env & 2) || !wavefront() || ch.size() != dl.size() || ch[0].din) return false;
+  if (!trail_fits || !dp_gran || !(dp_live & 2) || !wavefront() || ch.size() != dl.size() || ch[0].din) return false;
   DPersistArgs a{};
   a.nl = (int)ch.size(); a.N = ch[0].N; a.T = T; a.H = dl[0].H; a.len = ch[0].len;
   a.gran = dp_gran; a.ctl = dp_ctl; a.forget_bias = cfg.forget_bias;
@@ -1416,11 +1395,10 @@ void Model::layer_wgrads_gemms(const LayerRun& R, int t0, int t1, bool accumulat
 // launches are latency-bound (the discriminator's six per layer left the chip idle for 0.26 ms per D-run).  Returns whether dWp and
 // the column sums are done (*dK_done: the kernel gradients as well); the caller runs per layer what is not.
 bool Model::batch_wgrads(Chain& ch, int T, hipStream_t s, bool dK_too, bool* dK_done, bool check_only) {
-  static const bool on = [] { const char* e = getenv("RSRGAN_WGRAD_BATCH"); return !e || atoi(e) != 0; }();
   *dK_done = false;
   std::vector<const LayerRun*> rs;
   for (auto& R : ch) if (R.want_wgrads) rs.push_back(&R);
-  if (!on || rs.size() < 2 || rs.size() > (size_t)GEMM16_MAXB) return false;
+  if (!switches().wgrad_batch || rs.size() < 2 || rs.size() > (size_t)GEMM16_MAXB) return false;
   const LstmLayer& L0 = *rs[0]->L;
   for (auto* R : rs) {
     const LstmLayer& L = *R->L;
@@ -1480,10 +1458,9 @@ void Model::layer_wgrads(const LayerRun& R, int T, hipStream_t s) {
 // FCs' parameter gradients: short launches that used to follow the dK GEMMs): they ride the side stream too, `post` behind an event
 // recorded on s right after `between`.
 void Model::chain_wgrads(Chain& ch, int T, hipStream_t s, const StreamFn& between, const StreamFn& pre, const StreamFn& post) {
-  static const int streams = [] { const char* e = getenv("RSRGAN_WGRAD_STREAMS"); return e ? atoi(e) : 2; }();
   int nw = 0;
   for (auto& R : ch) nw += R.want_wgrads ? 1 : 0;
-  if (!side || streams < 2 || nw < 2) {
+  if (!side || switches().wgrad_streams < 2 || nw < 2) {
     if (pre) pre(s);
     if (between) between(s);
     if (post) post(s);
@@ -1493,7 +1470,7 @@ void Model::chain_wgrads(Chain& ch, int T, hipStream_t s, const StreamFn& betwee
   }
   // RSRGAN_DIN0_SIDE=1: `between` (the input gradient of layer 0 and what hangs on it) rides the side stream as well, the chip-filling
   // kernel-gradient GEMMs start at once on s
-  static const bool between_side = [] { const char* e = getenv("RSRGAN_DIN0_SIDE"); return e && atoi(e) != 0; }();
+  const bool between_side = switches().din0_side;
   hipEvent_t ev = ev_pool[ev_next++ & 15];
   (void)hipEventRecord(ev, s);
   (void)hipStreamWaitEvent(side, ev, 0);
@@ -1788,9 +1765,8 @@ void Model::d_logits(int N, int T, hipStream_t s) {
 // False: not applicable (the caller runs d_logits + launch_lsgan + the GEMMs of d_backward_pass).
 bool Model::d_head(int N, int T, int n_real, const float* t_real, const float* t_fake, float* loss3, bool want_grads, bool want_wgrads,
                    hipStream_t s) {
-  static const bool on = [] { const char* e = getenv("RSRGAN_DHEAD"); return !e || atoi(e) != 0; }();
   const int ldPd = pad4(dR), nb = (T * N + 63) / 64;
-  if (!on || d_dnn() || dl.empty() || dR % 4 != 0 || dR + 3 > 64 ||       // (k_dhead2 sums 64 quantities: 3 + dR)
+  if (!switches().dhead || d_dnn() || dl.empty() || dR % 4 != 0 || dR + 3 > 64 ||       // (k_dhead2 sums 64 quantities: 3 + dR)
       (size_t)nb * (DH_MAXR + 3) > scratch_floats) return false;
   DHeadArgs a{};
   a.top = d_st[dl.size() - 1].out; a.ldt = ldPd; a.w = D.W(d_fc_w); a.ldw = 4; a.b = D.W(d_fc_b);
@@ -1878,8 +1854,7 @@ int Model::d_backward(const float* x, const float* labels, const int32_t* length
   // RSRGAN_DPIPE: D(real) on the side stream, ahead of this call's place in the stream; the run itself is k_glstm_fwd_dt (D(G(x)) trailing)
   bool dsplit = false;
   // (RSRGAN_DPIPE=1 covers labels and lengths; a noise_real tensor drawn on the caller's stream right before the call is covered by =2 only)
-  static const int dpipe_level = [] { const char* e = getenv("RSRGAN_DPIPE"); return e ? atoi(e) : 0; }();
-  if (dpipe && (!nr || dpipe_level >= 2) && wavefront() && gp_fwd_on() && !d_dnn() && !seq_drop_on() && T > 0 && T <= Tmax) {
+  if (dpipe && (!nr || sw.dpipe >= 2) && wavefront() && gp_fwd_on() && !d_dnn() && !seq_drop_on() && T > 0 && T <= Tmax) {
     Chain dchk = d_chain(B, 2 * B, B);
     dsplit = persist_forward_real(T, side, true) && persist_forward_g_trail(dchk, T, s, nf, true);
   }
@@ -1896,8 +1871,7 @@ int Model::d_backward(const float* x, const float* labels, const int32_t* length
   if (seq_drop_on()) launch_drop_tick(drop_ctr, s);     // a new training run: new masks (read from device memory: graph-safe)
   // rsrgan_d_step: the update follows in the same call -- its launches close this segment (one graph: no launch boundary in front
   // of the clip / SGD / weight-copy kernels); RSRGAN_FUSED_SEG=0 keeps them in a segment of their own
-  static const bool fused_seg_d = [] { const char* e = getenv("RSRGAN_FUSED_SEG"); return !e || atoi(e) != 0; }();
-  const bool inl = fused_apply && fused_seg_d && want_grads && !d_dnn() && graphs_on();
+  const bool inl = fused_apply && switches().fused_seg && want_grads && !d_dnn() && graphs_on();
   const unsigned kbits = (want_grads ? 1u : 0u) | (nr ? 2u : 0u) | (nf ? 4u : 0u) | (inl ? 8u : 0u) | (dsplit ? 16u : 0u);
   run_seg(seg_key(SEG_D, T, kbits), s, [&]() {
   // discriminator input rows [0,B) = labels + noise_real (gan_rnn_placeholder.py:207,212; utils/ops.py:19-30)
@@ -2014,7 +1988,7 @@ int Model::g_backward(const float* x, const float* labels, const int32_t* length
   const bool wave_bwd = want_grads && !d_dnn() && wavefront();
   // (per-layer weight-gradient segments exist for the caller's bucketed all-reduce; rsrgan_g_step applies the update itself, so
   // nothing can run between the backward pass and the optimizer: one segment, no graph boundaries between the layers)
-  static const bool fused_seg = [] { const char* e = getenv("RSRGAN_FUSED_SEG"); return !e || atoi(e) != 0; }();
+  const bool fused_seg = switches().fused_seg;
   const bool bucketed = wave_bwd && gbk[RSRGAN_NET_G].size() > 1 && !overlap() && !(fused_apply && fused_seg);
   const int R = T * B, Ld = (int)dl.size(), Lg = (int)gl.size();
   const int ldPd = pad4(dR), P = gR, ldP = pad4(P);
@@ -2048,10 +2022,7 @@ int Model::g_backward(const float* x, const float* labels, const int32_t* length
   // Without gradient buckets (rsrgan_g_step) and with the generator's BPTT as a persistent launch, the two FCs' parameter gradients --
   // eight short launches that used to FOLLOW the dK GEMMs -- ride the side stream beside them.  Decided here, on the host: a
   // replayed segment does not run its body.
-  static const bool fc_side_env = [] {
-    const char* e = getenv("RSRGAN_WGRAD_STREAMS"); const char* f = getenv("RSRGAN_FC_SIDE");
-    return (!e || atoi(e) >= 2) && (!f || atoi(f) != 0);
-  }();
+  const bool fc_side_env = switches().wgrad_streams >= 2 && switches().fc_side;
   const bool fcs_inside = wave_bwd && !bucketed && side && fc_side_env && cfg.g_type == RSRGAN_G_LSTM && dl[0].ldI == ldDout &&
                           persist_backward_g(bw_chains[1], T, s, true);
   // rsrgan_g_step with nothing left between the backward segment and the update (no input-FC segment, no buckets): the loss
@@ -2094,9 +2065,8 @@ int Model::g_backward(const float* x, const float* labels, const int32_t* length
     }
     // the next D-run's D(real) (32 workgroups that own their CUs) runs beside these launches when the host is ahead: the chip-filling
     // GEMMs leave it room (a persistent stream-K launch on all 256 CUs would wait for it with 32 of its workers, and it for them)
-    static const int pipe_w = [] { const char* e = getenv("RSRGAN_DPIPE_W"); const int v = e ? atoi(e) : 224; return v >= 64 && v <= 256 ? v & ~7 : 224; }();
     const int saved_w = g_gemm_workers;
-    g_gemm_workers = std::min(saved_w, pipe_w);
+    g_gemm_workers = std::min(saved_w, switches().dpipe_w);
     defer_wgrads = bucketed;
     gp_phase = 2; persist_backward_g(bw_chains[1], T, s, false, pre, post); gp_phase = 0;
     defer_wgrads = false;

@@ -149,6 +149,7 @@ void launch_bnl_bn_in_bwd(const BnlLayer& a, float* dzx, int T, hipStream_t s);
 
 struct Model {
   rsrgan_cfg cfg{};
+  const HandleSwitches sw;       // the handle-scope rows of switches.h, read when rsrgan_create constructs the handle; never written
   int B = 0, Tmax = 0, Din = 0, Dout = 0, ldDin = 0, ldDout = 0;
   // B = rows per frame of every internal buffer; Bt = the caller's batch_size.  They differ when the batch is PADDED up to a multiple
   // of the persistent generator kernels' 32-row group (run_gan_rnn_placeholder.sh:126 ships batch_size=8, decode feeds 1): the
@@ -180,14 +181,13 @@ struct Model {
   std::vector<LstmLayer> dl_fold;                         // folded views of dl (has_proj = false, I' = H below, P' = H)
   std::vector<float*> dl_fold_K;                          // Kf [(I' + H)][4H], refreshed with the other weight copies
   std::vector<LstmStash> d_fold_st;                       // gates / c / h alias d_st; mst = carried h [T+1][2B][ldH]
-  bool fold_env = true;                                   // RSRGAN_DFOLD=0: off
   bool fold_forward(Chain& ch, int T, hipStream_t s);     // false: not applicable -> caller falls back
   void refresh_fold(hipStream_t s);
   // ---- persistent recurrence (dpersist.hip): the same chain as ONE launch; RSRGAN_DPERSIST=0: off (bits below)
   unsigned long long* dp_gran = nullptr;
   unsigned* dp_ctl = nullptr;                             // kernels.h DP_CTL_*
   size_t dp_gran_bytes = 0;
-  int dp_env = 3;                                         // RSRGAN_DPERSIST: bit 0 the forward launch, bit 1 the backward launch
+  int dp_live = sw.dpersist;                              // RSRGAN_DPERSIST's bits (0 forward, 1 backward) until persist_disable clears them
   bool persist_forward(Chain& ch, int T, hipStream_t s);  // false: not applicable -> caller falls back to fold_forward
   bool persist_backward(Chain& ch, int T, hipStream_t s); // BPTT of the chain + its weight gradients; false: not applicable
   // the G-run's discriminator BPTT in its trailing form (dpersist_dev.h): fills dt_args for the k_glstm_bwd_dt launch that
@@ -208,14 +208,13 @@ struct Model {
   bool persist_forward_real(int T, hipStream_t q, bool check_only = false);
   bool trail_fits = false;                                // both launches resident at once (resident_probe at init)
   bool gp_trail_next = false;                             // the next generator BPTT launch is k_glstm_bwd_dt (dt_args)
-  int trail_mode = 1;                                     // RSRGAN_TRAIL: 0 off
   DPersistArgs dt_args{};                                 // (mode 1) the discriminator half of the next k_glstm_bwd_dt launch
   // ---- persistent GENERATOR recurrence (gpersist.hip): the forward pass of the generator's stack as ONE launch (weights resident
   // in VGPRs / LDS for all T steps); RSRGAN_GPERSIST bit 0.  Needs B % 32 == 0, projected cells, no residual sums, no dropout.
   unsigned long long *gp_gran1 = nullptr, *gp_gran2 = nullptr, *gp_gran3 = nullptr;
   unsigned* gp_ctl = nullptr;
   size_t gp_gran2_bytes = 0;
-  int gp_env = 3;                                         // RSRGAN_GPERSIST: bit 0 the forward launch, bit 1 the backward launch (0: the launch-per-phase wavefront)
+  int gp_live = sw.gpersist;                              // RSRGAN_GPERSIST's bits (0 forward, 1 backward) until persist_disable clears them
   int gp_Tcap = 0;                                        // the rings are sized for min(max_frames, GP_TMAX) steps; longer batches take the launch path
   // the discriminator's weight gradients inside its stand-alone BPTT launch (dpersist.hip dp_dw_body; RSRGAN_DW_INKERNEL=0: the GEMM /
   // column-sum launches behind it): per-(layer, tile) partial sums, progress words, the tensors' offsets inside a record (device)
@@ -223,7 +222,7 @@ struct Model {
   bool d_partial_fresh = false;                           // k_dw_reduce has just left D.partial (the clip's sums of squares): the inlined update skips k_sumsq
   int dp_max_grid = 0;                                    // largest discriminator launch the device proved it can hold (resident_probe)
   void persist_disable(int which);                        // after a reported failure: 0 = discriminator, 1 = generator launches off for this handle
-  bool gp_fwd_on() const { return gp_gran1 && (gp_env & 1); }
+  bool gp_fwd_on() const { return gp_gran1 && (gp_live & 1); }
   bool gpersist_shape(GPersistArgs& a, int T) const;      // sizes + plan only (no buffers)
   int gp_np_nt = 0;                                       // ... its gate tiles per workgroup, fixed at init by the resident probe (0: not decided)
   bool gp_noproj = false;                                 // the generator's cells are unprojected (num_proj=None): the single-hop form (k_glstm_np_fwd; forward only)
@@ -261,7 +260,6 @@ struct Model {
   std::vector<char> rc_wgrad_implicit;        // per layer: weight gradient by k_conv_wgrad
   float* rc_wg_ws = nullptr;                  // its partial tiles
   float* rc_x4 = nullptr;                     // layer 0's single-channel input as [positions][4] when it takes the implicit path
-  bool rc_implicit = true;         // RSRGAN_RCED_IMPLICIT=0: patch-matrix GEMMs everywhere (the first correct path, kept for A/B)
   bool rc_keep_cols = false;
   size_t scratch_floats = 0;
   int rcS = 0, rcW = 0;
@@ -421,8 +419,7 @@ struct Model {
   hipEvent_t ev_in = nullptr, ev_out = nullptr;
   hipEvent_t ev_last = nullptr; bool ev_last_set = false; // recorded behind every call on the stream it worked on (rsrgan_device_status waits for it)
   float *noise_r_buf = nullptr, *noise_f_buf = nullptr;      // staged gaussian_noise_layer draws [B][Dout]
-  bool graphs_on() const { return (cfg.flags & RSRGAN_FLAG_GRAPH) != 0 && wavefront() && !overlap() && !prof_on && !g_dnn() && graphs_env; }
-  bool graphs_env = true;
+  bool graphs_on() const { return (cfg.flags & RSRGAN_FLAG_GRAPH) != 0 && wavefront() && !overlap() && !prof_on && !g_dnn() && sw.graphs; }
   template <class F> void run_seg(uint64_t key, hipStream_t s, F&& body);
   void drop_graphs();
   hipStream_t enter(hipStream_t caller);

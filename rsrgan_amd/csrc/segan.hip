@@ -431,8 +431,7 @@ void launch_colred(int mode, const float* a, int lda, int coff, const float* b, 
   // reference's E[h^2] - E[h]^2 (bnorm.py:40-41) is ill-conditioned in fp32 where |mean| >> sigma (the first two blocks on waveform
   // input), and the 16384-sample parity case holds its 2e-3 against the fp64 oracle only with sums that differ from the 16-byte
   // form's (correctly rounded) ones by one ulp -- 9e-4 .. 3e-3 on four tensors otherwise (tests/test_gpu_segan.py)
-  static int vecmask = -1;
-  if (vecmask < 0) { const char* e = getenv("RSRGAN_COLRED_VEC"); vecmask = e ? atoi(e) : 11; }
+  const int vecmask = switches().colred_vec;
   const bool vec = ((vecmask >> mode) & 1) && C % 4 == 0 && lda % 4 == 0 && coff % 4 == 0 && (!two || ldb % 4 == 0) && (mode != 3 || ldcoef % 4 == 0);
   // chunk: ~2048 workgroups per launch, <= 256 partials per (pass, column) (the final sum is one thread per column), scratch permitting
   int chunk = vec ? 64 : 256;

@@ -28,7 +28,7 @@ def test_padded_batch_against_oracle(B, T, flags):
 @pytest.mark.parametrize("net", ["lstm", "res_lstm_l"])
 def test_padded_batch_with_one_persistent_direction_against_oracle(net, mode, monkeypatch):
     """Round 6 (advisor): a padded batch (batch_size 8 -> one 32-row group) with only ONE of the generator's recurrences persistent
-    (RSRGAN_GPERSIST=1: forward only, =2: BPTT only; read at rsrgan_create).  The one-lane form of the persistent launches (GPersistArgs::
+    (RSRGAN_GPERSIST=1: forward only, =2: BPTT only; a handle-scope row of csrc/switches.h: read at rsrgan_create).  The one-lane form of the persistent launches (GPersistArgs::
     nrt = 1) relies on the padding rows of the stash never being written; a launch-path recurrence writes them, so the lane is dropped
     only when both directions run persistent -- every gradient against the oracle either way."""
     monkeypatch.setenv("RSRGAN_GPERSIST", mode)

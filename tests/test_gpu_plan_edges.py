@@ -127,7 +127,7 @@ def test_unprojected_bptt_launch_against_oracle(flags):
     _np_case(64, 100, flags, 915, np_bwd, g_type="res_lstm_base")
 
 
-# ---- B. the 16-cell unprojected form (RSRGAN_GP_NP_NT=4, read once per process): forward persistent, BPTT on the launch path ---------
+# ---- B. the 16-cell unprojected form (RSRGAN_GP_NP_NT=4, a process-scope row of csrc/switches.h: read once per process): forward persistent, BPTT on the launch path ---------
 
 def np16_case():
     assert os.environ.get("RSRGAN_GP_NP_NT") == "4"

@@ -140,7 +140,6 @@ static float time_graph(hipStream_t s, int per_graph, int replays, F f) {
 
 int main(int argc, char** argv) {
   hipStream_t s; CK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  if (const char* e = getenv("RSRGAN_BWD_A_FORM")) set_bwd_a_form(atoi(e));
   const int N = 64, H = 760, P = 280, HD = 256, PD = 40;
   int* len; CK(hipMalloc(&len, 256 * 4)); { std::vector<int> h(256, 1000); CK(hipMemcpy(len, h.data(), 256 * 4, hipMemcpyHostToDevice)); }
 
