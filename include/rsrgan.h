@@ -162,6 +162,25 @@ int rsrgan_get_grads(rsrgan_handle h, int32_t net, float* dense, void* stream);
 int rsrgan_forward_g(rsrgan_handle h, const float* x, const int32_t* lengths, int32_t T,
                      float* y, void* stream);
 
+/* ---- stateful generator forward: chunked, streaming and multi-stream decode ----
+ * The handle keeps a CARRIED generator state: per layer l the cell state c_l [batch_size, H] and the projected state m_l
+ * [batch_size, P] (P = H without num_proj: the state is h), fp32, zero after rsrgan_create.  Only the five calls below read or
+ * write it; rsrgan_forward_g and every training call start from cell.zero_state as before.  Sequence generators only:
+ * RSRGAN_ERR_INVALID for the frame-level ones (dnn, rced: no state) and for bnlstm (not built).
+ *
+ * floats of one row's state blob: sum over layers of (H + P); a row is layer 0's c, layer 0's m, layer 1's c, ... unpadded. */
+int rsrgan_g_state_floats(rsrgan_handle h, int32_t* n);
+/* zero the carried state of the rows whose entry of row_mask (DEVICE int32 [batch_size]) is non-zero; NULL = all rows. */
+int rsrgan_g_state_reset(rsrgan_handle h, const int32_t* row_mask, void* stream);
+/* copy the carried state out / in: DEVICE [batch_size, floats] buffers (park a stream, resume it on another row or handle). */
+int rsrgan_g_state_get(rsrgan_handle h, float* dst, void* stream);
+int rsrgan_g_state_set(rsrgan_handle h, const float* src, void* stream);
+/* rsrgan_forward_g, but every row b starts from its carried state, and afterwards the carried state is the row's state after
+ * its lengths[b] frames (dynamic_rnn copies the state of a finished row through; lengths[b] = 0: the row is inert and keeps
+ * its state).  y rows past lengths[b] are the output FC's bias, as in rsrgan_forward_g.  T in (0, max_frames]. */
+int rsrgan_forward_g_stream(rsrgan_handle h, const float* x, const int32_t* lengths, int32_t T,
+                            float* y, void* stream);
+
 /* sess.run([model.d_opt, model.d_rl_losses, model.d_fk_losses, model.d_losses], feed)
  * (train_gan_rnn_placeholder.py:77-82).  labels [B,T,Dout].  noise_real/noise_fake
  * are the two gaussian_noise_layer draws ([B,Dout], broadcast over T,

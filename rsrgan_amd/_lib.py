@@ -18,7 +18,9 @@ WHAT = {"variables": 0, "adam_m": 1, "adam_v": 2, "ema": 3}
 # every symbol include/rsrgan.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = ["rsrgan_default_cfg", "rsrgan_create", "rsrgan_destroy", "rsrgan_last_error", "rsrgan_set_scalar",
            "rsrgan_get_scalar", "rsrgan_num_tensors", "rsrgan_tensor_info", "rsrgan_param_count",
-           "rsrgan_get_params", "rsrgan_set_params", "rsrgan_get_grads", "rsrgan_forward_g", "rsrgan_d_step",
+           "rsrgan_get_params", "rsrgan_set_params", "rsrgan_get_grads", "rsrgan_forward_g",
+           "rsrgan_g_state_floats", "rsrgan_g_state_reset", "rsrgan_g_state_get", "rsrgan_g_state_set", "rsrgan_forward_g_stream",
+           "rsrgan_d_step",
            "rsrgan_g_step", "rsrgan_d_backward", "rsrgan_g_backward", "rsrgan_apply", "rsrgan_grad_buffer",
            "rsrgan_grad_bucket_count", "rsrgan_grad_bucket_info", "rsrgan_grad_bucket_wait",
            "rsrgan_profile_begin", "rsrgan_profile_read", "rsrgan_profile_read_kind", "rsrgan_profile_launches", "rsrgan_op_launch_floor", "rsrgan_device_status", "rsrgan_set_dropout",
@@ -78,6 +80,11 @@ def load():
     lib.rsrgan_set_params.argtypes = [vp, i32, i32, p, vp]
     lib.rsrgan_get_grads.argtypes = [vp, i32, p, vp]
     lib.rsrgan_forward_g.argtypes = [vp, p, p, i32, p, vp]
+    lib.rsrgan_g_state_floats.argtypes = [vp, C.POINTER(i32)]
+    lib.rsrgan_g_state_reset.argtypes = [vp, p, vp]
+    lib.rsrgan_g_state_get.argtypes = [vp, p, vp]
+    lib.rsrgan_g_state_set.argtypes = [vp, p, vp]
+    lib.rsrgan_forward_g_stream.argtypes = [vp, p, p, i32, p, vp]
     lib.rsrgan_d_step.argtypes = [vp, p, p, p, i32, p, p, p, i32, vp]
     lib.rsrgan_g_step.argtypes = [vp, p, p, p, i32, p, p, i32, i32, vp]
     lib.rsrgan_d_backward.argtypes = [vp, p, p, p, i32, p, p, p, vp]

@@ -228,6 +228,71 @@ int rsrgan_forward_g(rsrgan_handle h, const float* x, const int32_t* lengths, in
   });
 }
 
+// ---- the stateful generator forward ----
+static int gstate_check(Model& m, const char* what) {
+  if (m.g_dnn()) { set_error("%s: frame-level generators (dnn, rced) carry no recurrent state", what); return RSRGAN_ERR_INVALID; }
+  if (m.g_bnl()) { set_error("%s: g_type bnlstm: the stateful forward is not built", what); return RSRGAN_ERR_INVALID; }
+  if (!m.g_state) { set_error("%s: this generator has no carried state", what); return RSRGAN_ERR_INVALID; }
+  return RSRGAN_OK;
+}
+int rsrgan_g_state_floats(rsrgan_handle h, int32_t* n) {
+  CHECK_H(h);
+  if (!n) { set_error("null argument"); return RSRGAN_ERR_INVALID; }
+  if (int rc = gstate_check(h->m, "rsrgan_g_state_floats")) return rc;
+  *n = h->m.g_state_sf;
+  return RSRGAN_OK;
+}
+int rsrgan_g_state_reset(rsrgan_handle h, const int32_t* row_mask, void* stream) {
+  CHECK_H(h);
+  return guard("rsrgan_g_state_reset", [&]() -> int {
+    Model& m = h->m;
+    if (int rc = gstate_check(m, "rsrgan_g_state_reset")) return rc;
+    StreamScope sc(m, stream);
+    m.gstate_xfer(2, 0, m.Bt, row_mask, sc.work);
+    if (hipGetLastError() != hipSuccess) { set_error("kernel launch failed in g_state_reset"); return RSRGAN_ERR_HIP; }
+    return RSRGAN_OK;
+  });
+}
+static int gstate_copy(rsrgan_handle h, float* buf, bool get, void* stream, const char* what) {
+  CHECK_H(h);
+  return guard(what, [&]() -> int {
+    Model& m = h->m;
+    if (int rc = gstate_check(m, what)) return rc;
+    if (!buf) { set_error("%s: null pointer", what); return RSRGAN_ERR_INVALID; }
+    StreamScope sc(m, stream);
+    const size_t bytes = (size_t)m.Bt * m.g_state_sf * sizeof(float);      // (the caller's rows are rows [0, Bt) of a padded handle)
+    if (hipMemcpyAsync(get ? buf : m.g_state, get ? m.g_state : buf, bytes, hipMemcpyDeviceToDevice, sc.work) != hipSuccess) {
+      set_error("%s: hipMemcpyAsync failed", what); return RSRGAN_ERR_HIP;
+    }
+    return RSRGAN_OK;
+  });
+}
+int rsrgan_g_state_get(rsrgan_handle h, float* dst, void* stream) { return gstate_copy(h, dst, true, stream, "rsrgan_g_state_get"); }
+int rsrgan_g_state_set(rsrgan_handle h, const float* src, void* stream) { return gstate_copy(h, const_cast<float*>(src), false, stream, "rsrgan_g_state_set"); }
+
+int rsrgan_forward_g_stream(rsrgan_handle h, const float* x, const int32_t* lengths, int32_t T, float* y, void* stream) {
+  CHECK_H(h);
+  return guard("rsrgan_forward_g_stream", [&]() -> int {
+    Model& m = h->m;
+    if (int rc = gstate_check(m, "rsrgan_forward_g_stream")) return rc;
+    if (!y) { set_error("null output"); return RSRGAN_ERR_INVALID; }
+    StreamScope sc(m, stream);
+    hipStream_t s = sc.work;
+    int rc = m.prepare_batch(x, nullptr, lengths, T, s);
+    if (rc) return rc;
+    m.bn_eval_call = false;
+    m.gstate_xfer(0, 0, m.B, nullptr, s);           // slot 0 of every layer's c / mst <- the carried state (padding rows: zeros)
+    struct Carry { Model& m; explicit Carry(Model& m_) : m(m_) { m.g_carry = true; } ~Carry() { m.g_carry = false; } };
+    { Carry on(m); m.g_forward(T, s); }
+    m.g_fwd_valid = false;
+    // a row past its length copies its state through, so slot T holds every row's state after its lengths[b] frames
+    m.gstate_xfer(1, T, m.Bt, nullptr, s);
+    launch_unpack_bm(m.y_tm, m.ldDout, y, m.B, T, m.Dout, s, m.Bt);
+    if (hipGetLastError() != hipSuccess) { set_error("kernel launch failed in forward_g_stream"); return RSRGAN_ERR_HIP; }
+    return RSRGAN_OK;
+  });
+}
+
 int rsrgan_d_backward(rsrgan_handle h, const float* x, const float* labels, const int32_t* lengths, int32_t T,
                       const float* nr, const float* nf, float* out_losses, void* stream) {
   CHECK_H(h);

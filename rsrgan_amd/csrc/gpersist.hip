@@ -343,7 +343,10 @@ struct GpLds {
 // input).  The reducer of a half chunk is also the owner of that half chunk of the running sum: it adds its masked m(t) to the half
 // chunk of s_{l-1}(t) (layer 0: the input rows in memory; above: what the same-numbered reducer of the layer below published a step
 // ago), writes it to res_out and publishes it in the second region of gran2, where the layer above's X waves gather their x(t).
-template <int NT, int PROG, bool RES, bool TAG>
+// CARRY: the stateful forward (rsrgan_forward_g_stream): the initial state of every row is what slot 0 of the layer's c / mst stash
+// holds -- the host puts the handle's carried state there in front of the launch (kernels.hip k_gstate) -- instead of cell.zero_state.
+// A variant of its own: the launches of the training steps keep the code they had.
+template <int NT, int PROG, bool RES, bool TAG, bool CARRY = false>
 __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S, const unsigned c1, const unsigned bid) {
   static_assert(!(TAG && PROG), "the progressive sweeps know the sentinel form only");
   constexpr int NR = GP_NR, NU = NT * NR, CW = 4 * NT;
@@ -394,8 +397,18 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
     if (k < 3) S.peep[cl][k] = (k == 0 ? L.wi : k == 1 ? L.wf : L.wo)[cell];
     else S.bias[cl][k - 3] = L.bias[(k - 3) * H + cell];
   }
-  for (int e = tid; e < GP_NR * GP_NKB * 64; e += GP_WAVES * 64)       // the carried state m(-1) is zero (cell.zero_state)
-    *reinterpret_cast<f32x4*>(&S.mB[0][0][0][0] + 4 * e) = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (CARRY) {
+    // the carried state m(-1) = slot 0 of mst, as B fragments: lane (q, lr) of (tile r, k-block jb) = row 16 r + lr, columns 16 jb + 4 q ..
+    for (int e = tid; e < GP_NR * GP_NKB * 64; e += GP_WAVES * 64) {
+      const int ln = e & 63, jb = (e >> 6) % GP_NKB, r = e / (64 * GP_NKB);
+      const int col = 16 * jb + 4 * (ln >> 4);
+      const float4 v = *reinterpret_cast<const float4*>(L.mst + (size_t)(row0 + 16 * r + (ln & 15)) * ldP + min(col, ldP - 4));
+      *reinterpret_cast<f32x4*>(&S.mB[0][0][0][0] + 4 * e) = f32x4{col < P ? v.x : 0.f, col + 1 < P ? v.y : 0.f, col + 2 < P ? v.z : 0.f, col + 3 < P ? v.w : 0.f};
+    }
+  } else {
+    for (int e = tid; e < GP_NR * GP_NKB * 64; e += GP_WAVES * 64)     // the carried state m(-1) is zero (cell.zero_state)
+      *reinterpret_cast<f32x4*>(&S.mB[0][0][0][0] + 4 * e) = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
   if (tid < 32) (&S.cnt_x[0][0])[tid] = 0u;
   if (tid < GP_ROWS) S.len[tid] = a.len[row0 + tid];
   __syncthreads();
@@ -426,6 +439,15 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
     }
     // cell units of a row tile: gate tile w on every wave, gate tile 4 + w' (w' = 0 .. NT - 5) on wave w' as well
     float cprev[NR][2] = {{0.f, 0.f}, {0.f, 0.f}};
+    if (CARRY) {                                                       // c(-1) of this lane's cells: slot 0 of the c stash
+#pragma unroll
+      for (int r = 0; r < NR; ++r)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const int cell = cell0 + 4 * (w + 4 * s) + q;
+          if (w + 4 * s < NT && cell < H) cprev[r][s] = L.c[(size_t)(row0 + 16 * r + lr) * H + cell];
+        }
+    }
     // every LDS access below is one base register + a compile-time offset (hipcc otherwise hoists dozens of loop-invariant addresses
     // out of the step loop and spills them)
     float* const pbw = &S.pb[w][0][0][lane][0];                        // + (i * NR + r) * 256
@@ -450,7 +472,7 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
           f32x4 acc[NT];
 #pragma unroll
           for (int i = 0; i < NT; ++i) acc[i] = *reinterpret_cast<const f32x4*>(pbw + (i * NR + r) * 256);
-          if (t > 0) {
+          if (CARRY || t > 0) {                                          // (m(-1) = 0 needs no product)
             __builtin_amdgcn_s_setprio(2);
 #pragma unroll
             for (int jj = 0; jj < GP_KBW; ++jj) {
@@ -652,12 +674,19 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
   const int rrow = row0 + 16 * r + ((32 * hh + (lane & 31)) & 15), rcol = 16 * jbr + 4 * ((32 * hh + (lane & 31)) >> 4);
   const int rlen = a.len[rrow];
   f32x4 mcar = {0.f, 0.f, 0.f, 0.f};                                   // carried state of the reducer's four columns (the stash's mst)
-  // slot 0 of the carried states is zero (cell.zero_state)
-  for (int e = gw * 64 + lane; e < GP_ROWS * NT; e += 256) {
-    const int row = e / NT, cq = e - row * NT;
-    if (cell0 + 4 * cq < H) *reinterpret_cast<float4*>(L.c + (size_t)(row0 + row) * H + cell0 + 4 * cq) = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (CARRY) {                                                         // slot 0 of the carried states is the caller's: read, not written
+    if (reducer && gp == 1 && lane < 32 && rcol < ldP) {
+      const float4 v = *reinterpret_cast<const float4*>(L.mst + (size_t)rrow * ldP + rcol);
+      mcar = f32x4{v.x, v.y, v.z, v.w};
+    }
+  } else {
+    // slot 0 of the carried states is zero (cell.zero_state)
+    for (int e = gw * 64 + lane; e < GP_ROWS * NT; e += 256) {
+      const int row = e / NT, cq = e - row * NT;
+      if (cell0 + 4 * cq < H) *reinterpret_cast<float4*>(L.c + (size_t)(row0 + row) * H + cell0 + 4 * cq) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (reducer && gp == 1 && lane < 32 && rcol < ldP) *reinterpret_cast<float4*>(L.mst + (size_t)rrow * ldP + rcol) = make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  if (reducer && gp == 1 && lane < 32 && rcol < ldP) *reinterpret_cast<float4*>(L.mst + (size_t)rrow * ldP + rcol) = make_float4(0.f, 0.f, 0.f, 0.f);
   if (r >= nrt) return;                                                // (a tile of padding rows: nothing to project, publish, sum or gather)
   for (int t = 0; t < T; ++t) {
     const int par = t & 1, par1 = (int)((c1 + (unsigned)t) % GP_R1);      // (c1 = 0 without tags)
@@ -782,14 +811,14 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
 #endif
 }
 
-template <int NT, int PROG, bool RES, bool TAG>
+template <int NT, int PROG, bool RES, bool TAG, bool CARRY = false>
 __global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_fwd(const GPersistArgs a) {
   __shared__ __attribute__((aligned(16))) GpLds<NT> S;
   gu32* ctl = (gu32*)a.ctl;
   const unsigned gen = __hip_atomic_load(ctl + DP_CTL_GEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (counts launches; nothing depends on it)
   // (TAG) steps written to the hop-1 ring by the launches so far, mod 2 GP_R1: every workgroup reads it here, the last one to finish moves it on
   const unsigned c1 = TAG ? __hip_atomic_load(ctl + GP_CTL_C1 + GP_CIDX(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-  gp_fwd_body<NT, PROG, RES, TAG>(a, S, c1, blockIdx.x);
+  gp_fwd_body<NT, PROG, RES, TAG, CARRY>(a, S, c1, blockIdx.x);
   __syncthreads();                                                 // (every wave leaves the body on every path)
   if (threadIdx.x == 0) {
     const unsigned old = __hip_atomic_fetch_add(ctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1691,7 +1720,7 @@ struct NpLds {
   unsigned cnt_x[GP_NR][4], cnt_p[GP_NR], cnt_h[GP_NR], cnt_m[GP_NR], cnt_s[GP_NR], dead, pad_[15];
 };
 
-template <int NT, int KR, int KX>
+template <int NT, int KR, int KX, bool CARRY = false>      // CARRY: as gp_fwd_body's
 __device__ __forceinline__ void np_fwd_body(const GPersistArgs& a, NpLds<NT, KR, KX>& S) {
   static_assert(sizeof(NpLds<NT, KR, KX>) <= 160 * 1024, "LDS of the unprojected forward kernel");
   constexpr int NR = GP_NR, NU = NT * NR, CW = 4 * NT;
@@ -1718,8 +1747,17 @@ __device__ __forceinline__ void np_fwd_body(const GPersistArgs& a, NpLds<NT, KR,
     if (k < 3) S.peep[cl][k] = (k == 0 ? L.wi : k == 1 ? L.wf : L.wo)[cell];
     else S.bias[cl][k - 3] = L.bias[(k - 3) * H + cell];
   }
-  for (int e = tid; e < GP_NR * NP_NKB * 64; e += GP_WAVES * 64)       // the carried state h(-1) is zero (cell.zero_state)
-    *reinterpret_cast<f32x4*>(&S.mB[0][0][0][0] + 4 * e) = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (CARRY) {                                                         // the carried state h(-1) = slot 0 of mst, as B fragments
+    for (int e = tid; e < GP_NR * NP_NKB * 64; e += GP_WAVES * 64) {
+      const int ln = e & 63, jb = (e >> 6) % NP_NKB, r = e / (64 * NP_NKB);
+      const int col = 16 * jb + 4 * (ln >> 4);
+      const float4 v = *reinterpret_cast<const float4*>(L.mst + (size_t)(row0 + 16 * r + (ln & 15)) * ldP + min(col, ldP - 4));
+      *reinterpret_cast<f32x4*>(&S.mB[0][0][0][0] + 4 * e) = f32x4{col < P ? v.x : 0.f, col + 1 < P ? v.y : 0.f, col + 2 < P ? v.z : 0.f, col + 3 < P ? v.w : 0.f};
+    }
+  } else {
+    for (int e = tid; e < GP_NR * NP_NKB * 64; e += GP_WAVES * 64)     // the carried state h(-1) is zero (cell.zero_state)
+      *reinterpret_cast<f32x4*>(&S.mB[0][0][0][0] + 4 * e) = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
   if (tid < 32) (&S.cnt_x[0][0])[tid] = 0u;
   __syncthreads();
   const unsigned* dead = &S.dead;
@@ -1752,6 +1790,10 @@ __device__ __forceinline__ void np_fwd_body(const GPersistArgs& a, NpLds<NT, KR,
     }
     float cprev[NR] = {0.f, 0.f};
     const bool cellw = w < NT;                                        // this wave owns gate tile w (NT = 2: waves 0, 1)
+    if (CARRY && cellw) {                                             // c(-1) of this lane's cell: slot 0 of the c stash
+#pragma unroll
+      for (int r = 0; r < NR; ++r) cprev[r] = L.c[(size_t)(row0 + 16 * r + lr) * H + cell0 + 4 * w + q];
+    }
     float* const pbw = &S.pb[w][0][0][lane][0];                        // + (i * NR + r) * 256
     const float* const mbw = &S.mB[0][w][lane][0];                     // + (r * NP_NKB + 4 jj) * 256
     const float* const khw = &S.khl[w][0][0][lane][0];                 // + ((jj - KR) * NT + i) * 256
@@ -1767,7 +1809,7 @@ __device__ __forceinline__ void np_fwd_body(const GPersistArgs& a, NpLds<NT, KR,
           f32x4 acc[NT];
 #pragma unroll
           for (int i = 0; i < NT; ++i) acc[i] = *reinterpret_cast<const f32x4*>(pbw + (i * NR + r) * 256);
-          if (t > 0) {
+          if (CARRY || t > 0) {
             __builtin_amdgcn_s_setprio(2);
 #pragma unroll
             for (int jj = 0; jj < NP_KBW; ++jj) {
@@ -1927,11 +1969,18 @@ __device__ __forceinline__ void np_fwd_body(const GPersistArgs& a, NpLds<NT, KR,
   const int pjb = (CW * c) >> 4;                                       // the chunk this workgroup writes into
   const unsigned poff = (unsigned)(((CW * c) & 15) >> 2) * 256u + (unsigned)lane * 16u;      // ... and its quads' offset inside it (quad-major: 256 bytes per quad)
   f32x4 mcar = {0.f, 0.f, 0.f, 0.f};                                   // carried state of this lane's four cells (the stash's mst)
-  for (int e = gw * 64 + lane; e < GP_ROWS * NT; e += 256) {           // slot 0 of the carried states is zero (cell.zero_state)
-    const int row = e / NT, cq = e - row * NT;
-    if (cell0 + 4 * cq < H) {
-      *reinterpret_cast<float4*>(L.c + (size_t)(row0 + row) * H + cell0 + 4 * cq) = make_float4(0.f, 0.f, 0.f, 0.f);
-      *reinterpret_cast<float4*>(L.mst + (size_t)(row0 + row) * ldP + cell0 + 4 * cq) = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (CARRY) {                                                         // slot 0 of the carried states is the caller's: read, not written
+    if (gp == 1 && pubq && scol < H) {
+      const float4 v = *reinterpret_cast<const float4*>(L.mst + (size_t)srow * ldP + scol);
+      mcar = f32x4{v.x, v.y, v.z, v.w};
+    }
+  } else {
+    for (int e = gw * 64 + lane; e < GP_ROWS * NT; e += 256) {         // slot 0 of the carried states is zero (cell.zero_state)
+      const int row = e / NT, cq = e - row * NT;
+      if (cell0 + 4 * cq < H) {
+        *reinterpret_cast<float4*>(L.c + (size_t)(row0 + row) * H + cell0 + 4 * cq) = make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4*>(L.mst + (size_t)(row0 + row) * ldP + cell0 + 4 * cq) = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
     }
   }
   for (int t = 0; t < T; ++t) {
@@ -1958,12 +2007,12 @@ __device__ __forceinline__ void np_fwd_body(const GPersistArgs& a, NpLds<NT, KR,
   }
 }
 
-template <int NT, int KR, int KX>
+template <int NT, int KR, int KX, bool CARRY = false>
 __global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_np_fwd(const GPersistArgs a) {
   __shared__ __attribute__((aligned(16))) NpLds<NT, KR, KX> S;
   gu32* ctl = (gu32*)a.ctl;
   const unsigned gen = __hip_atomic_load(ctl + DP_CTL_GEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  np_fwd_body<NT, KR, KX>(a, S);
+  np_fwd_body<NT, KR, KX, CARRY>(a, S);
   __syncthreads();
   if (threadIdx.x == 0) {
     const unsigned old = __hip_atomic_fetch_add(ctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2396,6 +2445,15 @@ void gpersist_arm(const GPersistArgs& a, hipStream_t s) {
 void launch_glstm_fwd(const GPersistArgs& a, hipStream_t s) {
   gp_arm_gran2(a, s);
   const dim3 g(gp_grid(a)), b(GP_WAVES * 64);
+  if (a.carry) {                                                       // the stateful forward: the CARRY variants
+    if (a.tags && !GP_PROG_ONLY) {
+      if (a.res) hipLaunchKernelGGL((k_glstm_fwd<5, 0, true, true, true>), g, b, 0, s, a);
+      else hipLaunchKernelGGL((k_glstm_fwd<5, 0, false, true, true>), g, b, 0, s, a);
+    } else if (a.res) hipLaunchKernelGGL((k_glstm_fwd<5, GP_PROG_ONLY, true, false, true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_glstm_fwd<5, GP_PROG_ONLY, false, false, true>), g, b, 0, s, a);
+    ++g_chain_launches;
+    return;
+  }
   if (a.tags && !GP_PROG_ONLY) {
     if (a.res) hipLaunchKernelGGL((k_glstm_fwd<5, 0, true, true>), g, b, 0, s, a);
     else hipLaunchKernelGGL((k_glstm_fwd<5, 0, false, true>), g, b, 0, s, a);
@@ -2426,7 +2484,10 @@ size_t gpersist_np_gran2_bytes(const GPersistArgs& a) { return (size_t)(a.N / GP
 size_t gpersist_np_lds_bytes() { return sizeof(NpLds<4, 7, 6>); }
 void launch_glstm_np_fwd(const GPersistArgs& a, hipStream_t s) {
   gpersist_arm_bytes(a.gran2, gpersist_np_gran2_bytes(a), s);
-  if (a.NT == 2) hipLaunchKernelGGL((k_glstm_np_fwd<2, 8, 8>), dim3(gp_grid(a)), dim3(GP_WAVES * 64), 0, s, a);
+  if (a.carry) {
+    if (a.NT == 2) hipLaunchKernelGGL((k_glstm_np_fwd<2, 8, 8, true>), dim3(gp_grid(a)), dim3(GP_WAVES * 64), 0, s, a);
+    else hipLaunchKernelGGL((k_glstm_np_fwd<4, 7, 6, true>), dim3(gp_grid(a)), dim3(GP_WAVES * 64), 0, s, a);
+  } else if (a.NT == 2) hipLaunchKernelGGL((k_glstm_np_fwd<2, 8, 8>), dim3(gp_grid(a)), dim3(GP_WAVES * 64), 0, s, a);
   else hipLaunchKernelGGL((k_glstm_np_fwd<4, 7, 6>), dim3(gp_grid(a)), dim3(GP_WAVES * 64), 0, s, a);
   ++g_chain_launches;
 }

@@ -247,6 +247,9 @@ struct GPersistArgs {
   // bit 0: a lane's off-chain work waits for the lane's publication (gp_fwd_body: the X waves' product of step t + 1 and the R waves' stash
   // store of step t start when the G waves have issued the partial projections of step t: LDS counter cnt_j) instead of colliding with it
   int sched;
+  // the stateful forward (rsrgan_forward_g_stream): every row starts from slot 0 of the layers' c / mst stash as the host left it
+  // (Model::gstate_load) instead of cell.zero_state; the forward launches only (k_glstm_fwd / k_glstm_np_fwd, their CARRY variants)
+  int carry;
 };
 constexpr int GP_TMAX = 2046;                     // longest launch (slot offsets are 32-bit; a longer batch takes the launch-per-phase path)
 bool gpersist_plan(GPersistArgs& a);              // fills NT / NC; false: shape not supported
@@ -357,6 +360,12 @@ void launch_im2col(const float* src, size_t row_stride, int ldc, int C, int S, i
                    hipStream_t s);
 void launch_expand_c4(const float* src, int ld_src, int n, float* dst, size_t rows, hipStream_t s);
 void launch_col2im(const float* dcol, int ldk, int C, int S, int W, int kh, int kw, float* dst, int ldc, size_t M, hipStream_t s);
+// The generator's CARRIED state (rsrgan_forward_g_stream): state [rows][SF], one row = layer 0's c [H], layer 0's m [P], layer 1's c, ...
+// dir 0: state -> slot `slot` (a row offset, t * N) of every layer's c / mst stash (mst's padding columns zero); dir 1: the slot -> state;
+// dir 2: zero the state of the rows whose mask entry is non-zero (mask null: all rows).  One workgroup per row.
+struct GStateLayer { float *c, *mst; int H, P, ldP, off; };
+struct GStateArgs { GStateLayer L[GP_MAXL]; int nl, SF, rows, dir; float* state; size_t slot; const int* mask; };
+void launch_gstate(const GStateArgs& a, hipStream_t s);
 struct ZeroList { int n; float* p[32]; unsigned len[32]; };        // many small buffers zeroed by ONE launch
 void launch_zero_many(const ZeroList& zl, hipStream_t s);
 struct ColsumsBatch { const float* dz[4]; const float* cprev[4]; const float* ccur[4]; float* db[4]; float* dwi[4]; float* dwf[4]; float* dwo[4]; int n; };

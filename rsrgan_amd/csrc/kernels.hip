@@ -1393,6 +1393,34 @@ void launch_col2im(const float* dcol, int ldk, int C, int S, int W, int kh, int 
                      dst, ldc, M);
 }
 
+__global__ void k_gstate(GStateArgs a) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  float* st = a.state + (size_t)row * a.SF;
+  if (a.dir == 2) {
+    if (a.mask && a.mask[row] == 0) return;
+    for (int i = tid; i < a.SF; i += blockDim.x) st[i] = 0.f;
+    return;
+  }
+  for (int l = 0; l < a.nl; ++l) {
+    const GStateLayer L = a.L[l];
+    float* c = L.c + (a.slot + row) * L.H;
+    float* m = L.mst + (a.slot + row) * L.ldP;
+    float* sc = st + L.off;
+    float* sm = sc + L.H;
+    if (a.dir == 0) {
+      for (int i = tid; i < L.H; i += blockDim.x) c[i] = sc[i];
+      for (int i = tid; i < L.ldP; i += blockDim.x) m[i] = i < L.P ? sm[i] : 0.f;
+    } else {
+      for (int i = tid; i < L.H; i += blockDim.x) sc[i] = c[i];
+      for (int i = tid; i < L.P; i += blockDim.x) sm[i] = m[i];
+    }
+  }
+}
+void launch_gstate(const GStateArgs& a, hipStream_t s) {
+  if (a.rows <= 0) return;
+  hipLaunchKernelGGL(k_gstate, dim3(a.rows), dim3(256), 0, s, a);
+}
+
 __global__ void k_zero_many(ZeroList zl) {
   const int j = blockIdx.y;
   if (j >= zl.n) return;

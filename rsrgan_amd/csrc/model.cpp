@@ -317,6 +317,11 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   const int ldP = g_dnn() ? 4 : pad4(P);
   g_st.resize(gl.size());
   for (size_t l = 0; l < gl.size(); ++l) alloc_stash(*this, g_st[l], gl[l], B, Tmax);
+  if (!g_dnn() && !g_bnl() && !gl.empty() && gl.size() <= (size_t)GP_MAXL) {      // the carried state of the stateful forward
+    for (auto& L : gl) g_state_sf += L.H + L.P;
+    g_state = alloc<float>((size_t)B * g_state_sf);
+    if (!g_state) { set_error("hipMalloc failed (carried generator state)"); return RSRGAN_ERR_HIP; }
+  }
   g_ins.resize(gl.size() + 1);
   if (g_rced()) {
     const size_t M = TB * rcS * rcW;
@@ -885,6 +890,7 @@ void Model::rnn_forward(std::vector<Chain>& chains, int T, hipStream_t s, const 
     ZeroList zl{};
     for (auto& ch : chains)
       for (auto& R : ch) {
+        if (R.carry) continue;                       // (the stateful forward: slot 0 holds the carried state)
         if (zl.n + 2 > 32) { launch_zero_many(zl, s); zl.n = 0; }
         zl.p[zl.n] = R.S->c + (size_t)R.row0 * R.L->H; zl.len[zl.n++] = (unsigned)((size_t)R.N * R.L->H);
         zl.p[zl.n] = R.S->mst + (size_t)R.row0 * R.L->ldP; zl.len[zl.n++] = (unsigned)((size_t)R.N * R.L->ldP);
@@ -1140,6 +1146,7 @@ bool Model::persist_forward_g(int T, hipStream_t s) {
   GPersistArgs a{};
   if (!gpersist_args(a, T) || (gp_noproj ? gpersist_np_gran2_bytes(a) : gpersist_gran2_bytes(a)) > gp_gran2_bytes) return false;
   a.L[0].in = g_ins[0];                                // (layer 0's input product runs inside the launch as well)
+  a.carry = g_carry ? 1 : 0;                           // (the stateful forward: the CARRY variants of the same launches, counted alike)
   if (gp_noproj) {                                     // num_proj=None: the single-hop form (no event bracket: bench.py's dominant-kernel timing is the projected form's)
     for (size_t l = 0; l < gl.size(); ++l) a.L[l].Wp = nullptr;
     launch_glstm_np_fwd(a, s);
@@ -1713,6 +1720,7 @@ Chain Model::g_chain(int T) {
     R.ps = &G; R.L = &gl[l]; R.S = &g_st[l]; R.in = g_ins[l];
     R.N = B; R.Ns = B; R.row0 = 0; R.len = len_dev;
     R.zx_batched = (l == 0);                 // layer 0's input exists for all t before the wave starts
+    R.carry = g_carry;
     if (res) { R.res_in = g_ins[l]; R.res_out = g_res[l]; }   // inputs_{l+1} = outputs_l + inputs_l (res_lstm_l.py:111,121,131,190)
     if (seq_drop_on()) R.drop = DropSpec{drop_ctr, drop_seed, (1ull << 40) | ((unsigned long long)l << 20), drop_thr(), keep_prob};
     ch.push_back(R);
@@ -1730,6 +1738,17 @@ Chain Model::d_chain(int N, int Ns, int row0) {
     ch.push_back(R);
   }
   return ch;
+}
+
+void Model::gstate_xfer(int dir, int T, int rows, const int* mask, hipStream_t s) {
+  GStateArgs a{};
+  a.nl = (int)gl.size(); a.SF = g_state_sf; a.rows = rows; a.dir = dir; a.state = g_state; a.slot = (size_t)T * B; a.mask = mask;
+  int off = 0;
+  for (size_t l = 0; l < gl.size(); ++l) {
+    a.L[l] = GStateLayer{g_st[l].c, g_st[l].mst, gl[l].H, gl[l].P, gl[l].ldP, off};
+    off += gl[l].H + gl[l].P;
+  }
+  launch_gstate(a, s);
 }
 
 void Model::g_forward_head(int T, hipStream_t s) {

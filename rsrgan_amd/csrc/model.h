@@ -96,6 +96,7 @@ struct LayerRun {
   float* din = nullptr;           // [T][Ns][ldI] gradient w.r.t. the layer input (nullptr = not needed)
   bool din_accumulate = false;
   bool want_wgrads = false;
+  bool carry = false;             // forward: slot 0 of c / mst holds the caller's initial state (Model::g_carry): not zeroed
   DropSpec drop{};                // DropoutWrapper on this layer's output (tag = the layer's; the jobs add t); ctr == nullptr: off
 };
 typedef std::vector<LayerRun> Chain;
@@ -229,6 +230,14 @@ struct Model {
   bool gpersist_args(GPersistArgs& a, int T) const;       // false: not applicable
   void gpersist_rearm();                                  // the "not written" pattern in every ring slot (after allocation, after a failed launch)
   bool persist_forward_g(int T, hipStream_t s);           // layer 0's x-part batched first; fills the complete stash of every layer
+  // ---- the generator's carried state (rsrgan_forward_g_stream): [B][g_state_sf] floats, a row = layer 0's c, layer 0's m,
+  // layer 1's c, ... unpadded; zero after init.  Only the stateful forward and the rsrgan_g_state_* calls touch it: it goes into slot 0
+  // of the c / mst stashes in front of the forward (gstate_xfer(0, ..)) and comes back from slot T behind it, so every forward plan
+  // carries it -- the persistent launches read slot 0 instead of writing zeros (GPersistArgs::carry), rnn_forward leaves it alone.
+  float* g_state = nullptr;
+  int g_state_sf = 0;
+  bool g_carry = false;                                   // the forward being issued is the stateful one
+  void gstate_xfer(int dir, int T, int rows, const int* mask, hipStream_t s);
   typedef std::function<void(hipStream_t)> StreamFn;
   bool persist_backward_g(Chain& ch, int T, hipStream_t s, bool check_only = false, const StreamFn& pre = nullptr, const StreamFn& post = nullptr);   // BPTT of the generator chain (k_glstm_bwd), layer 0's input gradient as a GEMM, the weight gradients unless deferred
   // fully-connected stacks: models/dnn.py generator and models/discriminator_dnn.py discriminator

@@ -331,6 +331,48 @@ class HipEngine:
         check(self.lib.rsrgan_forward_g(self.h, _ptr(x), _ptr(ln), T, _ptr(y), self._stream()))
         return y
 
+    # -- the stateful forward (include/rsrgan.h: the carried generator state) -------------
+    def g_state_floats(self) -> int:
+        """floats of one row's state blob: layer 0's c, layer 0's m, layer 1's c, ... unpadded"""
+        n = C.c_int32()
+        check(self.lib.rsrgan_g_state_floats(self.h, C.byref(n)))
+        return n.value
+
+    def g_state_reset(self, rows=None):
+        """zero the carried state of the rows in `rows` (an iterable of row indices); None = every row"""
+        mask = None
+        if rows is not None:
+            m = np.zeros(self.batch_size, dtype=np.int32)
+            for r in rows:
+                if not 0 <= int(r) < self.batch_size:
+                    raise ValueError("row %d outside [0, batch_size=%d)" % (int(r), self.batch_size))
+                m[int(r)] = 1
+            mask = self._i32(m)
+        check(self.lib.rsrgan_g_state_reset(self.h, _ptr(mask), self._stream()))
+        self._keep_mask = mask
+
+    def g_state_get(self) -> torch.Tensor:
+        out = torch.empty(self.batch_size, self.g_state_floats(), dtype=torch.float32, device=self.device)
+        check(self.lib.rsrgan_g_state_get(self.h, _ptr(out), self._stream()))
+        return out
+
+    def g_state_set(self, t):
+        t = self._f32(t, (self.batch_size, self.g_state_floats()))
+        check(self.lib.rsrgan_g_state_set(self.h, _ptr(t), self._stream()))
+        self._keep_state = t
+
+    def forward_g_stream(self, x, lengths) -> torch.Tensor:
+        """forward_g from and into the carried state: row b continues where its previous call ended and advances by lengths[b]"""
+        x = self._f32(x)
+        if lengths is None:
+            raise ValueError("forward_g_stream needs lengths")
+        ln = self._i32(lengths)
+        T = self._check_batch(x, None, ln)
+        y = torch.empty(self.batch_size, T, self.output_dim, dtype=torch.float32, device=self.device)
+        check(self.lib.rsrgan_forward_g_stream(self.h, _ptr(x), _ptr(ln), T, _ptr(y), self._stream()))
+        self._keep3 = (x, ln)
+        return y
+
     def d_backward(self, x, lab, lengths, noise_real=None, noise_fake=None, train=True, apply=False) -> torch.Tensor:
         if os.environ.get("RSRGAN_DPIPE", "0") not in ("", "0"):      # the library reads labels / lengths ahead of the stream: hand it complete ones
             lab = self.upload_ready(lab)

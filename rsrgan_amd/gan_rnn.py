@@ -356,6 +356,19 @@ class GAN_RNN(Model):
         y = self.engine.forward_g(inputs, lengths)
         return y.cpu().numpy() if not isinstance(inputs, torch.Tensor) else y
 
+    def forward_stream(self, inputs, lengths, reset=None):
+        """forward() from and into the engine's carried generator state: row b continues where its previous call ended and advances
+        by lengths[b] frames (0: the row rests).  `reset`: rows (an iterable of indices, or True for all) whose state is zeroed
+        first -- the rows that begin a new utterance with this call.  Inference only; no training call sees the carried state."""
+        if reset is True:
+            self.engine.g_state_reset(None)
+        elif reset is not None and reset is not False:
+            rows = [int(r) for r in reset]
+            if rows:
+                self.engine.g_state_reset(rows)
+        y = self.engine.forward_g_stream(inputs, lengths)
+        return y.cpu().numpy() if not isinstance(inputs, torch.Tensor) else y
+
     # -- variables ---------------------------------------------------------------------
     def get_vars(self):
         """d_vars / g_vars split by name prefix with the reference's asserts (:301-317)."""

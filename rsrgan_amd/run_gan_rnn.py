@@ -59,6 +59,10 @@ def build_parser():
     p.add_argument("--apply_cmvn", type=str2bool, nargs="?", default="true", help="normalise with data_dir/train_cmvn.npz "
                    "(make_tfrecords.py:84-87 did this when writing TFRecords)")
     p.add_argument("--max_frames", type=int, default=3000, help="capacity of the padded time axis")
+    p.add_argument("--decode_chunk", type=int, default=0, help="decode: frames per forward call; > 0 decodes utterances of any length "
+                   "in chunks that carry the generator's state (0: one whole utterance per call, at most max_frames)")
+    p.add_argument("--decode_streams", type=int, default=1, help="decode with --decode_chunk: utterances decoded side by side, one per "
+                   "batch row")
     return p
 
 
@@ -157,9 +161,11 @@ def train(FLAGS, model_factory=None, log=print, net_overrides=None):
 
 def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
     """decode (:204-302): batch 1, G(x), de-normalise with the label CMVN, write feats.ark / feats.scp."""
-    mk = model_factory or (lambda: GAN_RNN(None, argparse.Namespace(**dict(vars(FLAGS), batch_size=1)), ["gpu:%d" % rdist.rank()],
-                                           cross_validation=True, infer=True, max_frames=FLAGS.max_frames,
-                                           net_overrides=net_overrides))
+    chunk, streams = int(getattr(FLAGS, "decode_chunk", 0) or 0), max(1, int(getattr(FLAGS, "decode_streams", 1) or 1))
+    # (--decode_chunk N: the handle holds N frames of `streams` rows; an utterance is a sequence of calls that carry the state)
+    mk = model_factory or (lambda: GAN_RNN(None, argparse.Namespace(**dict(vars(FLAGS), batch_size=streams if chunk > 0 else 1)),
+                                           ["gpu:%d" % rdist.rank()], cross_validation=True, infer=True,
+                                           max_frames=chunk if chunk > 0 else FLAGS.max_frames, net_overrides=net_overrides))
     model = mk()
     if model.load(model.save_dir, moving_average=False):
         log("[*] Load SUCCESS")
@@ -175,11 +181,26 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
     reader = ArkReader()
     reader(FLAGS.test_inputs_scp)
     start = datetime.datetime.now()
-    for i, utt in enumerate(reader.utt_ids):
+
+    def features(i):
         x = reader.read_utt_data_from_index(i).astype(np.float64)
         if cmvn is not None:
             x = (x - cmvn["mean_inputs"]) / cmvn["stddev_inputs"]
-        x = splice_feats(x, FLAGS.left_context, FLAGS.right_context).astype(np.float32)[None]
+        return splice_feats(x, FLAGS.left_context, FLAGS.right_context).astype(np.float32)
+
+    if chunk > 0:
+        from .stream import decode_streams
+        outs = decode_streams(model, (features(i) for i in range(len(reader.utt_ids))), chunk, streams)
+        for i, (utt, activations) in enumerate(zip(reader.utt_ids, outs)):         # (in scp order, as the loop below writes them)
+            activations = np.asarray(activations)
+            sequence = activations * cmvn["stddev_labels"] + cmvn["mean_labels"] if cmvn is not None else activations
+            writer.write_next_utt(write_ark_path, utt, sequence)
+            log("[{}/{}] Write inferred {} to {}".format(i + 1, len(reader.utt_ids), utt, write_ark_path))
+        writer.close()
+        log("Decoding time is {}s".format((datetime.datetime.now() - start).total_seconds()))
+        return write_scp_path
+    for i, utt in enumerate(reader.utt_ids):
+        x = features(i)[None]
         activations = np.asarray(model.forward(x, np.array([x.shape[1]], np.int32)))
         sequence = activations * cmvn["stddev_labels"] + cmvn["mean_labels"] if cmvn is not None else activations
         writer.write_next_utt(write_ark_path, utt, np.vstack(sequence))

@@ -1,0 +1,142 @@
+#!/usr/bin/env python
+"""Decode throughput and streaming latency of the sequence generators, one JSON line per configuration.
+
+    python tools/decode_bench.py [--g_type res_lstm_l] [--utts 256] [--min_frames 200] [--max_frames 1500] [--repeats 3]
+                                 [--configs a,b,c,d,live] [--lib path/to/librsrgan_hip.so]
+
+A seeded synthetic test set (utterance lengths uniform in [min_frames, max_frames], N(0,1) features, the handle's initial
+variables) goes through
+
+    a     whole utterances, batch_size 1: run_gan_rnn.decode's loop (model.forward per utterance, handle of max_frames frames)
+    b     --decode_chunk 200 --decode_streams 1   (rsrgan_amd.stream.decode_streams)
+    c     --decode_chunk 200 --decode_streams 32
+    d     --decode_chunk 200 --decode_streams 64
+    live  one stream on a batch_size-1 handle: ms per StreamEnhancer.push of 10 / 50 / 100 frames (median and p90 of the pushes
+          of one long utterance; the host waits for every push's output, as a recogniser behind it would)
+
+and reports utterances/s and frames/s of every repeat (host wall clock around the whole set, device drained at the end: the
+copies of the inputs and outputs are part of decoding).  `--lib`: time another build of the library (configuration a only
+makes sense for a build without the stateful forward)."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+from types import SimpleNamespace
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def build(g_type, batch, frames, din, dout):
+    from rsrgan_amd import GAN_RNN
+    args = SimpleNamespace(batch_size=batch, input_dim=din, output_dim=dout, left_context=0, right_context=0, g_type=g_type,
+                           keep_prob=1.0, batch_norm=False, num_gpu=1, save_dir=None, l2_scale=0.0)
+    return GAN_RNN(None, args, ["gpu:0"], cross_validation=True, infer=True, max_frames=frames)
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--g_type", default="res_lstm_l")
+    p.add_argument("--utts", type=int, default=256)
+    p.add_argument("--min_frames", type=int, default=200)
+    p.add_argument("--max_frames", type=int, default=1500)
+    p.add_argument("--chunk", type=int, default=200)
+    p.add_argument("--repeats", type=int, default=3)
+    p.add_argument("--configs", default="a,b,c,d,live")
+    p.add_argument("--input_dim", type=int, default=257)
+    p.add_argument("--output_dim", type=int, default=40)
+    p.add_argument("--seed", type=int, default=1234)
+    p.add_argument("--lib", default=None)
+    a = p.parse_args(argv)
+    if a.lib:
+        from rsrgan_amd import _lib
+        _lib.LIB_PATH = os.path.abspath(a.lib)
+        import ctypes
+
+        class OlderBuild(ctypes.CDLL):
+            """a build from before the stateful forward lacks its entry points: the binding may still set their argtypes (on a stand-in
+            that nothing calls: configuration a uses rsrgan_forward_g only)"""
+            def __getattr__(self, name):
+                try:
+                    return super().__getattr__(name)
+                except AttributeError:
+                    if name.startswith("rsrgan_g_state_") or name == "rsrgan_forward_g_stream":
+                        return SimpleNamespace()
+                    raise
+        _lib.C.CDLL = OlderBuild
+    import torch
+    rng = np.random.default_rng(a.seed)
+    lens = rng.integers(a.min_frames, a.max_frames + 1, size=a.utts)
+    utts = [rng.standard_normal((int(n), a.input_dim)).astype(np.float32) for n in lens]
+    frames = int(lens.sum())
+    base = dict(g_type=a.g_type, utterances=a.utts, frames=frames, min_frames=a.min_frames, max_frames=a.max_frames,
+                device=torch.cuda.get_device_name(0), lib=a.lib or "built")
+
+    def report(name, extra, secs):
+        rec = dict(base, config=name, **extra)
+        rec["seconds"] = [round(s, 4) for s in secs]
+        rec["utts_per_s"] = [round(a.utts / s, 2) for s in secs]
+        rec["frames_per_s"] = [round(frames / s, 1) for s in secs]
+        rec["utts_per_s_median"] = round(a.utts / float(np.median(secs)), 2)
+        print(json.dumps(rec), flush=True)
+
+    def timed(fn):
+        fn()                                              # warm-up: allocations, the library's lazy copies, first launches
+        secs = []
+        for _ in range(a.repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            secs.append(time.perf_counter() - t0)
+        return secs
+
+    for name in [c.strip() for c in a.configs.split(",") if c.strip()]:
+        if name == "a":
+            model = build(a.g_type, 1, a.max_frames, a.input_dim, a.output_dim)
+
+            def whole():
+                for u in utts:
+                    model.forward(u[None], np.array([len(u)], np.int32))
+            report("a", dict(batch_size=1, chunk=0, streams=1), timed(whole))
+        elif name in ("b", "c", "d"):
+            from rsrgan_amd.stream import decode_streams
+            streams = {"b": 1, "c": 32, "d": 64}[name]
+            model = build(a.g_type, streams, a.chunk, a.input_dim, a.output_dim)
+
+            def chunked():
+                n = sum(1 for _ in decode_streams(model, iter(utts), a.chunk, streams))
+                assert n == len(utts)
+            report(name, dict(batch_size=streams, chunk=a.chunk, streams=streams), timed(chunked))
+        elif name == "live":
+            from rsrgan_amd.stream import StreamEnhancer
+            model = build(a.g_type, 1, 100, a.input_dim, a.output_dim)
+            enh = StreamEnhancer(model, None, 0, 0, chunk=100)
+            long_utt = rng.standard_normal((3000, a.input_dim)).astype(np.float32)
+            out = {}
+            for n in (10, 50, 100):
+                ms = []
+                for rep in range(2):                      # (the first pass warms up)
+                    ms = []
+                    for pos in range(0, len(long_utt), n):
+                        t0 = time.perf_counter()
+                        enh.push(long_utt[pos:pos + n])   # returns host arrays: the device has finished
+                        ms.append(1e3 * (time.perf_counter() - t0))
+                    enh.flush()
+                out["push_%d" % n] = dict(pushes=len(ms), ms_median=round(float(np.median(ms)), 4), ms_p90=round(float(np.percentile(ms, 90)), 4),
+                                          ms_per_frame=round(float(np.median(ms)) / n, 5))
+            print(json.dumps(dict(base, config="live", batch_size=1, **out)), flush=True)
+        else:
+            raise SystemExit("unknown configuration %r" % name)
+        del model
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
