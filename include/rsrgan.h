@@ -49,7 +49,11 @@ enum { RSRGAN_G_LSTM = 0, RSRGAN_G_RES_LSTM_L = 1, RSRGAN_G_RES_LSTM_BASE = 2,
        RSRGAN_G_RCED = 4, /* models/rced.py: frame-level 9 x conv2d + FC generator (dnn_trainer.py:98-99), batch_norm=False */
        RSRGAN_G_BNLSTM = 5 /* models/bnlstm.py: input FC + ReLU, BNLSTMCell(g_cells, num_proj=g_proj, peepholes) x g_layers with batch
                               normalisation inside the recurrence, output FC; RSRGAN_FLAG_SUPERVISED only (models/rnn_trainer.py),
-                              batch_size <= 64, no RSRGAN_FLAG_BATCH_NORM, no dropout */ };
+                              batch_size <= 64, no RSRGAN_FLAG_BATCH_NORM, no dropout */,
+       RSRGAN_G_RES_LSTM_I = 6 /* models/res_lstm_i.py: res_lstm_l's cells and variable table, but the residual is always the stack's
+                                  input: inputs_{l+1} = outputs_l + x, the output FC reads outputs_L + x (never a running sum);
+                                  needs g_proj == input_dim; RSRGAN_FLAG_SUPERVISED only (models/rnn_trainer.py:97-108: the
+                                  reference GAN has no such generator) */ };
 /* self.discriminator (gan_rnn_placeholder.py:117; models/gan.py:104) */
 enum { RSRGAN_D_LSTM = 0, RSRGAN_D_DNN = 1 /* models/discriminator_dnn.py */ };
 /* which network a call addresses */
@@ -81,7 +85,7 @@ typedef struct rsrgan_cfg {
   int32_t input_dim;       /* input_dim*(left_context+1+right_context) (:96-98) */
   int32_t output_dim;      /* 40 */
   int32_t g_type;          /* RSRGAN_G_* */
-  int32_t g_layers;        /* 3 (lstm) / 4 (res_lstm_*) */
+  int32_t g_layers;        /* 3 (lstm) / 4 (res_lstm_l, res_lstm_base) / 2 (res_lstm_i) */
   int32_t g_cells;         /* 760 */
   int32_t g_proj;          /* 280 (lstm) / 257 (res_lstm_*) */
   int32_t d_type;          /* RSRGAN_D_LSTM */

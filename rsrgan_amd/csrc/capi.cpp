@@ -57,6 +57,7 @@ int rsrgan_default_cfg(int32_t g_type, rsrgan_cfg* c) {
   c->g_type = g_type;
   if (g_type == RSRGAN_G_LSTM) { c->g_layers = 3; c->g_cells = 760; c->g_proj = 280; }           // models/lstm.py:43-45
   else if (g_type == RSRGAN_G_RES_LSTM_L || g_type == RSRGAN_G_RES_LSTM_BASE) { c->g_layers = 4; c->g_cells = 760; c->g_proj = 257; }  // models/res_lstm_l.py:43-45
+  else if (g_type == RSRGAN_G_RES_LSTM_I) { c->g_layers = 2; c->g_cells = 760; c->g_proj = 257; }  // models/res_lstm_i.py:43-44,101-118 (two layers are built)
   else if (g_type == RSRGAN_G_DNN) { c->g_layers = 4; c->g_cells = 1024; c->g_proj = 0; }        // models/dnn.py:34-35 (1+3 hidden layers)
   else if (g_type == RSRGAN_G_RCED) { c->g_layers = 9; c->g_cells = 32; c->g_proj = 0; c->g_splice = 11; }   // models/rced.py:92-93 (fixed filter table)
   else if (g_type == RSRGAN_G_BNLSTM) { c->g_layers = 3; c->g_cells = 760; c->g_proj = 280; }    // models/bnlstm.py:41-43

@@ -346,9 +346,13 @@ struct GpLds {
 // CARRY: the stateful forward (rsrgan_forward_g_stream): the initial state of every row is what slot 0 of the layer's c / mst stash
 // holds -- the host puts the handle's carried state there in front of the launch (kernels.hip k_gstate) -- instead of cell.zero_state.
 // A variant of its own: the launches of the training steps keep the code they had.
-template <int NT, int PROG, bool RES, bool TAG, bool CARRY = false>
+// RESX (with RES; models/res_lstm_i.py:101-190): the residual is the stack's input at EVERY layer, never a running sum -- layer l + 1 reads
+// out_l + x, the output FC out_{L-1} + x.  The reducer adds its masked m(t) to its half chunk of x(t), read from the stack's input rows in
+// memory as RES does for layer 0; nothing is polled from the layer below.  res_out and the second region of gran2 as under RES.
+template <int NT, int PROG, bool RES, bool TAG, bool CARRY = false, bool RESX = false>
 __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S, const unsigned c1, const unsigned bid) {
   static_assert(!(TAG && PROG), "the progressive sweeps know the sentinel form only");
+  static_assert(RES || !RESX, "RESX is a form of RES");
   constexpr int NR = GP_NR, NU = NT * NR, CW = 4 * NT;
   GPT_DECL
   const int tid = threadIdx.x, lane = tid & 63, lr = lane & 15, q = lane >> 4;
@@ -786,7 +790,11 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
       const bool act = lane < 32;
       const unsigned off = slot2(t, r, jbr) + (unsigned)hh * 512u + (unsigned)(lane & 31) * 16u;
       f32x4 sb;
-      if (l == 0) {
+      if (RESX) {                                                        // x(t) itself at every layer (gpersist_plan: every layer as wide as the stack's input)
+        const int ldx = a.L[0].ldI;
+        const float4 v = *reinterpret_cast<const float4*>(a.L[0].in + ((size_t)t * N + rrow) * ldx + min(rcol, ldx - 4));
+        sb = rcol < ldx ? f32x4{v.x, v.y, v.z, v.w} : f32x4{0.f, 0.f, 0.f, 0.f};
+      } else if (l == 0) {
         const float4 v = *reinterpret_cast<const float4*>(L.in + ((size_t)t * N + rrow) * L.ldI + min(rcol, L.ldI - 4));
         sb = rcol < L.ldI ? f32x4{v.x, v.y, v.z, v.w} : f32x4{0.f, 0.f, 0.f, 0.f};
       } else {
@@ -819,6 +827,28 @@ __global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_fwd(const GPersistAr
   // (TAG) steps written to the hop-1 ring by the launches so far, mod 2 GP_R1: every workgroup reads it here, the last one to finish moves it on
   const unsigned c1 = TAG ? __hip_atomic_load(ctl + GP_CTL_C1 + GP_CIDX(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
   gp_fwd_body<NT, PROG, RES, TAG, CARRY>(a, S, c1, blockIdx.x);
+  __syncthreads();                                                 // (every wave leaves the body on every path)
+  if (threadIdx.x == 0) {
+    const unsigned old = __hip_atomic_fetch_add(ctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (old == gridDim.x - 1) {
+      if (TAG) __hip_atomic_store(ctl + GP_CTL_C1 + GP_CIDX(a), (c1 + (unsigned)a.T) % (2u * GP_R1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (__hip_atomic_load(ctl + DP_CTL_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
+        a.L[a.nl - 1].out[0] = __builtin_nanf("");
+      __hip_atomic_store(ctl + DP_CTL_DONE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned g1 = gen + 1u;
+      __hip_atomic_store(ctl + DP_CTL_GEN, g1 >= (1u << 21) ? 1u : g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+// res_lstm_i's forward stack (gp_fwd_body RESX): a kernel of its own, so that every instantiation of k_glstm_fwd stays what it was
+template <int NT, int PROG, bool TAG, bool CARRY>
+__global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_fwd_ri(const GPersistArgs a) {
+  __shared__ __attribute__((aligned(16))) GpLds<NT> S;
+  gu32* ctl = (gu32*)a.ctl;
+  const unsigned gen = __hip_atomic_load(ctl + DP_CTL_GEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (counts launches; nothing depends on it)
+  // (TAG) steps written to the hop-1 ring by the launches so far, mod 2 GP_R1: every workgroup reads it here, the last one to finish moves it on
+  const unsigned c1 = TAG ? __hip_atomic_load(ctl + GP_CTL_C1 + GP_CIDX(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+  gp_fwd_body<NT, PROG, true, TAG, CARRY, true>(a, S, c1, blockIdx.x);
   __syncthreads();                                                 // (every wave leaves the body on every path)
   if (threadIdx.x == 0) {
     const unsigned old = __hip_atomic_fetch_add(ctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2445,6 +2475,15 @@ void gpersist_arm(const GPersistArgs& a, hipStream_t s) {
 void launch_glstm_fwd(const GPersistArgs& a, hipStream_t s) {
   gp_arm_gran2(a, s);
   const dim3 g(gp_grid(a)), b(GP_WAVES * 64);
+  if (a.res == 2) {                                                    // res_lstm_i: out_l + x at every layer (gp_fwd_body RESX)
+    if (a.tags && !GP_PROG_ONLY) {
+      if (a.carry) hipLaunchKernelGGL((k_glstm_fwd_ri<5, 0, true, true>), g, b, 0, s, a);
+      else hipLaunchKernelGGL((k_glstm_fwd_ri<5, 0, true, false>), g, b, 0, s, a);
+    } else if (a.carry) hipLaunchKernelGGL((k_glstm_fwd_ri<5, GP_PROG_ONLY, false, true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_glstm_fwd_ri<5, GP_PROG_ONLY, false, false>), g, b, 0, s, a);
+    ++g_chain_launches;
+    return;
+  }
   if (a.carry) {                                                       // the stateful forward: the CARRY variants
     if (a.tags && !GP_PROG_ONLY) {
       if (a.res) hipLaunchKernelGGL((k_glstm_fwd<5, 0, true, true, true>), g, b, 0, s, a);

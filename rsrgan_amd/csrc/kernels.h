@@ -229,6 +229,8 @@ struct GPersistArgs {
   int ld_din0;
   // models/res_lstm_l.py:101-194: inputs_{l+1} = outputs_l + inputs_l (inputs_1 = the stack's input, L[0].in; needs I == P everywhere).
   // gran2 then holds a second region of the same size: the running sums s_l (forward) / their gradients (backward), one slot per step.
+  // 2: models/res_lstm_i.py:101-190, inputs_{l+1} = outputs_l + the stack's input at every layer (the forward launch only, k_glstm_fwd_ri;
+  // its BPTT is the plain stack's: the caller clears res for the backward launch).
   int res;
   // ring slots told apart by the parity of the ring pass in every word's lowest bit instead of sentinels that somebody has to put back
   // (gpersist.hip gp_store_t; the projected kernels only): no re-arming stores

@@ -250,9 +250,18 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
       add_lstm(G, gl, "g_model/rnn/multi_rnn_cell/cell_" + std::to_string(l) + "/lstm_cell", P, H, c.g_proj);
     g_fc_out_w = G.add("g_model/fully_connected_1/weights", P, Dout, false);
     g_fc_out_b = G.add("g_model/fully_connected_1/biases", 1, Dout, true);
-  } else if (c.g_type == RSRGAN_G_RES_LSTM_L || c.g_type == RSRGAN_G_RES_LSTM_BASE) {   // models/res_lstm_l.py:101-194
+  } else if (c.g_type == RSRGAN_G_RES_LSTM_L || c.g_type == RSRGAN_G_RES_LSTM_BASE || c.g_type == RSRGAN_G_RES_LSTM_I) {   // models/res_lstm_l.py:101-194
     if (c.g_type == RSRGAN_G_RES_LSTM_L && P != Din) {
       set_error("res_lstm_l needs g_proj == input_dim (models/res_lstm_l.py:111)");
+      return RSRGAN_ERR_INVALID;
+    }
+    // models/res_lstm_i.py:101-190: the same cells and variable names; the sums are outputs_l + the stack's input
+    if (c.g_type == RSRGAN_G_RES_LSTM_I && !supervised()) {
+      set_error("g_type res_lstm_i is built for the supervised trainer only (RSRGAN_FLAG_SUPERVISED; the reference GAN has no res_lstm_i generator)");
+      return RSRGAN_ERR_INVALID;
+    }
+    if (c.g_type == RSRGAN_G_RES_LSTM_I && P != Din) {
+      set_error("res_lstm_i needs g_proj == input_dim (models/res_lstm_i.py:111)");
       return RSRGAN_ERR_INVALID;
     }
     int in = Din;
@@ -383,7 +392,7 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   } else {
     g_ins[0] = x_tm;
     for (size_t l = 0; l < gl.size(); ++l) {
-      if (c.g_type == RSRGAN_G_RES_LSTM_L) {
+      if (c.g_type == RSRGAN_G_RES_LSTM_L || c.g_type == RSRGAN_G_RES_LSTM_I) {      // (res_lstm_i: g_res[l] = out_l + x)
         g_res.push_back(alloc<float>(TB * ldP));
         g_ins[l + 1] = g_res.back();
       } else {
@@ -1050,11 +1059,11 @@ int Model::trail_nrt() const {
   return on && B == 32 && Bt <= 16 && (gp_live & 3) == 3 && (dp_live & 3) == 3 ? 1 : 0;
 }
 bool Model::gpersist_shape(GPersistArgs& a, int T) const {              // (sizes only: usable before any buffer exists)
-  const bool res = cfg.g_type == RSRGAN_G_RES_LSTM_L && switches().gp_res;          // the running residual sum rides the hand-offs (gpersist.hip RES)
+  const bool res = (cfg.g_type == RSRGAN_G_RES_LSTM_L || g_resi()) && switches().gp_res;      // the running residual sum rides the hand-offs (gpersist.hip RES)
   // (res_lstm_base, models/res_lstm_base.py:101-139: the same stack of projected cells fed the input frames directly, no sums)
   if (!gp_live || gl.empty() || gl.size() > (size_t)GP_MAXL || (cfg.g_type != RSRGAN_G_LSTM && cfg.g_type != RSRGAN_G_RES_LSTM_BASE && !res)) return false;
   a = GPersistArgs{};
-  a.nl = (int)gl.size(); a.N = B; a.T = T; a.H = gl[0].H; a.res = res ? 1 : 0;
+  a.nl = (int)gl.size(); a.N = B; a.T = T; a.H = gl[0].H; a.res = res ? (g_resi() ? 2 : 1) : 0;      // (2: res_lstm_i, the sums are out_l + x -- gpersist.hip RESX, the forward launch only)
   bool noproj = !gl[0].has_proj;
   // ring slots tagged with the parity of the ring pass instead of re-armed with sentinels (gpersist.hip gp_store_t); RSRGAN_GP_TAGS=0: the sentinel form
   a.tags = switches().gp_tags && !noproj ? 1 : 0;
@@ -1201,7 +1210,7 @@ bool Model::persist_forward_real(int T, hipStream_t q, bool check_only) {
 bool Model::persist_forward_g_trail(Chain& ch, int T, hipStream_t s, const float* nf, bool check_only) {
   if (!switches().trail_fwd || !trail_fits || !gp_fwd_on() || gp_noproj || !wavefront() || seq_drop_on() || !dp_gran || !(dp_live & 1) || ch.size() != dl.size()) return false;
   GPersistArgs a{};
-  if (!gpersist_args(a, T) || gpersist_gran2_bytes(a) > gp_gran2_bytes) return false;
+  if (!gpersist_args(a, T) || a.res == 2 || gpersist_gran2_bytes(a) > gp_gran2_bytes) return false;      // (res_lstm_i: no fused launches)
   a.L[0].in = g_ins[0];
   a.fwd_trail = 1;
   DPersistArgs d{};
@@ -1255,11 +1264,15 @@ bool Model::persist_backward_g(Chain& ch, int T, hipStream_t s, bool check_only,
     else { if (pre) pre(s); if (post) post(s); }
     return true;
   }
+  // res_lstm_i: x is data, nothing flows into the residual branch -- d(out_{l-1}) = d(in_l) through K_x only, the plain stack's BPTT
+  // (the RES = false launches); the forward sums of the chain are the stack's input + out_l
+  const bool resi = a.res == 2;
+  if (resi) { a.res = 0; if (gp_trail_next) return false; }
   for (size_t l = 0; l < ch.size(); ++l) {
     const LayerRun& R = ch[l];
     if (R.L != &gl[l] || R.S != &g_st[l] || R.row0 != 0 || R.Ns != R.N || R.N != a.N || R.len != a.len) return false;
     if (!a.res) {
-      if (R.res_in || R.res_out) return false;
+      if (resi ? (R.res_in != g_ins[0] || R.res_out != g_res[l]) : (R.res_in || R.res_out)) return false;
       if (l > 0 && (R.din_accumulate || ch[l].din != ch[l - 1].dout)) return false;
     } else {
       // res_lstm_l: the callers keep d(inputs_l) = dx_l + d(inputs_{l+1}) accumulated in ONE buffer (dout == din, accumulate); inside the
@@ -1722,6 +1735,7 @@ Chain Model::g_chain(int T) {
     R.zx_batched = (l == 0);                 // layer 0's input exists for all t before the wave starts
     R.carry = g_carry;
     if (res) { R.res_in = g_ins[l]; R.res_out = g_res[l]; }   // inputs_{l+1} = outputs_l + inputs_l (res_lstm_l.py:111,121,131,190)
+    if (g_resi()) { R.res_in = g_ins[0]; R.res_out = g_res[l]; }      // inputs_{l+1} = outputs_l + x (res_lstm_i.py:111,190)
     if (seq_drop_on()) R.drop = DropSpec{drop_ctr, drop_seed, (1ull << 40) | ((unsigned long long)l << 20), drop_thr(), keep_prob};
     ch.push_back(R);
   }

@@ -166,7 +166,7 @@ struct Model {
   // generator activations (N = B rows per frame)
   float *x_tm = nullptr, *lab_tm = nullptr, *g_h0 = nullptr, *y_tm = nullptr;
   std::vector<float*> g_ins;      // g_ins[l] = input of layer l, g_ins[L] = input of the output FC
-  std::vector<float*> g_res;      // res_lstm_l: out_l + in_l buffers (g_ins[l+1] aliases these)
+  std::vector<float*> g_res;      // res_lstm_l: out_l + in_l buffers (g_ins[l+1] aliases these); res_lstm_i: out_l + x
   std::vector<LstmStash> g_st;
   float *g_dA = nullptr, *g_dB = nullptr, *g_dC = nullptr;   // ping-pong gradient buffers [T*B][max ld]
   // discriminator activations (N = 2B rows per frame)
@@ -248,6 +248,7 @@ struct Model {
   int *adam_t_dev_d = nullptr;
   bool g_dnn() const { return cfg.g_type == RSRGAN_G_DNN || cfg.g_type == RSRGAN_G_RCED; }   // frame-level generator
   bool g_rced() const { return cfg.g_type == RSRGAN_G_RCED; }
+  bool g_resi() const { return cfg.g_type == RSRGAN_G_RES_LSTM_I; }      // models/res_lstm_i.py: every layer above the first reads outputs + x
   // bnlstm generator (bnlstm.cpp): input FC + ReLU, BNLSTMCell layers, output FC; supervised trainer only
   std::vector<BnlCell> bnl;
   bool g_bnl() const { return cfg.g_type == RSRGAN_G_BNLSTM; }

@@ -32,7 +32,7 @@ namespace rsr {
   X(GP_NP_BWD,      gp_np_bwd,      BOOL, 1,    ANY,  process, "persistent BPTT of an unprojected generator (8 cells per workgroup); 0 = its BPTT takes the launch path") \
   X(GP_NP_NT,       gp_np_nt,       INT,  0,    ANY,  process, "gate tiles per workgroup of the unprojected generator's launches: 2 or 4; 0 = what the resident probe admits") \
   X(GP_NOPROJ,      gp_noproj,      BOOL, 1,    ANY,  process, "persistent forward recurrence for num_proj=None generators (the single-hop form); 0 = launch path") \
-  X(GP_RES,         gp_res,         BOOL, 1,    ANY,  process, "res_lstm_l inside the persistent launches (the running residual sum rides the hand-offs); 0 = launch path") \
+  X(GP_RES,         gp_res,         BOOL, 1,    ANY,  process, "res_lstm_l and res_lstm_i inside the persistent launches (the residual sums ride the hand-offs); 0 = launch path") \
   X(GP_TAGS,        gp_tags,        BOOL, 1,    ANY,  process, "ring slots tagged with the parity of the ring pass; 0 = slots re-armed with sentinels") \
   X(GP_NRT,         gp_nrt,         BOOL, 1,    ANY,  process, "a padded generator whose real rows fit one 16-row tile skips the padding tile; 0 = both tiles run") \
   X(DP_NRT,         dp_nrt,         BOOL, 1,    ANY,  process, "the same for the discriminator's halves of the fused launches (only together with GP_NRT); 0 = the padding tile runs") \

@@ -30,8 +30,10 @@ class _Args(object):
 
 
 class RNNTrainer(GAN_RNN):
-    """models/rnn_trainer.py:66 -- g_type in {lstm, res_lstm_l, res_lstm_base, bnlstm} (res_lstm_i is not built)."""
-    G_TYPES = GAN_RNN.G_TYPES + ("bnlstm",)
+    """models/rnn_trainer.py:66 -- g_type in {lstm, res_lstm_l, res_lstm_base, bnlstm, res_lstm_i}: all five of rnn_trainer.py:97-108.
+    res_lstm_i (models/res_lstm_i.py) is res_lstm_l's stack with the residual always taken from the stack's input
+    (inputs_{l+1} = outputs_l + x); it exists under this trainer only, GAN_RNN refuses it as the reference GAN does."""
+    G_TYPES = GAN_RNN.G_TYPES + ("bnlstm", "res_lstm_i")
 
     def __init__(self, sess, args, devices, inputs=None, labels=None, lengths=None, cross_validation=False,
                  name="RNNTrainer", *, max_frames: Optional[int] = None, engine=None, process_group=None, seed: int = 4321,
