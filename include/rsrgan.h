@@ -293,6 +293,43 @@ int rsrgan_op_gemm(const float* A, int32_t lda, int32_t a_kcontig,
                    float* C, int32_t ldc, int32_t M, int32_t N, int32_t K,
                    const float* bias, int32_t act, float alpha, int32_t accumulate, void* stream);
 
+/* The entries below exist for the unit parity tests only (tests/test_gpu_wgrad_ops.py, tests/test_op_args.py); no trainer calls them.
+ * Each goes through the host launch function the model calls, with a private workspace of the model's size (32 Mi floats).  Every
+ * argument error -- a null pointer, a leading dimension that is no multiple of 4, a table size outside the table, A2 together with
+ * a_kcontig, M1 % 4 != 0 -- returns RSRGAN_ERR_INVALID before the first HIP call, rsrgan_last_error() naming it.
+ *
+ * rsrgan_op_gemm2: rsrgan_op_gemm over the stacked operand [A | A2] (A stored [K][M1], A2 [K][M - M1]; A2 NULL: none) and / or a
+ * row map of A (map_rows_per > 0: row r of A is at A + (r / rows_per) * outer + (r % rows_per) * inner -- a window view of a
+ * [samples][positions][channels] activation; with a_kcontig the mapped index is the row m, without it the reduction index k).
+ * workers: worker slots of the stream-K launch for this call (0: the default, 256).  force_cfg: -1 = the planner's choice; 0..7 =
+ * that tile form (k_gemm 128x128, 96x128, 128x96, 256x64, 256x32; k_gemm_s 256x256, 128x256, 256x128) whatever the routing rule and
+ * the cost model say. */
+int rsrgan_op_gemm2(const float* A, int32_t lda, int32_t a_kcontig, const float* A2, int32_t lda2, int32_t M1,
+                    const float* B, int32_t ldb, int32_t b_kcontig, float* C, int32_t ldc, int32_t M, int32_t N, int32_t K,
+                    const float* bias, int32_t act, float alpha, int32_t accumulate,
+                    int32_t map_rows_per, int64_t map_outer, int64_t map_inner, int32_t workers, int32_t force_cfg, void* stream);
+/* nb same-shaped products C[b] (+)= [A[b] | A2[b]]^T-style (operands [K][M1 | M - M1], [K][N]) as ONE stream-K launch.  Returns
+ * RSRGAN_OP_NOT_APPLICABLE (nothing launched, C untouched: the caller runs them one by one) for nb < 2, nb > 4 and products below the
+ * routing threshold of the stream-K kernels; RSRGAN_OK when it launched. */
+#define RSRGAN_OP_NOT_APPLICABLE 1
+int rsrgan_op_gemm_batch(int32_t nb, const float* const* A, int32_t lda, const float* const* A2, int32_t lda2, int32_t M1,
+                         const float* const* B, int32_t ldb, float* const* C, int32_t ldc, int32_t M, int32_t N, int32_t K,
+                         int32_t accumulate, int32_t workers, void* stream);
+/* n = 1..4 same-shaped products on the split-K kernel in one launch (+ one reduce launch) */
+int rsrgan_op_gemm16_batch(int32_t n, const float* const* A, int32_t lda, const float* const* A2, int32_t lda2, int32_t M1,
+                           const float* const* B, int32_t ldb, float* const* C, int32_t ldc, int32_t M, int32_t N, int32_t K,
+                           int32_t accumulate, void* stream);
+/* what the calling thread's last GEMM launch was: out = { kernel class (1 gemm16, 2 n32, 3 k_gemm, 4 k_gemm_s, 5 gemm16 batch,
+ * 6 k_gemm batch, 7 k_gemm_s batch; 0: none yet), BM, BN, W, n_dp, 1 if a fix-up launch followed, split-K factor, Ur } */
+int rsrgan_op_gemm_last_plan(int32_t out[8]);
+/* LSTM bias / peephole column sums of nb = 1..4 layers: db[4H] = colsum(dz [rows][4H]); dwi = colsum(dz_i * cprev), dwf =
+ * colsum(dz_f * cprev), dwo = colsum(dz_o * ccur) (cprev, ccur [rows][H]).  nb = 1: the single-layer launch; nb > 1: the batch. */
+int rsrgan_op_lstm_colsums(int32_t nb, const float* const* dz, const float* const* cprev, const float* const* ccur, float* const* db,
+                           float* const* dwi, float* const* dwf, float* const* dwo, int32_t rows, int32_t H, void* stream);
+/* out[c] = sum_r a[r * lda + c] * (b ? b[r * ldb + c] : 1); tall != 0: the tall-and-narrow form (b must be NULL) */
+int rsrgan_op_colsum(const float* a, int32_t lda, const float* b, int32_t ldb, float* out, int32_t rows, int32_t cols, int32_t tall,
+                     void* stream);
+
 /* ---- SEGAN-style conv G/D (models/segan.py:SEGAN with generator.py:AEGenerator, discriminator.py:discriminator, utils/bnorm.py:VBN;
  * BASELINE.json configs[4]).  The reference's trainer cannot run as shipped (segan.py:136 calls an undefined variables_on_gpu0(),
  * scripts/train_segan.py:20 imports a missing module); the graph it would build is fully specified and is what these entry

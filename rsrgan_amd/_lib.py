@@ -24,7 +24,8 @@ SYMBOLS = ["rsrgan_default_cfg", "rsrgan_create", "rsrgan_destroy", "rsrgan_last
            "rsrgan_g_step", "rsrgan_d_backward", "rsrgan_g_backward", "rsrgan_apply", "rsrgan_grad_buffer",
            "rsrgan_grad_bucket_count", "rsrgan_grad_bucket_info", "rsrgan_grad_bucket_wait",
            "rsrgan_profile_begin", "rsrgan_profile_read", "rsrgan_profile_read_kind", "rsrgan_profile_launches", "rsrgan_op_launch_floor", "rsrgan_device_status", "rsrgan_set_dropout",
-           "rsrgan_op_gemm", "rsrgan_version",
+           "rsrgan_op_gemm", "rsrgan_op_gemm2", "rsrgan_op_gemm_batch", "rsrgan_op_gemm16_batch", "rsrgan_op_gemm_last_plan",
+           "rsrgan_op_lstm_colsums", "rsrgan_op_colsum", "rsrgan_version",
            "rsrgan_segan_default_cfg", "rsrgan_segan_create", "rsrgan_segan_destroy", "rsrgan_segan_set_scalar",
            "rsrgan_segan_num_tensors", "rsrgan_segan_tensor_info", "rsrgan_segan_param_count", "rsrgan_segan_get_params",
            "rsrgan_segan_set_params", "rsrgan_segan_forward_g", "rsrgan_segan_d_backward", "rsrgan_segan_g_backward",
@@ -102,6 +103,13 @@ def load():
     lib.rsrgan_profile_launches.argtypes = [vp, C.POINTER(i64)]
     lib.rsrgan_op_launch_floor.argtypes = [i32, i32, C.POINTER(C.c_double), vp]
     lib.rsrgan_op_gemm.argtypes = [p, i32, i32, p, i32, i32, p, i32, i32, i32, i32, p, i32, f32, i32, vp]
+    pp = C.POINTER(C.c_void_p)
+    lib.rsrgan_op_gemm2.argtypes = [p, i32, i32, p, i32, i32, p, i32, i32, p, i32, i32, i32, i32, p, i32, f32, i32, i32, i64, i64, i32, i32, vp]
+    lib.rsrgan_op_gemm_batch.argtypes = [i32, pp, i32, pp, i32, i32, pp, i32, pp, i32, i32, i32, i32, i32, i32, vp]
+    lib.rsrgan_op_gemm16_batch.argtypes = [i32, pp, i32, pp, i32, i32, pp, i32, pp, i32, i32, i32, i32, i32, vp]
+    lib.rsrgan_op_gemm_last_plan.argtypes = [C.POINTER(i32)]
+    lib.rsrgan_op_lstm_colsums.argtypes = [i32, pp, pp, pp, pp, pp, pp, pp, i32, i32, vp]
+    lib.rsrgan_op_colsum.argtypes = [p, i32, p, i32, p, i32, i32, i32, vp]
     lib.rsrgan_segan_default_cfg.argtypes = [C.POINTER(SeganCfg)]
     lib.rsrgan_segan_create.argtypes = [C.POINTER(SeganCfg), C.c_uint64, C.POINTER(vp)]
     lib.rsrgan_segan_destroy.argtypes = [vp]
@@ -119,6 +127,20 @@ def load():
     lib.rsrgan_segan_apply.argtypes = [vp, i32, vp]
     _lib = lib
     return lib
+
+
+OP_NOT_APPLICABLE = 1         # include/rsrgan.h RSRGAN_OP_NOT_APPLICABLE
+# rsrgan_op_gemm_last_plan: kernel classes and the fields of the record
+GEMM_CLASSES = {0: "none", 1: "gemm16", 2: "n32", 3: "k_gemm", 4: "k_gemm_s", 5: "gemm16_batch", 6: "k_gemm_batch", 7: "k_gemm_s_batch"}
+GEMM_PLAN_FIELDS = ("cls", "bm", "bn", "W", "n_dp", "fixup", "splits", "Ur")
+# force_cfg of rsrgan_op_gemm2: (kernel class, BM, BN) of each tile form
+GEMM_FORMS = [("k_gemm", 128, 128), ("k_gemm", 96, 128), ("k_gemm", 128, 96), ("k_gemm", 256, 64), ("k_gemm", 256, 32),
+              ("k_gemm_s", 256, 256), ("k_gemm_s", 128, 256), ("k_gemm_s", 256, 128)]
+
+
+def ptr_table(ptrs):
+    """a C array of device pointers (None stays NULL) for the batched operator entries"""
+    return (C.c_void_p * max(len(ptrs), 1))(*[None if q is None else q for q in ptrs])
 
 
 def check(rc):

@@ -507,16 +507,154 @@ int rsrgan_op_launch_floor(int32_t n, int32_t mode, double* us_per_launch, void*
   return rc;
 }
 
+// ---- unit-test entries of the operators (tests/test_gpu_gemm.py, test_gpu_wgrad_ops.py, test_op_args.py).  Each goes through the host
+// launch function the model calls, with a private workspace of the model's size (Model::gemm_ws_floats: 32 Mi floats -- with less,
+// launch_gemm_batch's 192 x 256 form, the one the training step runs, is never taken).  Every argument error returns before the
+// first HIP call, so the refusals are testable without a device.
+static const size_t g_op_ws_floats = (size_t)32 << 20;
+static const size_t g_op_scratch_floats = (size_t)2 << 20;       // column-sum partials (4 layers x 64 slices x 7 x 760 = 1.4 M)
+static float* op_ws() {
+  static float* ws = nullptr;
+  if (!ws && hipMalloc((void**)&ws, g_op_ws_floats * sizeof(float)) != hipSuccess) ws = nullptr;
+  return ws;
+}
+static float* op_scratch() {
+  static float* sc = nullptr;
+  if (!sc && hipMalloc((void**)&sc, g_op_scratch_floats * sizeof(float)) != hipSuccess) sc = nullptr;
+  return sc;
+}
+#define OP_REFUSE(cond, ...) do { if (cond) { set_error(__VA_ARGS__); return RSRGAN_ERR_INVALID; } } while (0)
+struct WorkersScope {            // narrows g_gemm_workers for one call (the step: 224 under DPIPE, 256 otherwise)
+  int saved;
+  explicit WorkersScope(int w) : saved(g_gemm_workers) { if (w > 0) g_gemm_workers = w; }
+  ~WorkersScope() { g_gemm_workers = saved; }
+};
+
 int rsrgan_op_gemm(const float* A, int32_t lda, int32_t a_kc, const float* B, int32_t ldb, int32_t b_kc, float* C, int32_t ldc,
                    int32_t M, int32_t N, int32_t K, const float* bias, int32_t act, float alpha, int32_t accumulate, void* stream) {
   if (!A || !B || !C || (lda & 3) || (ldb & 3)) { set_error("op_gemm: null pointer or leading dimension not a multiple of 4"); return RSRGAN_ERR_INVALID; }
-  // unit-test entry: a private split-K workspace so the same code path as the model is exercised
-  static float* ws = nullptr;
-  static const size_t ws_floats = (size_t)16 << 20;
-  if (!ws && hipMalloc((void**)&ws, ws_floats * sizeof(float)) != hipSuccess) ws = nullptr;
+  float* ws = op_ws();
   launch_gemm(A, lda, a_kc != 0, B, ldb, b_kc != 0, C, ldc, M, N, K, bias, act, alpha, accumulate != 0, (hipStream_t)stream,
-              ws, ws ? ws_floats : 0);
+              ws, ws ? g_op_ws_floats : 0);
   if (hipGetLastError() != hipSuccess) { set_error("op_gemm launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
+
+int rsrgan_op_gemm2(const float* A, int32_t lda, int32_t a_kc, const float* A2, int32_t lda2, int32_t M1, const float* B, int32_t ldb,
+                    int32_t b_kc, float* C, int32_t ldc, int32_t M, int32_t N, int32_t K, const float* bias, int32_t act, float alpha,
+                    int32_t accumulate, int32_t map_rows_per, int64_t map_outer, int64_t map_inner, int32_t workers, int32_t force_cfg,
+                    void* stream) {
+  OP_REFUSE(!A || !B || !C, "op_gemm2: null pointer (A, B or C)");
+  OP_REFUSE(M <= 0 || N <= 0 || K <= 0, "op_gemm2: M, N, K must be positive (got %d, %d, %d)", M, N, K);
+  OP_REFUSE((lda & 3) || (ldb & 3) || (ldc & 3) || (A2 && (lda2 & 3)), "op_gemm2: leading dimension not a multiple of 4 (lda %d, lda2 %d, ldb %d, ldc %d)", lda, lda2, ldb, ldc);
+  OP_REFUSE(workers < 0 || workers > 256, "op_gemm2: workers = %d outside 0 (default) .. 256", workers);
+  OP_REFUSE(force_cfg < -1 || force_cfg > 7, "op_gemm2: force_cfg = %d outside -1 (planner) .. 7", force_cfg);
+  OP_REFUSE(map_rows_per < 0, "op_gemm2: row map with rows_per = %d", map_rows_per);
+  if (map_rows_per > 0) {
+    OP_REFUSE(A2 != nullptr, "op_gemm2: A2 together with a row map");
+    OP_REFUSE(b_kc != 0, "op_gemm2: a row map together with b_kcontig");
+    OP_REFUSE((map_outer & 3) || (map_inner & 3), "op_gemm2: row map strides not multiples of 4 (outer %lld, inner %lld)", (long long)map_outer, (long long)map_inner);
+  }
+  if (A2) {
+    OP_REFUSE(a_kc != 0, "op_gemm2: A2 together with a_kcontig (the stacked operand is m-contiguous)");
+    OP_REFUSE(M1 <= 0 || M1 >= M, "op_gemm2: M1 = %d outside (0, M = %d)", M1, M);
+    OP_REFUSE(M1 & 3, "op_gemm2: M1 = %d is not a multiple of 4: every kernel moves the stacked operand in 16-byte chunks", M1);
+  }
+  float* ws = op_ws();
+  {
+    WorkersScope wsc(workers);
+    const GemmRowMap ma{map_rows_per, (long long)map_outer, (long long)map_inner};
+    launch_gemm_mapped(A, lda, ma, A2, lda2, M1, a_kc != 0, B, ldb, b_kc != 0, C, ldc, M, N, K, bias, act, alpha, accumulate != 0,
+                       (hipStream_t)stream, ws, ws ? g_op_ws_floats : 0, force_cfg);
+  }
+  if (hipGetLastError() != hipSuccess) { set_error("op_gemm2 launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
+
+int rsrgan_op_gemm_batch(int32_t nb, const float* const* A, int32_t lda, const float* const* A2, int32_t lda2, int32_t M1,
+                         const float* const* B, int32_t ldb, float* const* C, int32_t ldc, int32_t M, int32_t N, int32_t K,
+                         int32_t accumulate, int32_t workers, void* stream) {
+  OP_REFUSE(nb < 1 || nb > 64, "op_gemm_batch: nb = %d outside 1 .. 64 (more than %d: not applicable)", nb, GEMM_MAXB);
+  OP_REFUSE(!A || !B || !C, "op_gemm_batch: null pointer table (A, B or C)");
+  for (int b = 0; b < nb; ++b) OP_REFUSE(!A[b] || !B[b] || !C[b] || (A2 && !A2[b]), "op_gemm_batch: null pointer in problem %d", b);
+  OP_REFUSE(M <= 0 || N <= 0 || K <= 0, "op_gemm_batch: M, N, K must be positive (got %d, %d, %d)", M, N, K);
+  OP_REFUSE((lda & 3) || (ldb & 3) || (ldc & 3) || (A2 && (lda2 & 3)), "op_gemm_batch: leading dimension not a multiple of 4 (lda %d, lda2 %d, ldb %d, ldc %d)", lda, lda2, ldb, ldc);
+  OP_REFUSE(workers < 0 || workers > 256, "op_gemm_batch: workers = %d outside 0 (default) .. 256", workers);
+  if (A2) {
+    OP_REFUSE(M1 <= 0 || M1 >= M, "op_gemm_batch: M1 = %d outside (0, M = %d)", M1, M);
+    OP_REFUSE(M1 & 3, "op_gemm_batch: M1 = %d is not a multiple of 4: the kernels move the stacked operand in 16-byte chunks", M1);
+  }
+  float* ws = op_ws();
+  bool ran;
+  {
+    WorkersScope wsc(workers);
+    ran = launch_gemm_batch(nb, A, lda, A2, lda2, M1, B, ldb, C, ldc, M, N, K, accumulate != 0, (hipStream_t)stream, ws, ws ? g_op_ws_floats : 0);
+  }
+  if (hipGetLastError() != hipSuccess) { set_error("op_gemm_batch launch failed"); return RSRGAN_ERR_HIP; }
+  return ran ? RSRGAN_OK : RSRGAN_OP_NOT_APPLICABLE;
+}
+
+int rsrgan_op_gemm16_batch(int32_t n, const float* const* A, int32_t lda, const float* const* A2, int32_t lda2, int32_t M1,
+                           const float* const* B, int32_t ldb, float* const* C, int32_t ldc, int32_t M, int32_t N, int32_t K,
+                           int32_t accumulate, void* stream) {
+  OP_REFUSE(n < 1 || n > GEMM16_MAXB, "op_gemm16_batch: n = %d outside the table (1 .. %d)", n, GEMM16_MAXB);
+  OP_REFUSE(!A || !B || !C, "op_gemm16_batch: null pointer table (A, B or C)");
+  for (int p = 0; p < n; ++p) OP_REFUSE(!A[p] || !B[p] || !C[p] || (A2 && !A2[p]), "op_gemm16_batch: null pointer in problem %d", p);
+  OP_REFUSE(M <= 0 || N <= 0 || K <= 0, "op_gemm16_batch: M, N, K must be positive (got %d, %d, %d)", M, N, K);
+  OP_REFUSE((lda & 3) || (ldb & 3) || (ldc & 3) || (A2 && (lda2 & 3)), "op_gemm16_batch: leading dimension not a multiple of 4 (lda %d, lda2 %d, ldb %d, ldc %d)", lda, lda2, ldb, ldc);
+  if (A2) {
+    OP_REFUSE(M1 <= 0 || M1 >= M, "op_gemm16_batch: M1 = %d outside (0, M = %d)", M1, M);
+    OP_REFUSE(M1 & 3, "op_gemm16_batch: M1 = %d is not a multiple of 4: k_gemm16 loads the stacked operand as float4", M1);
+  }
+  Gemm16Batch bt{};
+  bt.n = n;
+  for (int p = 0; p < n; ++p) { bt.A[p] = A[p]; bt.A2[p] = A2 ? A2[p] : nullptr; bt.B[p] = B[p]; bt.C[p] = C[p]; }
+  float* ws = op_ws();
+  launch_gemm16_batch(bt, lda, lda2, M1, ldb, ldc, M, N, K, accumulate != 0, (hipStream_t)stream, ws, ws ? g_op_ws_floats : 0);
+  if (hipGetLastError() != hipSuccess) { set_error("op_gemm16_batch launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
+
+int rsrgan_op_gemm_last_plan(int32_t out[8]) {
+  OP_REFUSE(!out, "op_gemm_last_plan: null pointer");
+  const GemmPlanRecord& r = g_gemm_last_plan;
+  out[0] = r.cls; out[1] = r.bm; out[2] = r.bn; out[3] = r.W; out[4] = r.n_dp; out[5] = r.fixup; out[6] = r.splits; out[7] = r.Ur;
+  return RSRGAN_OK;
+}
+
+int rsrgan_op_lstm_colsums(int32_t nb, const float* const* dz, const float* const* cprev, const float* const* ccur, float* const* db,
+                           float* const* dwi, float* const* dwf, float* const* dwo, int32_t rows, int32_t H, void* stream) {
+  OP_REFUSE(nb < 1 || nb > 4, "op_lstm_colsums: nb = %d outside the table (1 .. 4)", nb);
+  OP_REFUSE(!dz || !cprev || !ccur || !db || !dwi || !dwf || !dwo, "op_lstm_colsums: null pointer table");
+  for (int p = 0; p < nb; ++p)
+    OP_REFUSE(!dz[p] || !cprev[p] || !ccur[p] || !db[p] || !dwi[p] || !dwf[p] || !dwo[p], "op_lstm_colsums: null pointer in layer %d", p);
+  OP_REFUSE(rows <= 0 || H <= 0, "op_lstm_colsums: rows and H must be positive (got %d, %d)", rows, H);
+  OP_REFUSE((size_t)nb * 64 * 7 * (size_t)H > g_op_scratch_floats, "op_lstm_colsums: nb x 64 x 7 x H = %zu floats of partials exceed the entry's scratch", (size_t)nb * 64 * 7 * (size_t)H);
+  float* sc = op_scratch();
+  if (!sc) { set_error("op_lstm_colsums: hipMalloc failed"); return RSRGAN_ERR_HIP; }
+  if (nb == 1) launch_lstm_colsums(dz[0], cprev[0], ccur[0], db[0], dwi[0], dwf[0], dwo[0], rows, H, sc, (hipStream_t)stream);
+  else {
+    ColsumsBatch cb{};
+    cb.n = nb;
+    for (int p = 0; p < nb; ++p) { cb.dz[p] = dz[p]; cb.cprev[p] = cprev[p]; cb.ccur[p] = ccur[p]; cb.db[p] = db[p]; cb.dwi[p] = dwi[p]; cb.dwf[p] = dwf[p]; cb.dwo[p] = dwo[p]; }
+    launch_lstm_colsums_batch(cb, rows, H, sc, (hipStream_t)stream);
+  }
+  if (hipGetLastError() != hipSuccess) { set_error("op_lstm_colsums launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
+
+int rsrgan_op_colsum(const float* a, int32_t lda, const float* b, int32_t ldb, float* out, int32_t rows, int32_t cols, int32_t tall,
+                     void* stream) {
+  OP_REFUSE(!a || !out, "op_colsum: null pointer (a or out)");
+  OP_REFUSE(rows <= 0 || cols <= 0, "op_colsum: rows and cols must be positive (got %d, %d)", rows, cols);
+  OP_REFUSE(lda < cols || (b && ldb < cols), "op_colsum: leading dimension below cols = %d (lda %d, ldb %d)", cols, lda, ldb);
+  OP_REFUSE(tall && b, "op_colsum: the tall form has no multiplier b");
+  OP_REFUSE((size_t)(tall ? 512 : 64) * (size_t)cols > g_op_scratch_floats, "op_colsum: cols = %d exceeds the entry's scratch", cols);
+  float* sc = op_scratch();
+  if (!sc) { set_error("op_colsum: hipMalloc failed"); return RSRGAN_ERR_HIP; }
+  if (tall) launch_colsum_tall(a, lda, out, rows, cols, sc, g_op_scratch_floats, (hipStream_t)stream);
+  else launch_colsum(a, lda, b, ldb, out, rows, cols, sc, (hipStream_t)stream);
+  if (hipGetLastError() != hipSuccess) { set_error("op_colsum launch failed"); return RSRGAN_ERR_HIP; }
   return RSRGAN_OK;
 }
 

@@ -884,6 +884,13 @@ static int pick_splits(int tiles, int nk, size_t out_bytes, int max_splits, doub
 }
 
 
+thread_local GemmPlanRecord g_gemm_last_plan = {0, 0, 0, 0, 0, 0, 0, 0};    // what this host thread launched last (host-only; rsrgan_op_gemm_last_plan)
+// The stacked operand [A | A2] moves in 16-byte chunks (k_gemm / k_gemm_s: one DMA chunk, k_gemm16: one float4), each taken whole from
+// A or whole from A2: a seam M1 that is no multiple of 4 would put a chunk across it and read the wrong rows.  Callers pad (model.cpp:
+// Ie = ldI into dk_tmp) or split the product; a call that does neither stops here instead of computing something else.
+static void require_m1_chunked(const float* A2, int M1, const char* who) {
+  if (A2 && (M1 & 3)) { fprintf(stderr, "rsrgan: %s: stacked operand [A | A2] with M1 = %d: M1 must be a multiple of 4 (16-byte chunks)\n", who, M1); abort(); }
+}
 thread_local int g_gemm_workers = 256;     // (per host thread: Model::g_backward narrows it around the launches that share the chip with the next D(real))
                                             // worker slots of a launch = one block (4 MFMA + 2 loader waves, ring of LDS buffers) per CU
 namespace {
@@ -942,11 +949,13 @@ void launch_cfg(GemmArgs& g, const Plan& pl, hipStream_t s, float* ws, GemmBatch
       static bool attr_b = false;
       if (!attr_b) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm<AKC, BKC, RT, CT, WM, MAPA, GemmBatch>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_b = true; }
       bt->tn1 = (g.N + BN - 1) / BN;
+      g_gemm_last_plan = GemmPlanRecord{GEMM_CLS_KGEMM_B, BM, BN, g.W, g.n_dp, cut ? 1 : 0, 1, g.Ur};
       hipLaunchKernelGGL((k_gemm<AKC, BKC, RT, CT, WM, MAPA, GemmBatch>), dim3(g.W), dim3(64 * (4 + NL)), lds, s, g, *bt);
       if (cut) hipLaunchKernelGGL((k_gemm_fixup<RT, CT, WM, GemmBatch>), dim3(g.NT - g.n_dp, RT * CT * 4 > 16 ? RT : 1), dim3(256), 0, s, g, *bt);
     }
     return;
   }
+  g_gemm_last_plan = GemmPlanRecord{GEMM_CLS_KGEMM, BM, BN, g.W, g.n_dp, cut ? 1 : 0, 1, g.Ur};
   hipLaunchKernelGGL((k_gemm<AKC, BKC, RT, CT, WM, MAPA>), dim3(g.W), dim3(64 * (4 + NL)), lds, s, g, NoBatch{0});
   if (cut) hipLaunchKernelGGL((k_gemm_fixup<RT, CT, WM>), dim3(g.NT - g.n_dp, RT * CT * 4 > 16 ? RT : 1), dim3(256), 0, s, g, NoBatch{0});
 }
@@ -970,13 +979,15 @@ void launch_cfg_s(GemmArgs& g, const Plan& pl, hipStream_t s, float* ws, BT* bt 
   g.Uq = U / g.W; g.Ur = U % g.W;
   BT btv{}; if (bt) { btv = *bt; }
   if constexpr (std::is_same<BT, GemmBatch>::value) btv.tn1 = (g.N + BN - 1) / BN;
+  const bool cut = U > 0 && !(U % g.W == 0 && (U / g.W) % g.NK == 0);
+  g_gemm_last_plan = GemmPlanRecord{std::is_same<BT, GemmBatch>::value ? GEMM_CLS_KGEMM_S_B : GEMM_CLS_KGEMM_S, BM, BN, g.W, g.n_dp, cut ? 1 : 0, 1, g.Ur};
   hipLaunchKernelGGL((k_gemm_s<AKC, BKC, RT, CT, WM, MAPA, BT>), dim3(g.W), dim3(256), lds, s, g, btv);
-  if (U > 0 && !(U % g.W == 0 && (U / g.W) % g.NK == 0))
+  if (cut)
     hipLaunchKernelGGL((k_gemm_fixup<RT, CT, WM, BT>), dim3(g.NT - g.n_dp, RT * CT * 4 > 16 ? RT : 1), dim3(256), 0, s, g, btv);
 }
 
 template <bool AKC, bool BKC, bool MAPA>
-void launch_layout(GemmArgs& g, hipStream_t s, float* ws, size_t ws_floats) {
+void launch_layout(GemmArgs& g, hipStream_t s, float* ws, size_t ws_floats, int force_cfg) {
   // (192 x 128 and 256 x 128 tiles were measured too: +4 % at 4096^3, slower on every shape of the training steps -- fewer, larger
   //  pieces to fix up -- and past the 256-register budget of a 6-wave block: they spill.  Not instantiated.)
   // 256 x 32 / 256 x 64: the window-view products of the first SEGAN layers have 16..64 output channels and ~1e5..1e6 rows
@@ -984,6 +995,10 @@ void launch_layout(GemmArgs& g, hipStream_t s, float* ws, size_t ws_floats) {
   static const int cfgs[][2] = {{128, 128}, {96, 128}, {128, 96}, {256, 64}, {256, 32}, {256, 256}, {128, 256}, {256, 128}};
   int best = 0;
   Plan bp{};
+  if (force_cfg >= 0 && force_cfg < 8) {      // (unit tests only: this tile form whatever the cost model says; plan_cfg still splits the work)
+    best = force_cfg;
+    bp = plan_cfg(g.M, g.N, g.K, cfgs[best][0], cfgs[best][1], g_gemm_workers, ws, ws_floats);
+  } else
   for (int c = 0; c < (switches().gemm_self ? 8 : 5); ++c) {
     // the 256-wide tiles pay off with at least two full rounds of whole tiles (measured: 4096^3 118-121 -> 131-133 TFLOP/s,
     // 32768 x 1024 x 1024 105-109 -> 116-118; 6400 x 1024 x 1024, 200 tiles of 128 x 256: 87 either way, the frame-level step 2 % slower)
@@ -1021,6 +1036,7 @@ static void launch_gemm16(const float* A, int lda, const float* A2, int lda2, in
   float* w = splits > 1 ? ws : nullptr;
   dim3 grid(gx, gy, splits), block(256);
   const int acc = accumulate ? 1 : 0;
+  g_gemm_last_plan = GemmPlanRecord{GEMM_CLS_GEMM16, BM, BN, 0, 0, 0, splits, 0};
   if (a_kc && !b_kc)
     hipLaunchKernelGGL((k_gemm16<true, false>), grid, block, 0, s, A, lda, B, ldb, C, ldc, M, N, K, bias, act, alpha, acc, w, ldw, per, nullptr, 0, 0);
   else if (a_kc && b_kc)
@@ -1041,6 +1057,7 @@ static void launch_gemm16(const float* A, int lda, const float* A2, int lda2, in
 void launch_gemm16_batch(const Gemm16Batch& bt, int lda, int lda2, int M1, int ldb, int ldc, int M, int N, int K, bool accumulate,
                          hipStream_t s, float* ws, size_t ws_floats) {
   if (bt.n <= 0 || M <= 0 || N <= 0 || K <= 0) return;
+  for (int p = 0; p < bt.n; ++p) require_m1_chunked(bt.A2[p], M1, "launch_gemm16_batch");
   const int gx = (N + BN - 1) / BN, gy = (M + BM - 1) / BM;
   const int nk = (K + GBK - 1) / GBK;
   int splits = 1;
@@ -1053,6 +1070,7 @@ void launch_gemm16_batch(const Gemm16Batch& bt, int lda, int lda2, int M1, int l
   const int per = std::max(1, (nk + splits - 1) / splits);
   splits = std::max(1, (nk + per - 1) / per);
   float* w = splits > 1 ? ws : nullptr;
+  g_gemm_last_plan = GemmPlanRecord{GEMM_CLS_GEMM16_B, BM, BN, 0, 0, 0, splits, 0};
   hipLaunchKernelGGL(k_gemm16_b, dim3(gx, gy, splits * bt.n), dim3(256), 0, s, bt, lda, ldb, ldc, M, N, K, accumulate ? 1 : 0, w, ldw, per,
                      splits, lda2, M1);
   if (splits > 1) {
@@ -1064,10 +1082,12 @@ void launch_gemm16_batch(const Gemm16Batch& bt, int lda, int lda2, int M1, int l
 
 void launch_gemm_mapped(const float* A, int lda, const GemmRowMap& ma, const float* A2, int lda2, int M1, bool a_kc, const float* B, int ldb,
                         bool b_kc, float* C, int ldc, int M, int N, int K, const float* bias, int act, float alpha,
-                        bool accumulate, hipStream_t s, float* ws, size_t ws_floats) {
+                        bool accumulate, hipStream_t s, float* ws, size_t ws_floats, int force_cfg) {
   if (M <= 0 || N <= 0 || K <= 0) return;
   const bool mapped = ma.rows_per > 0;
-  if (N <= NBN && !b_kc && !A2 && M >= NBM && !mapped) {         // narrow output: 256 x 32 tiles
+  if (!a_kc && !mapped) require_m1_chunked(A2, M1, "launch_gemm_mapped");
+  if (mapped && b_kc) { fprintf(stderr, "rsrgan: launch_gemm_mapped: a row map of A with a k-contiguous B is not instantiated\n"); abort(); }
+  if (N <= NBN && !b_kc && !A2 && M >= NBM && !mapped && force_cfg < 0) {         // narrow output: 256 x 32 tiles
     const int gy = (M + NBM - 1) / NBM, nk = (K + BK - 1) / BK, ldw = (N + 3) & ~3;
     int splits = 1;
     if (ws && gy < 192 && nk >= 8) {
@@ -1080,6 +1100,7 @@ void launch_gemm_mapped(const float* A, int lda, const GemmRowMap& ma, const flo
     float* w = splits > 1 ? ws : nullptr;
     dim3 grid(1, gy, splits), block(256);
     const int acc = accumulate ? 1 : 0;
+    g_gemm_last_plan = GemmPlanRecord{GEMM_CLS_N32, NBM, NBN, 0, 0, 0, splits, 0};
     if (a_kc) hipLaunchKernelGGL((k_gemm_n32<true>), grid, block, 0, s, A, lda, B, ldb, C, ldc, M, N, K, bias, act, alpha, acc, w, ldw, per);
     else hipLaunchKernelGGL((k_gemm_n32<false>), grid, block, 0, s, A, lda, B, ldb, C, ldc, M, N, K, bias, act, alpha, acc, w, ldw, per);
     if (splits > 1) {
@@ -1092,7 +1113,7 @@ void launch_gemm_mapped(const float* A, int lda, const GemmRowMap& ma, const flo
   // k_gemm (stream-K, loader waves, LDS ring) for the window views and for the products with enough work per tile and enough
   // tiles; k_gemm16 for the rest (measured, tools/ubench/gemm_bench.hip; the two are within noise of each other in between)
   const double outs = (double)M * N;
-  if (!mapped && !(K >= 256 && outs >= 4.0e6) && !(K >= 2048 && outs >= 1.5e6)) {
+  if (force_cfg < 0 && !mapped && !(K >= 256 && outs >= 4.0e6) && !(K >= 2048 && outs >= 1.5e6)) {
     launch_gemm16(A, lda, a_kc ? nullptr : A2, lda2, M1, a_kc, B, ldb, b_kc, C, ldc, M, N, K, bias, act, alpha, accumulate, s, ws, ws_floats);
     return;
   }
@@ -1103,13 +1124,13 @@ void launch_gemm_mapped(const float* A, int lda, const GemmRowMap& ma, const flo
   g.ma = ma;
   if (mapped) {                 // the SEGAN-style convolutions: a window view times a [K][N] filter / gradient (b_kc never occurs)
     g.A2 = nullptr;
-    if (a_kc) launch_layout<true, false, true>(g, s, ws, ws_floats);
-    else launch_layout<false, false, true>(g, s, ws, ws_floats);
+    if (a_kc) launch_layout<true, false, true>(g, s, ws, ws_floats, force_cfg);
+    else launch_layout<false, false, true>(g, s, ws, ws_floats, force_cfg);
   }
-  else if (a_kc && !b_kc) launch_layout<true, false, false>(g, s, ws, ws_floats);
-  else if (a_kc && b_kc) launch_layout<true, true, false>(g, s, ws, ws_floats);
-  else if (!a_kc && !b_kc) launch_layout<false, false, false>(g, s, ws, ws_floats);
-  else launch_layout<false, true, false>(g, s, ws, ws_floats);
+  else if (a_kc && !b_kc) launch_layout<true, false, false>(g, s, ws, ws_floats, force_cfg);
+  else if (a_kc && b_kc) launch_layout<true, true, false>(g, s, ws, ws_floats, force_cfg);
+  else if (!a_kc && !b_kc) launch_layout<false, false, false>(g, s, ws, ws_floats, force_cfg);
+  else launch_layout<false, true, false>(g, s, ws, ws_floats, force_cfg);
 }
 
 // nb same-shaped products C_b = [A_b | A2_b]^T-style (x-contiguous operands, no bias / activation) as ONE stream-K launch of k_gemm
@@ -1122,6 +1143,7 @@ bool launch_gemm_batch(int nb, const float* const* A, int lda, const float* cons
   if (!form || nb < 2 || nb > GEMM_MAXB || M <= 0 || N <= 0 || K <= 0 || !ws) return false;
   const double outs = (double)M * N;
   if (!(K >= 256 && outs >= 4.0e6) && !(K >= 2048 && outs >= 1.5e6)) return false;      // (k_gemm16's products: launch_gemm16_batch)
+  if (A2) for (int b = 0; b < nb; ++b) require_m1_chunked(A2[b], M1, "launch_gemm_batch");
   GemmArgs g{};
   g.A = A[0]; g.A2 = A2 ? A2[0] : nullptr; g.B = B[0]; g.bias = nullptr; g.C = C[0];
   g.lda = lda; g.lda2 = lda2; g.M1 = M1; g.ldb = ldb; g.ldc = ldc; g.M = M; g.N = N; g.K = K;

@@ -293,9 +293,19 @@ void launch_floor_chain(float* a, float* b, int n, int mode, hipStream_t s);
 // GEMM: inner = stride * channels, a row = kwidth * channels contiguous floats).  For a k-contiguous operand the mapped index is the
 // row (m or n); for an x-contiguous operand it is k.
 struct GemmRowMap { int rows_per; long long outer; long long inner; };
+// What the GEMM launch code of this host thread launched last: a few host stores per launch, read back by rsrgan_op_gemm_last_plan so a
+// unit test can assert WHICH kernel and work split computed its numbers.  W, n_dp, fixup, Ur: the stream-K plan (0 for the split-K
+// kernels); splits: the split-K factor (1 for the stream-K kernels).
+enum { GEMM_CLS_NONE = 0, GEMM_CLS_GEMM16 = 1, GEMM_CLS_N32 = 2, GEMM_CLS_KGEMM = 3, GEMM_CLS_KGEMM_S = 4, GEMM_CLS_GEMM16_B = 5,
+       GEMM_CLS_KGEMM_B = 6, GEMM_CLS_KGEMM_S_B = 7 };
+struct GemmPlanRecord { int cls, bm, bn, W, n_dp, fixup, splits, Ur; };
+extern thread_local GemmPlanRecord g_gemm_last_plan;
+// force_cfg >= 0 (unit tests only): tile form force_cfg of launch_layout's table (0..4 k_gemm 128x128, 96x128, 128x96, 256x64, 256x32;
+// 5..7 k_gemm_s 256x256, 128x256, 256x128), skipping the routing rule and the cost comparison.
+// A2 with an m-contiguous A: M1 % 4 == 0 (checked: a named abort).
 void launch_gemm_mapped(const float* A, int lda, const GemmRowMap& ma, const float* A2, int lda2, int M1, bool a_kc, const float* B, int ldb,
                         bool b_kc, float* C, int ldc, int M, int N, int K, const float* bias, int act, float alpha,
-                        bool accumulate, hipStream_t s, float* ws, size_t ws_floats);
+                        bool accumulate, hipStream_t s, float* ws, size_t ws_floats, int force_cfg = -1);
 // up to 4 products of one shape in one k_gemm16 launch (+ one reduce launch): C[p] (+)= [A[p] | A2[p]]^T . B[p], operands [K][M1 | M - M1], [K][N]
 constexpr int GEMM16_MAXB = 4;
 struct Gemm16Batch { const float* A[GEMM16_MAXB]; const float* A2[GEMM16_MAXB]; const float* B[GEMM16_MAXB]; float* C[GEMM16_MAXB]; int n; };

@@ -454,3 +454,50 @@ class HipEngine:
         check(self.lib.rsrgan_op_gemm(_ptr(A), A.stride(0), 1 if a_kc else 0, _ptr(B), B.stride(0), 1 if b_kc else 0,
                                       _ptr(C_), C_.stride(0), M, N, K, _ptr(bias), act, alpha, 1 if accumulate else 0,
                                       self._stream()))
+
+    # ---- test-only operator entries (include/rsrgan.h): the model's own host launch code on caller-supplied buffers ----
+    def op_gemm2(self, A, a_kc, B, b_kc, C_, M, N, K, A2=None, M1=0, lda=None, lda2=None, bias=None, act=0, alpha=0.3,
+                 accumulate=False, row_map=None, workers=0, force_cfg=-1):
+        """row_map = (rows_per, outer, inner) in floats: a window view of A (then lda is unused)"""
+        rp, outer, inner = row_map if row_map else (0, 0, 0)
+        check(self.lib.rsrgan_op_gemm2(_ptr(A), A.stride(0) if lda is None else lda, 1 if a_kc else 0, _ptr(A2),
+                                       0 if A2 is None else (A2.stride(0) if lda2 is None else lda2), M1, _ptr(B), B.stride(0),
+                                       1 if b_kc else 0, _ptr(C_), C_.stride(0), M, N, K, _ptr(bias), act, alpha,
+                                       1 if accumulate else 0, rp, outer, inner, workers, force_cfg, self._stream()))
+
+    @staticmethod
+    def _table(ts):
+        from ._lib import ptr_table
+        return None if ts is None else ptr_table([None if t is None else t.data_ptr() for t in ts])
+
+    def op_gemm_batch(self, As, A2s, Bs, Cs, M, N, K, M1=0, accumulate=False, workers=0) -> bool:
+        """True: launched; False: not applicable (nothing ran, the caller launches the products one by one)"""
+        rc = self.lib.rsrgan_op_gemm_batch(len(As), self._table(As), As[0].stride(0), self._table(A2s),
+                                           A2s[0].stride(0) if A2s else 0, M1, self._table(Bs), Bs[0].stride(0), self._table(Cs),
+                                           Cs[0].stride(0), M, N, K, 1 if accumulate else 0, workers, self._stream())
+        if rc == 1:
+            return False
+        check(rc)
+        return True
+
+    def op_gemm16_batch(self, As, A2s, Bs, Cs, M, N, K, M1=0, accumulate=False):
+        check(self.lib.rsrgan_op_gemm16_batch(len(As), self._table(As), As[0].stride(0), self._table(A2s),
+                                              A2s[0].stride(0) if A2s else 0, M1, self._table(Bs), Bs[0].stride(0), self._table(Cs),
+                                              Cs[0].stride(0), M, N, K, 1 if accumulate else 0, self._stream()))
+
+    def op_gemm_last_plan(self) -> dict:
+        from ._lib import GEMM_CLASSES, GEMM_PLAN_FIELDS
+        out = (C.c_int32 * 8)()
+        check(self.lib.rsrgan_op_gemm_last_plan(out))
+        d = dict(zip(GEMM_PLAN_FIELDS, list(out)))
+        d["cls"] = GEMM_CLASSES[d["cls"]]
+        return d
+
+    def op_lstm_colsums(self, dz, cprev, ccur, db, dwi, dwf, dwo, rows, H):
+        """lists of nb tensors each: dz [rows][4H], cprev / ccur [rows][H], db [>= 4H], dwi / dwf / dwo [>= H]"""
+        check(self.lib.rsrgan_op_lstm_colsums(len(dz), self._table(dz), self._table(cprev), self._table(ccur), self._table(db),
+                                              self._table(dwi), self._table(dwf), self._table(dwo), rows, H, self._stream()))
+
+    def op_colsum(self, a, out, rows, cols, b=None, tall=False):
+        check(self.lib.rsrgan_op_colsum(_ptr(a), a.stride(0), _ptr(b), 0 if b is None else b.stride(0), _ptr(out), rows, cols,
+                                        1 if tall else 0, self._stream()))

@@ -16,10 +16,14 @@ def pad4(n):
     return (n + 3) // 4 * 4
 
 
+# Which kernel each shape reaches (the routing of launch_gemm_mapped: the stream-K kernels need K >= 256 and M*N >= 4e6, or K >= 2048
+# and M*N >= 1.5e6): (1600, 3040, 280) runs on k_gemm (96 x 128 whole tiles, no fix-up); the four shapes with N <= 32 and M >= 256 on
+# k_gemm_n32 (b_kcontig: k_gemm16); the other eight -- (8200, 2050, 72) and (4100, 4100, 40) among them: K < 256 -- on k_gemm16.
+# k_gemm_s, k_gemm_fixup, the other tile forms, the batches and the row maps: tests/test_gpu_wgrad_ops.py.
 @pytest.mark.parametrize("M,N,K", [(128, 128, 16), (300, 257, 40), (1600, 3040, 280), (37, 1, 40), (560, 3040, 640),
                                    (257, 280, 1003), (5, 7, 3),
-                                   (1000, 12, 143), (512, 32, 2464), (2500, 24, 20000), (256, 1, 77),       # N <= 32: 256x32 tiles
-                                   (8200, 2050, 72), (4100, 4100, 40)])      # >= 512 big tiles: k_gemm_s (128 x 256 / 256 x 256, four self-loading waves)
+                                   (1000, 12, 143), (512, 32, 2464), (2500, 24, 20000), (256, 1, 77),       # N <= 32: k_gemm_n32 (256 x 32 tiles)
+                                   (8200, 2050, 72), (4100, 4100, 40)])      # large outputs with a short K: k_gemm16
 @pytest.mark.parametrize("akc,bkc", [(True, False), (True, True), (False, False), (False, True)])
 def test_gemm_variants(M, N, K, akc, bkc):
     eng = _eng()
