@@ -357,15 +357,8 @@ __global__ __launch_bounds__(512, 1) void k_dlstm_fwd(const DPersistArgs a) {
   // every wave reads the generation itself: it only changes when ALL workgroups have passed their epilogue
   const unsigned gen = __hip_atomic_load(ctl + DP_CTL_GEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   dp_fwd_body(a, gen);
-  if (threadIdx.x == 0) {                                          // (thread 0 leaves the body on every path, failures included)
-    const unsigned old = __hip_atomic_fetch_add(ctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == gridDim.x - 1) {
-      if (__hip_atomic_load(ctl + DP_CTL_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
-        a.L[a.nl - 1].out[0] = __builtin_nanf("");                 // (the other workgroups have finished: nobody overwrites it)
-      __hip_atomic_store(ctl + DP_CTL_DONE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(ctl + DP_CTL_GEN, gen + 1u == 0u ? 1u : gen + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  // (thread 0 leaves the body on every path, failures included; the other workgroups have finished: nobody overwrites the poisoned word)
+  if (threadIdx.x == 0) persist_last_out(ctl, gen, [] { return gridDim.x; }, [&] { return a.L[a.nl - 1].out; }, 0u, [] {});
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -915,15 +908,7 @@ __global__ __launch_bounds__(512, 1) void k_dlstm_bwd(const DPersistArgs a) {
       }
     }
   }
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add(ctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == gridDim.x - 1) {
-      if (__hip_atomic_load(ctl + DP_CTL_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
-        a.L[0].gates[0] = __builtin_nanf("");                      // poisons layer 0's kernel gradient, hence the clipped update
-      __hip_atomic_store(ctl + DP_CTL_DONE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(ctl + DP_CTL_GEN, gen + 1u == 0u ? 1u : gen + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  if (threadIdx.x == 0) persist_last_out(ctl, gen, [] { return gridDim.x; }, [&] { return a.L[0].gates; }, 0u, [] {});      // (poisons layer 0's kernel gradient, hence the clipped update)
 }
 
 
@@ -978,14 +963,7 @@ __global__ __launch_bounds__(768, 3) void k_dlstm_fwd_t(const DPersistArgs a) {
   if (threadIdx.x == 0) S.dead = 0;
   __syncthreads();
   dp_fwdt_body<false>(a, gen, S, (int)blockIdx.x, false);
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add(ctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == gridDim.x - 1) {
-      if (__hip_atomic_load(ctl + DP_CTL_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) a.L[a.nl - 1].out[0] = __builtin_nanf("");
-      __hip_atomic_store(ctl + DP_CTL_DONE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(ctl + DP_CTL_GEN, gen + 1u == 0u ? 1u : gen + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  if (threadIdx.x == 0) persist_last_out(ctl, gen, [] { return gridDim.x; }, [&] { return a.L[a.nl - 1].out; }, 0u, [] {});
 }
 void launch_dlstm_fwd_t(const DPersistArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_dlstm_fwd_t, dim3(a.nl * (a.N / 32) * DP_NQ), dim3(768), 0, s, a);

@@ -25,6 +25,25 @@ __device__ __forceinline__ float dp_tanh(float x) {
   return fabsf(x) < 0.1f ? ser : big;
 }
 
+// The "last workgroup out" epilogue of every persistent launch: thread 0 of a workgroup calls it behind the body (the caller places
+// the barrier its body needs in front).  It counts the workgroup in at DP_CTL_DONE; the last of the nwg() to arrive -- every other one
+// has finished -- lets move_on() advance what the launch carries over to the next one (the generator's ring counters), writes a NaN to
+// the word poison() points to if a bounded wait expired (DP_CTL_ERR), clears DONE and moves the generation on.  0 is never a
+// generation: it starts again at 1 behind wrap - 1 (the generator's control block), or behind 2^32 - 1 (wrap = 0: the discriminator's).
+// (nwg and poison are callables so that each is evaluated where it is used, the count behind the DONE add, the address on the error path
+// only: as values they are loaded in front of the add, and that alone shifts the register allocation of the whole body in front.)
+template <class N, class P, class F>
+__device__ __forceinline__ void persist_last_out(gu32* ctl, unsigned gen, N&& nwg, P&& poison, unsigned wrap, F&& move_on) {
+  const unsigned old = __hip_atomic_fetch_add(ctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (old == nwg() - 1u) {
+    move_on();
+    if (__hip_atomic_load(ctl + DP_CTL_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) *poison() = __builtin_nanf("");
+    __hip_atomic_store(ctl + DP_CTL_DONE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned g1 = gen + 1u;
+    __hip_atomic_store(ctl + DP_CTL_GEN, (wrap ? g1 >= wrap : g1 == 0u) ? 1u : g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // 16-byte write-through accesses carrying two granules each (8-byte scalar sc1 stores are one fabric write per lane: 2.7x the time
 // per byte, MI355X_MICROARCH.md "stores of each flavour"; the 8-byte halves of a 16-byte sc1 access are observed untorn).  Inline
 // asm: the compiler has no 16-byte agent-scope atomic.  (Its vmcnt bookkeeping does not see these: the loads wait inside the asm,

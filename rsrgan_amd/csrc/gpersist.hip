@@ -45,24 +45,12 @@ constexpr int GP_NKB = 18;               // k-blocks of 16 of the recurrent / in
 constexpr int GP_KBW = 5;                // k-blocks per R / X wave (k-block jb belongs to wave jb & 3)
 constexpr int GP_SLOT = 1024;            // bytes per chunk slot: a 16 x 16 tile of floats, 16 bytes (four columns of one row) per fragment lane
 constexpr unsigned GP_SENT = 0xFFFFFFFFu; // a word of a slot nobody has written yet
-#ifndef GP_R1_STEPS
-#define GP_R1_STEPS 3
-#endif
-constexpr int GP_R1 = GP_R1_STEPS;                 // steps in the hop-1 ring: a slot is summed in step t, re-armed at the end of step t + 1, written again in step t + 3
+constexpr int GP_R1 = 3;                 // steps in the hop-1 ring: a slot is summed in step t, re-armed at the end of step t + 1, written again in step t + 3
 constexpr int GP_NCH = GP_NKB * GP_NR;   // chunk slots per layer and step (the layout's stride; a layer uses its first nkb * NR)
 constexpr unsigned GP_SC1 = 16u;         // aux of the raw-buffer builtins: sc1 (agent scope: write-through store / L1-bypassing load)
 constexpr unsigned GP_VOL = 1u << 31;    // ... compiler-only: volatile (a polled load must not be hoisted out of its loop)
-#ifndef GP_GATE_NUM                      // progressive sweeps start reading when GP_GATE_NUM / GP_GATE_DEN of the awaited sentinel pieces are there
-#define GP_GATE_NUM 1
-#define GP_GATE_DEN 2
-#endif
-#ifndef GP_HB10                          // pieces per round trip of a progressive pass (hop 1: 10 per lane, hop 2: 9)
-#define GP_HB10 10
-#define GP_HB9 9
-#endif
 
 #ifdef GP_TRACE
-__device__ unsigned g_gp_cnt[8];          // (GP_COUNT builds only: the atomics distort the timeline)          // [0] cached first reads, [1] of them with a stale / missing tag; [2], [3] the same for write-through first reads
 __device__ unsigned g_gp_trace[256][24][24];
 #define GPT_DECL __shared__ unsigned gp_tr[24][24];
 #define GPT(i) do { if ((w & 3) == 0 && lane == 0 && t < 24) gp_tr[t][i] = (unsigned)__builtin_amdgcn_s_memtime(); } while (0)
@@ -98,18 +86,9 @@ __device__ __forceinline__ float gp_tanh(float x) {          // (dpersist.hip dp
 }
 
 // The stash (gate activations, c, h, dz: written once per launch, read by the NEXT launch at the earliest) streams through the
-// memory system beside the hand-off rings, which want to stay in the Infinity Cache.  GP_STASH_NT = 1: non-temporal stores / loads
-// for it (measured: profiles/r5_hbm_phases.txt).
-#ifndef GP_STASH_NT
-#define GP_STASH_NT 0
-#endif
-__device__ __forceinline__ void gp_stash_store(float* dst, const float4& v) {
-#if GP_STASH_NT
-  __builtin_nontemporal_store(v.x, dst); __builtin_nontemporal_store(v.y, dst + 1); __builtin_nontemporal_store(v.z, dst + 2); __builtin_nontemporal_store(v.w, dst + 3);
-#else
-  *reinterpret_cast<float4*>(dst) = v;
-#endif
-}
+// memory system beside the hand-off rings, which want to stay in the Infinity Cache.  Plain stores: non-temporal ones for it were
+// measured and did not pay (profiles/r5_hbm_phases.txt).
+__device__ __forceinline__ void gp_stash_store(float* dst, const float4& v) { *reinterpret_cast<float4*>(dst) = v; }
 
 // ---- intra-workgroup synchronisation: monotonic LDS counters ----
 __device__ __forceinline__ void gp_signal(unsigned* cnt, int lane) {
@@ -176,9 +155,6 @@ constexpr int GP_CTL_C1 = 4, GP_CTL_C3 = 5;      // control-block words: steps w
 // Re-arm the NP producers' 512-byte half chunks at base + p * GP_SLOT (p = 0 .. NP-1): one store covers two producers (a half
 // wave each); wave w of the four R waves takes every fourth store.
 __device__ __forceinline__ void gp_rearm(const GpBuf& b, unsigned base, int NP, int w, int lane) {
-#ifdef GP_NOREARM                   // (harness experiment: rings as deep as the launch is long, armed by a memset in front of every launch)
-  return;
-#endif
   const u32x4 sent = {GP_SENT, GP_SENT, GP_SENT, GP_SENT};
   for (int k = w; 2 * k < NP; k += 4) {
     const int p = 2 * k + (lane >> 5);
@@ -197,6 +173,9 @@ __device__ __forceinline__ void gp_rearm(const GpBuf& b, unsigned base, int NP, 
 // L2s are invalidated at the kernel boundary behind the memset), i.e. it is detected like a store that has not landed, and the retry
 // reads past the caches (sc1).
 // false on time-out / peer failure.
+// (A hand-off costs two round trips after its last piece has landed: the poll that notices it, then the full read.  A PROGRESSIVE form
+// -- read what is there, ask again for the missing pieces only -- saved the second trip and still lost to the extra passes' traffic:
+// profiles/r5_gpersist_progressive_sweep_negative.txt)
 template <int NL, bool POLL_FIRST, int BATCH, bool CACHED, bool TAGGED = false, class F>
 __device__ __forceinline__ bool gp_sweep(const GpBuf& b, const unsigned (&lo)[NL], int nl, unsigned lane_off, unsigned so, bool son,
                                          gu32* err, F&& consume, unsigned tag = 0u) {
@@ -232,15 +211,8 @@ __device__ __forceinline__ bool gp_sweep(const GpBuf& b, const unsigned (&lo)[NL
   };
   bool read_now = !POLL_FIRST, first = true;
   for (unsigned spins = 0;; ++spins) {
-#ifdef GP_ABL
-    if (read_now && POLL_FIRST && ((GP_ABL >> (CACHED ? 2 : 1)) & 1)) return true;      // timing ablation: the sentinels only
-    if (!POLL_FIRST && (GP_ABL & 1)) return true;                                        // timing ablation: no x sweeps
-#endif
     if (read_now) {
       const bool ok = (CACHED && first) ? read_all(std::true_type{}) : read_all(std::false_type{});
-#ifdef GP_COUNT
-      if (first && (threadIdx.x & 63) == 0) { atomicAdd(&g_gp_cnt[CACHED ? 0 : 2], 1u); if (!ok) atomicAdd(&g_gp_cnt[CACHED ? 1 : 3], 1u); }
-#endif
       first = false;
       if (ok) return true;
       asm volatile("" ::: "memory");
@@ -260,68 +232,6 @@ __device__ __forceinline__ bool gp_sweep(const GpBuf& b, const unsigned (&lo)[NL
   }
 }
 
-// The PROGRESSIVE form of a sweep (round 5).  gp_sweep above costs a hand-off two round trips after the last piece has landed -- the
-// poll that notices it, then the full read (10 pieces per lane: ~4.5 k cycles of the forward period for hop 1, ~2.5 k for hop 2,
-// profiles/r4_gpersist_trace.txt "sentinels only") -- although most of the pieces arrived long before the last one (the producers
-// finish 7-9 k cycles apart).  Here the data is its own flag all the way: once `gate` of the awaited sentinel pieces are there (cheap
-// polling until then: a lane per producer, as before -- a wave that arrives early must not spin on full reads, that is what
-// saturated the fabric in the first version), every pass reads the pieces that are still PENDING, keeps the ones that came back
-// valid in registers, and asks again for the rest only: a finished piece's load is sent to an out-of-range offset (a raw-buffer load
-// beyond num_records returns zeros without a memory access).  What is left behind the last arrival is one round trip of the one or
-// two pieces that were missing.  out[] is complete and in slot order when the function returns, so the caller's sum keeps its fixed
-// order whatever the arrival order was.  nlw: wave-uniform number of pieces (>= every lane's nl).
-template <int NL, int HB>
-__device__ __forceinline__ bool gp_sweep_prog(const GpBuf& b, const unsigned (&lo)[NL], int nl, int nlw, unsigned lane_off, unsigned so, bool son,
-                                              int gate, gu32* err, f32x4 (&out)[NL]) {
-  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-  constexpr unsigned OOB = 0xFFFFFF00u;
-  unsigned of[NL];
-#pragma unroll
-  for (int k = 0; k < NL; ++k) of[k] = (unsigned)__builtin_amdgcn_readfirstlane((int)lo[k]);
-  if (gate > 0) {
-    for (unsigned polls = 0;; ++polls) {
-      const u32x4 y = __builtin_amdgcn_raw_buffer_load_b128(b.rs, so, 0, GP_SC1 | GP_VOL);
-      if (__popcll(__ballot(son && gp_valid(y))) >= gate) break;
-      asm volatile("" ::: "memory");
-      if ((polls & 63) == 63) {
-        if (__builtin_amdgcn_s_memrealtime() - t0 > 100000000ull || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-  }
-  unsigned pend = (unsigned)__builtin_amdgcn_readfirstlane((int)((1u << nlw) - 1u));
-  for (unsigned pass = 0;; ++pass) {
-#pragma unroll
-    for (int k0 = 0; k0 < NL; k0 += HB) {
-      if (((pend >> k0) & ((1u << HB) - 1u)) == 0u) continue;                       // (uniform)
-      u32x4 t[HB];
-#pragma unroll
-      for (int j = 0; j < HB; ++j) {
-        const int k = k0 + j < NL ? k0 + j : NL - 1;
-        const bool want = k0 + j < NL && ((pend >> k) & 1u) && k < nl;
-        t[j] = __builtin_amdgcn_raw_buffer_load_b128(b.rs, want ? of[k] + lane_off : OOB, 0, GP_SC1 | GP_VOL);   // (unconditional)
-      }
-#pragma unroll
-      for (int j = 0; j < HB; ++j) {
-        const int k = k0 + j;
-        if (k < NL) {
-          const bool ok = __all(k >= nl || gp_valid(t[j]));
-          if (((pend >> k) & 1u) && ok) {                                              // (uniform)
-            out[k] = f32x4{__uint_as_float(t[j][0]), __uint_as_float(t[j][1]), __uint_as_float(t[j][2]), __uint_as_float(t[j][3])};
-            pend &= ~(1u << k);
-          }
-        }
-      }
-    }
-    if (pend == 0u) return true;
-    asm volatile("" ::: "memory");
-    if ((pass & 31) == 31) {
-      if (__builtin_amdgcn_s_memrealtime() - t0 > 100000000ull || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
-}
-
 // LDS of a workgroup (NT = 5: 129 KB)
 template <int NT>
 struct GpLds {
@@ -338,7 +248,6 @@ struct GpLds {
   float pb[4][NT][GP_NR][64][4];            // accumulator tiles: x-part (X wave w -> R wave w), then the R waves' partial sums
 };
 
-// PROG: bit 0 the reducers' hop-1 sweeps, bit 1 the gathers of hop 2 in the progressive form (gp_sweep_prog); RSRGAN_GP_PROG
 // RES: a residual stack (models/res_lstm_l.py:101-194): layer l + 1 reads s_l = out_l + s_{l-1} instead of out_l (s_{-1} = the stack's
 // input).  The reducer of a half chunk is also the owner of that half chunk of the running sum: it adds its masked m(t) to the half
 // chunk of s_{l-1}(t) (layer 0: the input rows in memory; above: what the same-numbered reducer of the layer below published a step
@@ -349,9 +258,8 @@ struct GpLds {
 // RESX (with RES; models/res_lstm_i.py:101-190): the residual is the stack's input at EVERY layer, never a running sum -- layer l + 1 reads
 // out_l + x, the output FC out_{L-1} + x.  The reducer adds its masked m(t) to its half chunk of x(t), read from the stack's input rows in
 // memory as RES does for layer 0; nothing is polled from the layer below.  res_out and the second region of gran2 as under RES.
-template <int NT, int PROG, bool RES, bool TAG, bool CARRY = false, bool RESX = false>
+template <int NT, bool RES, bool TAG, bool CARRY = false, bool RESX = false>
 __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S, const unsigned c1, const unsigned bid) {
-  static_assert(!(TAG && PROG), "the progressive sweeps know the sentinel form only");
   static_assert(RES || !RESX, "RESX is a form of RES");
   constexpr int NR = GP_NR, NU = NT * NR, CW = 4 * NT;
   GPT_DECL
@@ -541,9 +449,6 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
           const float4 v = *reinterpret_cast<const float4*>(&S.st[k][row][4 * cq]);
           const size_t rowg = (size_t)t * N + row0 + row;
           float* dst = (k < 4 ? L.gates + rowg * H4 + k * H : k == 4 ? L.c + (rowg + N) * H : L.h + rowg * L.ldH) + cell0 + 4 * cq;
-#ifdef GP_ABL2
-          if (GP_ABL2 & 2) continue;                                     // timing ablation: no stash stores
-#endif
           if (e < 6 * 16 * NT && cell0 + 4 * cq < H) gp_stash_store(dst, v);
         }
         gp_signal(&S.cnt_s[r], lane);
@@ -628,9 +533,6 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
         __builtin_amdgcn_s_setprio(1);                                 // (below the R waves' and the projection's bursts, above every spin loop)
 #pragma unroll
         for (int jj = 0; jj < GP_KBW; ++jj) {
-#ifdef GP_ABL2
-          if (GP_ABL2 & 1) continue;                                   // timing ablation: no x-part products
-#endif
           if (xw + 4 * jj < nkbx) {
             const float b0 = live ? xv[jj][0] : 0.f, b1 = live ? xv[jj][1] : 0.f, b2_ = live ? xv[jj][2] : 0.f, b3 = live ? xv[jj][3] : 0.f;
             float4 ka[NT];
@@ -714,9 +616,6 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
         for (int ks = 0; ks < NT; ++ks)
 #pragma unroll
           for (int j = 0; j < 3; ++j) {
-#ifdef GP_ABL2
-            if (GP_ABL2 & 4) continue;                                 // timing ablation: no projection products
-#endif
             pm[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wpw[(2 * (n0 + j) * NT + ks) * 64], hv[ks], pm[j], 0, 0, 0);
           }
 #pragma unroll
@@ -734,13 +633,7 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
 #pragma unroll
       for (int k = 0; k < 10; ++k) lo[k] = slot1(par1, r, jbr, min(pp0 + 2 * k, NC - 1)) + (unsigned)hh * 512u;
       f32x4 sa = {0.f, 0.f, 0.f, 0.f};
-      if (PROG & 1) {
-        f32x4 pv[10];
-        if (!gp_sweep_prog<10, GP_HB10>(b1, lo, nlr, (pn + 1) >> 1, pair_off, slot1(par1, r, jbr, min(pp0 + lane, NC - 1)) + (unsigned)hh * 512u + 496u, lane < pn,
-                                  (pn * GP_GATE_NUM) / GP_GATE_DEN, err, pv)) { fail(); return; }
-#pragma unroll
-        for (int k = 0; k < 10; ++k) { if (k == 0) sa = k < nlr ? pv[0] : f32x4{0.f, 0.f, 0.f, 0.f}; else if (k < nlr) sa += pv[k]; }      // (slot order: the same bits as the other form)
-      } else if (!gp_sweep<10, true, 10, false, TAG>(b1, lo, nlr, pair_off, slot1(par1, r, jbr, min(pp0 + lane, NC - 1)) + (unsigned)hh * 512u + 496u, lane < pn, err,
+      if (!gp_sweep<10, true, 10, false, TAG>(b1, lo, nlr, pair_off, slot1(par1, r, jbr, min(pp0 + lane, NC - 1)) + (unsigned)hh * 512u + 496u, lane < pn, err,
                                   [&](int k, const f32x4& v) { if (k == 0) sa = k < nlr ? v : f32x4{0.f, 0.f, 0.f, 0.f}; else if (k < nlr) sa += v; }, tag1)) { fail(); return; }
       GPT(15);
       *reinterpret_cast<f32x4*>(&S.gs[par][r][gp][lane][0]) = sa;
@@ -763,10 +656,7 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
 #pragma unroll
       for (int n = 0; n < 9; ++n) lo[n] = slot2(t, r, min(gp + 2 * n, nkb - 1));
       f32x4 mv[9];
-      if (PROG & 2) {
-        if (!gp_sweep_prog<9, GP_HB9>(b2, lo, nvg, nvg, frag_off, slot2(t, r, min(gp + 2 * (lane >> 1), nkb - 1)) + (unsigned)(lane & 1) * 512u + 496u,
-                                 lane < 2 * nvg, (2 * nvg * GP_GATE_NUM) / GP_GATE_DEN, err, mv)) { fail(); return; }
-      } else if (!gp_sweep<9, true, 9, true>(b2, lo, nvg, frag_off, slot2(t, r, min(gp + 2 * (lane >> 1), nkb - 1)) + (unsigned)(lane & 1) * 512u + 496u,
+      if (!gp_sweep<9, true, 9, true>(b2, lo, nvg, frag_off, slot2(t, r, min(gp + 2 * (lane >> 1), nkb - 1)) + (unsigned)(lane & 1) * 512u + 496u,
                                  lane < 2 * nvg, err, [&](int k, const f32x4& v) { mv[k] = v; })) { fail(); return; }
       GPT(17);
       const bool live = t < S.len[16 * r + lr];
@@ -819,48 +709,20 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
 #endif
 }
 
-template <int NT, int PROG, bool RES, bool TAG, bool CARRY = false>
+constexpr unsigned GP_GEN_WRAP = 1u << 21;      // the generator's control block: generation 2^21 - 1 is followed by 1
+template <int NT, bool RES, bool TAG, bool CARRY = false, bool RESX = false>
 __global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_fwd(const GPersistArgs a) {
   __shared__ __attribute__((aligned(16))) GpLds<NT> S;
   gu32* ctl = (gu32*)a.ctl;
   const unsigned gen = __hip_atomic_load(ctl + DP_CTL_GEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (counts launches; nothing depends on it)
   // (TAG) steps written to the hop-1 ring by the launches so far, mod 2 GP_R1: every workgroup reads it here, the last one to finish moves it on
   const unsigned c1 = TAG ? __hip_atomic_load(ctl + GP_CTL_C1 + GP_CIDX(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-  gp_fwd_body<NT, PROG, RES, TAG, CARRY>(a, S, c1, blockIdx.x);
+  gp_fwd_body<NT, RES, TAG, CARRY, RESX>(a, S, c1, blockIdx.x);
   __syncthreads();                                                 // (every wave leaves the body on every path)
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add(ctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == gridDim.x - 1) {
+  if (threadIdx.x == 0)
+    persist_last_out(ctl, gen, [&] { return gridDim.x; }, [&] { return a.L[a.nl - 1].out; }, GP_GEN_WRAP, [&] {
       if (TAG) __hip_atomic_store(ctl + GP_CTL_C1 + GP_CIDX(a), (c1 + (unsigned)a.T) % (2u * GP_R1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__hip_atomic_load(ctl + DP_CTL_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
-        a.L[a.nl - 1].out[0] = __builtin_nanf("");
-      __hip_atomic_store(ctl + DP_CTL_DONE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned g1 = gen + 1u;
-      __hip_atomic_store(ctl + DP_CTL_GEN, g1 >= (1u << 21) ? 1u : g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-// res_lstm_i's forward stack (gp_fwd_body RESX): a kernel of its own, so that every instantiation of k_glstm_fwd stays what it was
-template <int NT, int PROG, bool TAG, bool CARRY>
-__global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_fwd_ri(const GPersistArgs a) {
-  __shared__ __attribute__((aligned(16))) GpLds<NT> S;
-  gu32* ctl = (gu32*)a.ctl;
-  const unsigned gen = __hip_atomic_load(ctl + DP_CTL_GEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (counts launches; nothing depends on it)
-  // (TAG) steps written to the hop-1 ring by the launches so far, mod 2 GP_R1: every workgroup reads it here, the last one to finish moves it on
-  const unsigned c1 = TAG ? __hip_atomic_load(ctl + GP_CTL_C1 + GP_CIDX(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-  gp_fwd_body<NT, PROG, true, TAG, CARRY, true>(a, S, c1, blockIdx.x);
-  __syncthreads();                                                 // (every wave leaves the body on every path)
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add(ctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == gridDim.x - 1) {
-      if (TAG) __hip_atomic_store(ctl + GP_CTL_C1 + GP_CIDX(a), (c1 + (unsigned)a.T) % (2u * GP_R1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__hip_atomic_load(ctl + DP_CTL_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
-        a.L[a.nl - 1].out[0] = __builtin_nanf("");
-      __hip_atomic_store(ctl + DP_CTL_DONE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned g1 = gen + 1u;
-      __hip_atomic_store(ctl + DP_CTL_GEN, g1 >= (1u << 21) ? 1u : g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+    });
 }
 
 // =====================================================================================================================================
@@ -1021,38 +883,21 @@ __global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_fwd_dt(const GPersis
     __syncthreads();
     if (dbid < nD) { if (d.nrt == 1) dp_fwdt_body<true>(d, dgen, S.d, dbid, true); else dp_fwdt_body<false>(d, dgen, S.d, dbid, true); }
     else gp_fcf_body(a, d, dgen, S.f, dbid - nD, RES);
-    if (threadIdx.x == 0) {
-      const unsigned old = __hip_atomic_fetch_add(dctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (old == (unsigned)nReal - 1u) {
-        if (__hip_atomic_load(dctl + DP_CTL_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) d.L[d.nl - 1].out[0] = __builtin_nanf("");
-        __hip_atomic_store(dctl + DP_CTL_DONE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(dctl + DP_CTL_GEN, dgen + 1u == 0u ? 1u : dgen + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
+    if (threadIdx.x == 0) persist_last_out(dctl, dgen, [&] { return (unsigned)nReal; }, [&] { return d.L[d.nl - 1].out; }, 0u, [] {});
     return;
   }
   gu32* ctl = (gu32*)a.ctl;
   const unsigned gen = __hip_atomic_load(ctl + DP_CTL_GEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const unsigned c1 = TAG ? __hip_atomic_load(ctl + GP_CTL_C1 + GP_CIDX(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-  gp_fwd_body<NT, 0, RES, TAG>(a, S.g, c1, blockIdx.x - (unsigned)dt_pad);
+  gp_fwd_body<NT, RES, TAG>(a, S.g, c1, blockIdx.x - (unsigned)dt_pad);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add(ctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == gridDim.x - (unsigned)dt_pad - 1u) {
+  if (threadIdx.x == 0)
+    persist_last_out(ctl, gen, [&] { return gridDim.x - (unsigned)dt_pad; }, [&] { return a.L[a.nl - 1].out; }, GP_GEN_WRAP, [&] {
       if (TAG) __hip_atomic_store(ctl + GP_CTL_C1 + GP_CIDX(a), (c1 + (unsigned)a.T) % (2u * GP_R1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__hip_atomic_load(ctl + DP_CTL_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
-        a.L[a.nl - 1].out[0] = __builtin_nanf("");
-      __hip_atomic_store(ctl + DP_CTL_DONE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned g1 = gen + 1u;
-      __hip_atomic_store(ctl + DP_CTL_GEN, g1 >= (1u << 21) ? 1u : g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+    });
 }
 
-#ifndef GP_XR_STEPS
-#define GP_XR_STEPS 6
-#endif
-constexpr int GP_XR = GP_XR_STEPS;   // (a slot is re-armed, acknowledged, two steps after it was summed: four steps of slack)
+constexpr int GP_XR = 6;   // (a slot is re-armed, acknowledged, two steps after it was summed: four steps of slack)
 
 template <int NT>
 struct GpLdsB {
@@ -1085,9 +930,7 @@ __device__ __forceinline__ bool gp_poll(const GpBuf& b, unsigned so, bool son, g
   }
 }
 
-#ifndef GP_RES_NB
-#define GP_RES_NB 10
-#endif
+constexpr int GP_RES_NB = 10;        // loads in flight of the residual stack's sum on the reducer's path (gp_bwd_body)
 // One wave sums the half chunks of ALL NC producers at base + p * GP_SLOT (off the critical path: a plain loop, four loads in flight --
 // the unrolled gp_sweep over 20 pieces cost the backward kernel 8 spilled registers): even producers in lanes 0..31, odd ones in
 // 32..63, then the two halves (even first); every lane ends with the total of its (lane & 31) piece.  false: time-out / peer failure.
@@ -1141,9 +984,8 @@ __device__ __forceinline__ bool gp_sum_all(const GpBuf& b, unsigned base, int NC
 // chunk of D: its second G wave sums ALL input-gradient partials of the layer above (alone: the sum is needed on its own), adds the
 // D_{l+1}(t) piece the same-numbered reducer above published a step ago, hands D_l(t) into the state-gradient sum and publishes it
 // for the layer below in the second region of gran2 (one slot per step, behind the hand-offs).
-template <int NT, int PROG, bool RES, bool TAG>
+template <int NT, bool RES, bool TAG>
 __device__ __forceinline__ void gp_bwd_body(const GPersistArgs& a, GpLdsB<NT>& S, const unsigned c1, const unsigned c3, const unsigned bid) {
-  static_assert(!(TAG && PROG), "the progressive sweeps know the sentinel form only");
   constexpr int NR = GP_NR, CW = 4 * NT;
   GPT_DECL
   const int tid = threadIdx.x, lane = tid & 63, lr = lane & 15, q = lane >> 4;
@@ -1271,9 +1113,6 @@ __device__ __forceinline__ void gp_bwd_body(const GPersistArgs& a, GpLdsB<NT>& S
         for (int j = 0; j < 3; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
-#ifdef GP_ABL2
-          if ((GP_ABL2 & 8) && isx) continue;                           // timing ablation: no input-gradient products (zeros are published)
-#endif
           const float4 b = *reinterpret_cast<const float4*>(dzr + (r * NT + i) * 256);
           float4 ka[3];
 #pragma unroll
@@ -1319,9 +1158,6 @@ __device__ __forceinline__ void gp_bwd_body(const GPersistArgs& a, GpLdsB<NT>& S
         return *reinterpret_cast<const float4*>((k < 4 ? L.gates + rowg * H4 + k * H : L.c + rowg * H) + cell);
       };
       auto fetch = [&](int t, int r) {
-#ifdef GP_ABL2
-        if (GP_ABL2 & 32) { pv0 = pv1 = make_float4(0.3f, 0.3f, 0.3f, 0.3f); return; }      // timing ablation: no stash prefetch
-#endif
         int ln = lane;
         asm volatile("" : "+v"(ln));
         pv0 = fetch1(t, r, 0, ln);
@@ -1469,9 +1305,6 @@ __device__ __forceinline__ void gp_bwd_body(const GPersistArgs& a, GpLdsB<NT>& S
           const int cq = e % NT, pr = e / NT, row = 16 * r + (pr & 15), k = min(pr >> 4, 3);
           const float4 v = *reinterpret_cast<const float4*>(&S.st[k][row][4 * cq]);
           float* dst = L.gates + ((size_t)t * N + row0 + row) * H4 + k * H + cell0 + 4 * cq;
-#ifdef GP_ABL2
-          if (GP_ABL2 & 16) continue;                                    // timing ablation: no dz stores
-#endif
           if (e < 4 * 16 * NT && cell0 + 4 * cq < H) gp_stash_store(dst, v);
         }
         // This workgroup's G waves summed this step's partials before they gathered dm(t) (the wait at the top): re-arm their slots of
@@ -1589,13 +1422,7 @@ __device__ __forceinline__ void gp_bwd_body(const GPersistArgs& a, GpLdsB<NT>& S
 #pragma unroll
         for (int k = 0; k < 10; ++k) lo[k] = slot1(r1, r, jbr, min(pp0 + 2 * k, NC - 1)) + (unsigned)hh * 512u;
         f32x4 ua = {0.f, 0.f, 0.f, 0.f};
-        if (PROG & 1) {
-          f32x4 pv[10];
-          if (!gp_sweep_prog<10, GP_HB10>(b1, lo, nlr, (pn + 1) >> 1, pair_off, slot1((s + GP_R1 - 1) % GP_R1, r, jbr, min(pp0 + lane, NC - 1)) + (unsigned)hh * 512u + 496u, lane < pn,
-                                    (pn * GP_GATE_NUM) / GP_GATE_DEN, err, pv)) { fail(); return; }
-#pragma unroll
-          for (int k = 0; k < 10; ++k) { if (k == 0) ua = k < nlr ? pv[0] : f32x4{0.f, 0.f, 0.f, 0.f}; else if (k < nlr) ua += pv[k]; }
-        } else if (!gp_sweep<10, true, 10, false, TAG>(b1, lo, nlr, pair_off, slot1(r1, r, jbr, min(pp0 + lane, NC - 1)) + (unsigned)hh * 512u + 496u, lane < pn, err,
+        if (!gp_sweep<10, true, 10, false, TAG>(b1, lo, nlr, pair_off, slot1(r1, r, jbr, min(pp0 + lane, NC - 1)) + (unsigned)hh * 512u + 496u, lane < pn, err,
                                     [&](int k, const f32x4& v) { if (k == 0) ua = k < nlr ? v : f32x4{0.f, 0.f, 0.f, 0.f}; else if (k < nlr) ua += v; }, tag1)) { fail(); return; }
         sa += ua;
       }
@@ -1619,10 +1446,7 @@ __device__ __forceinline__ void gp_bwd_body(const GPersistArgs& a, GpLdsB<NT>& S
 #pragma unroll
       for (int n = 0; n < 9; ++n) lo[n] = slot2(t, r, min(gp + 2 * n, nkb - 1));
       f32x4 mv[9];
-      if (PROG & 2) {
-        if (!gp_sweep_prog<9, GP_HB9>(b2, lo, nvg, nvg, frag_off, slot2(t, r, min(gp + 2 * (lane >> 1), nkb - 1)) + (unsigned)(lane & 1) * 512u + 496u,
-                                 lane < 2 * nvg, (2 * nvg * GP_GATE_NUM) / GP_GATE_DEN, err, mv)) { fail(); return; }
-      } else if (!gp_sweep<9, true, 9, true>(b2, lo, nvg, frag_off, slot2(t, r, min(gp + 2 * (lane >> 1), nkb - 1)) + (unsigned)(lane & 1) * 512u + 496u,
+      if (!gp_sweep<9, true, 9, true>(b2, lo, nvg, frag_off, slot2(t, r, min(gp + 2 * (lane >> 1), nkb - 1)) + (unsigned)(lane & 1) * 512u + 496u,
                                  lane < 2 * nvg, err, [&](int k, const f32x4& v) { mv[k] = v; })) { fail(); return; }
       GPTSG(16);
 #pragma unroll
@@ -1641,7 +1465,7 @@ __device__ __forceinline__ void gp_bwd_body(const GPersistArgs& a, GpLdsB<NT>& S
 #endif
 }
 
-template <int NT, int PROG, bool RES, bool TAG>
+template <int NT, bool RES, bool TAG>
 __global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_bwd(const GPersistArgs a) {
   __shared__ __attribute__((aligned(16))) GpLdsB<NT> S;
   gu32* ctl = (gu32*)a.ctl;
@@ -1649,22 +1473,15 @@ __global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_bwd(const GPersistAr
   // (TAG) the ring step counters: T - 1 state-gradient steps and T input-gradient steps are written per launch
   const unsigned c1 = TAG ? __hip_atomic_load(ctl + GP_CTL_C1 + GP_CIDX(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
   const unsigned c3 = TAG ? __hip_atomic_load(ctl + GP_CTL_C3 + GP_CIDX(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-  gp_bwd_body<NT, PROG, RES, TAG>(a, S, c1, c3, blockIdx.x);
+  gp_bwd_body<NT, RES, TAG>(a, S, c1, c3, blockIdx.x);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add(ctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == gridDim.x - 1) {
+  if (threadIdx.x == 0)
+    persist_last_out(ctl, gen, [&] { return gridDim.x; }, [&] { return a.L[0].gates; }, GP_GEN_WRAP, [&] {
       if (TAG) {
         __hip_atomic_store(ctl + GP_CTL_C1 + GP_CIDX(a), (c1 + (unsigned)a.T - 1u) % (2u * GP_R1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(ctl + GP_CTL_C3 + GP_CIDX(a), (c3 + (unsigned)a.T) % (2u * GP_XR), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
-      if (__hip_atomic_load(ctl + DP_CTL_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
-        a.L[0].gates[0] = __builtin_nanf("");
-      __hip_atomic_store(ctl + DP_CTL_DONE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned g1 = gen + 1u;
-      __hip_atomic_store(ctl + DP_CTL_GEN, g1 >= (1u << 21) ? 1u : g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+    });
 }
 
 // The generator's BPTT AND the trailing form of the discriminator's (dpersist_dev.h dp_bwdt_body / dp_fcb_body) as ONE launch: the
@@ -1692,14 +1509,7 @@ __global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_bwd_dt(const GPersis
     __syncthreads();
     if (dbid < nD) { if (d.nrt == 1) dp_bwdt_body<true>(d, dgen, S.d, dbid); else dp_bwdt_body<false>(d, dgen, S.d, dbid); }
     else dp_fcb_body(d, dgen, S.d, dbid - nD);
-    if (threadIdx.x == 0) {
-      const unsigned old = __hip_atomic_fetch_add(dctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (old == (unsigned)nReal - 1u) {
-        if (__hip_atomic_load(dctl + DP_CTL_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) d.dy[0] = __builtin_nanf("");
-        __hip_atomic_store(dctl + DP_CTL_DONE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(dctl + DP_CTL_GEN, dgen + 1u == 0u ? 1u : dgen + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
+    if (threadIdx.x == 0) persist_last_out(dctl, dgen, [&] { return (unsigned)nReal; }, [&] { return d.dy; }, 0u, [] {});
     return;
   }
   gu32* ctl = (gu32*)a.ctl;
@@ -1707,22 +1517,15 @@ __global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_bwd_dt(const GPersis
   const unsigned gen = __hip_atomic_load(ctl + DP_CTL_GEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const unsigned c1 = TAG ? __hip_atomic_load(ctl + GP_CTL_C1 + GP_CIDX(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
   const unsigned c3 = TAG ? __hip_atomic_load(ctl + GP_CTL_C3 + GP_CIDX(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-  gp_bwd_body<NT, 0, RES, TAG>(a, S.g, c1, c3, gbid);
+  gp_bwd_body<NT, RES, TAG>(a, S.g, c1, c3, gbid);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add(ctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == gridDim.x - (unsigned)dt_pad - 1u) {
+  if (threadIdx.x == 0)
+    persist_last_out(ctl, gen, [&] { return gridDim.x - (unsigned)dt_pad; }, [&] { return a.L[0].gates; }, GP_GEN_WRAP, [&] {
       if (TAG) {
         __hip_atomic_store(ctl + GP_CTL_C1 + GP_CIDX(a), (c1 + (unsigned)a.T - 1u) % (2u * GP_R1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(ctl + GP_CTL_C3 + GP_CIDX(a), (c3 + (unsigned)a.T) % (2u * GP_XR), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
-      if (__hip_atomic_load(ctl + DP_CTL_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
-        a.L[0].gates[0] = __builtin_nanf("");
-      __hip_atomic_store(ctl + DP_CTL_DONE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned g1 = gen + 1u;
-      __hip_atomic_store(ctl + DP_CTL_GEN, g1 >= (1u << 21) ? 1u : g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+    });
 }
 
 
@@ -2044,16 +1847,7 @@ __global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_np_fwd(const GPersis
   const unsigned gen = __hip_atomic_load(ctl + DP_CTL_GEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   np_fwd_body<NT, KR, KX, CARRY>(a, S);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add(ctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == gridDim.x - 1) {
-      if (__hip_atomic_load(ctl + DP_CTL_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
-        a.L[a.nl - 1].h[0] = __builtin_nanf("");
-      __hip_atomic_store(ctl + DP_CTL_DONE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned g1 = gen + 1u;
-      __hip_atomic_store(ctl + DP_CTL_GEN, g1 >= (1u << 21) ? 1u : g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  if (threadIdx.x == 0) persist_last_out(ctl, gen, [] { return gridDim.x; }, [&] { return a.L[a.nl - 1].h; }, GP_GEN_WRAP, [] {});
 }
 
 
@@ -2345,16 +2139,7 @@ __global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_np_bwd(const GPersis
   const unsigned gen = __hip_atomic_load(ctl + DP_CTL_GEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   np_bwd_body(a, S);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add(ctl + DP_CTL_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == gridDim.x - 1) {
-      if (__hip_atomic_load(ctl + DP_CTL_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
-        a.L[0].gates[0] = __builtin_nanf("");
-      __hip_atomic_store(ctl + DP_CTL_DONE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned g1 = gen + 1u;
-      __hip_atomic_store(ctl + DP_CTL_GEN, g1 >= (1u << 21) ? 1u : g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  if (threadIdx.x == 0) persist_last_out(ctl, gen, [] { return gridDim.x; }, [&] { return a.L[0].gates; }, GP_GEN_WRAP, [] {});
 }
 
 static int gp_grid(const GPersistArgs& a) {
@@ -2468,36 +2253,22 @@ void gpersist_arm(const GPersistArgs& a, hipStream_t s) {
   if (a.gran3) (void)hipMemsetAsync(a.gran3, 0xFF, gpersist_gran3_bytes(a), s);
   (void)hipMemsetAsync(a.ctl + 4, 0, 12 * sizeof(unsigned), s);          // (tagged rings: every word's parity bit is 1 now, pass 0 writes 0)
 }
-// (-DGP_PROG_ONLY=mask: the progressive sweeps, gp_sweep_prog -- the harness only: measured slower, profiles/r5_gpersist_progressive_sweep_negative.txt)
-#ifndef GP_PROG_ONLY
-#define GP_PROG_ONLY 0
-#endif
+// Runtime flags as template arguments: f(std::bool_constant of every flag, in order).  (A launcher's `if constexpr` keeps the
+// combinations it never launches from being instantiated.)
+template <class F>
+static void gp_static(F&& f) { f(); }
+template <class F, class... B>
+static void gp_static(F&& f, bool v, B... more) {
+  if (v) gp_static([&](auto... c) { f(std::true_type{}, c...); }, more...);
+  else gp_static([&](auto... c) { f(std::false_type{}, c...); }, more...);
+}
 void launch_glstm_fwd(const GPersistArgs& a, hipStream_t s) {
   gp_arm_gran2(a, s);
   const dim3 g(gp_grid(a)), b(GP_WAVES * 64);
-  if (a.res == 2) {                                                    // res_lstm_i: out_l + x at every layer (gp_fwd_body RESX)
-    if (a.tags && !GP_PROG_ONLY) {
-      if (a.carry) hipLaunchKernelGGL((k_glstm_fwd_ri<5, 0, true, true>), g, b, 0, s, a);
-      else hipLaunchKernelGGL((k_glstm_fwd_ri<5, 0, true, false>), g, b, 0, s, a);
-    } else if (a.carry) hipLaunchKernelGGL((k_glstm_fwd_ri<5, GP_PROG_ONLY, false, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_glstm_fwd_ri<5, GP_PROG_ONLY, false, false>), g, b, 0, s, a);
-    ++g_chain_launches;
-    return;
-  }
-  if (a.carry) {                                                       // the stateful forward: the CARRY variants
-    if (a.tags && !GP_PROG_ONLY) {
-      if (a.res) hipLaunchKernelGGL((k_glstm_fwd<5, 0, true, true, true>), g, b, 0, s, a);
-      else hipLaunchKernelGGL((k_glstm_fwd<5, 0, false, true, true>), g, b, 0, s, a);
-    } else if (a.res) hipLaunchKernelGGL((k_glstm_fwd<5, GP_PROG_ONLY, true, false, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_glstm_fwd<5, GP_PROG_ONLY, false, false, true>), g, b, 0, s, a);
-    ++g_chain_launches;
-    return;
-  }
-  if (a.tags && !GP_PROG_ONLY) {
-    if (a.res) hipLaunchKernelGGL((k_glstm_fwd<5, 0, true, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_glstm_fwd<5, 0, false, true>), g, b, 0, s, a);
-  } else if (a.res) hipLaunchKernelGGL((k_glstm_fwd<5, GP_PROG_ONLY, true, false>), g, b, 0, s, a);
-  else hipLaunchKernelGGL((k_glstm_fwd<5, GP_PROG_ONLY, false, false>), g, b, 0, s, a);
+  // (a.res == 2, res_lstm_i: out_l + x at every layer, gp_fwd_body RESX; a.carry: the stateful forward)
+  gp_static([&](auto res, auto tag, auto carry, auto resx) {
+    if constexpr (res.value || !resx.value) hipLaunchKernelGGL((k_glstm_fwd<5, res.value, tag.value, carry.value, resx.value>), g, b, 0, s, a);
+  }, a.res != 0, a.tags != 0, a.carry != 0, a.res == 2);
   ++g_chain_launches;
 }
 // ---- the unprojected form: plan, sizes, launch ----
@@ -2523,11 +2294,11 @@ size_t gpersist_np_gran2_bytes(const GPersistArgs& a) { return (size_t)(a.N / GP
 size_t gpersist_np_lds_bytes() { return sizeof(NpLds<4, 7, 6>); }
 void launch_glstm_np_fwd(const GPersistArgs& a, hipStream_t s) {
   gpersist_arm_bytes(a.gran2, gpersist_np_gran2_bytes(a), s);
-  if (a.carry) {
-    if (a.NT == 2) hipLaunchKernelGGL((k_glstm_np_fwd<2, 8, 8, true>), dim3(gp_grid(a)), dim3(GP_WAVES * 64), 0, s, a);
-    else hipLaunchKernelGGL((k_glstm_np_fwd<4, 7, 6, true>), dim3(gp_grid(a)), dim3(GP_WAVES * 64), 0, s, a);
-  } else if (a.NT == 2) hipLaunchKernelGGL((k_glstm_np_fwd<2, 8, 8>), dim3(gp_grid(a)), dim3(GP_WAVES * 64), 0, s, a);
-  else hipLaunchKernelGGL((k_glstm_np_fwd<4, 7, 6>), dim3(gp_grid(a)), dim3(GP_WAVES * 64), 0, s, a);
+  const dim3 g(gp_grid(a)), b(GP_WAVES * 64);
+  gp_static([&](auto nt2, auto carry) {
+    if constexpr (nt2.value) hipLaunchKernelGGL((k_glstm_np_fwd<2, 8, 8, carry.value>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_glstm_np_fwd<4, 7, 6, carry.value>), g, b, 0, s, a);
+  }, a.NT == 2, a.carry != 0);
   ++g_chain_launches;
 }
 // (the unprojected BPTT: 8 cells per workgroup only; gran1 / gran3 = its two rings, armed once)
@@ -2546,31 +2317,19 @@ int gpersist_dt_grid(const GPersistArgs& a, const DPersistArgs& d) { return gp_g
 void launch_glstm_bwd_dt(const GPersistArgs& a, const DPersistArgs& d, hipStream_t s) {
   gp_arm_gran2(a, s);
   const dim3 g(gpersist_dt_grid(a, d)), b(GP_WAVES * 64);
-  if (a.tags) {
-    if (a.res) hipLaunchKernelGGL((k_glstm_bwd_dt<5, true, true>), g, b, 0, s, a, d);
-    else hipLaunchKernelGGL((k_glstm_bwd_dt<5, false, true>), g, b, 0, s, a, d);
-  } else if (a.res) hipLaunchKernelGGL((k_glstm_bwd_dt<5, true, false>), g, b, 0, s, a, d);
-  else hipLaunchKernelGGL((k_glstm_bwd_dt<5, false, false>), g, b, 0, s, a, d);
+  gp_static([&](auto res, auto tag) { hipLaunchKernelGGL((k_glstm_bwd_dt<5, res.value, tag.value>), g, b, 0, s, a, d); }, a.res != 0, a.tags != 0);
   g_chain_launches += 2;
 }
 void launch_glstm_fwd_dt(const GPersistArgs& a, const DPersistArgs& d, hipStream_t s) {
   gp_arm_gran2(a, s);
   const dim3 g(gpersist_dt_grid(a, d)), b(GP_WAVES * 64);
-  if (a.tags) {
-    if (a.res) hipLaunchKernelGGL((k_glstm_fwd_dt<5, true, true>), g, b, 0, s, a, d);
-    else hipLaunchKernelGGL((k_glstm_fwd_dt<5, false, true>), g, b, 0, s, a, d);
-  } else if (a.res) hipLaunchKernelGGL((k_glstm_fwd_dt<5, true, false>), g, b, 0, s, a, d);
-  else hipLaunchKernelGGL((k_glstm_fwd_dt<5, false, false>), g, b, 0, s, a, d);
+  gp_static([&](auto res, auto tag) { hipLaunchKernelGGL((k_glstm_fwd_dt<5, res.value, tag.value>), g, b, 0, s, a, d); }, a.res != 0, a.tags != 0);
   g_chain_launches += 2;
 }
 void launch_glstm_bwd(const GPersistArgs& a, hipStream_t s) {
   gp_arm_gran2(a, s);
   const dim3 g(gp_grid(a)), b(GP_WAVES * 64);
-  if (a.tags && !GP_PROG_ONLY) {
-    if (a.res) hipLaunchKernelGGL((k_glstm_bwd<5, 0, true, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_glstm_bwd<5, 0, false, true>), g, b, 0, s, a);
-  } else if (a.res) hipLaunchKernelGGL((k_glstm_bwd<5, GP_PROG_ONLY, true, false>), g, b, 0, s, a);
-  else hipLaunchKernelGGL((k_glstm_bwd<5, GP_PROG_ONLY, false, false>), g, b, 0, s, a);
+  gp_static([&](auto res, auto tag) { hipLaunchKernelGGL((k_glstm_bwd<5, res.value, tag.value>), g, b, 0, s, a); }, a.res != 0, a.tags != 0);
   ++g_chain_launches;
 }
 

@@ -5,7 +5,7 @@ Bounds: the small nets are held to tests/test_gpu_parity.py's for the same quant
 tensor, variables and EMA after the steps 1e-4, outputs 1e-4), the reference widths to tests/test_gpu_fullsize.py's (losses and
 enhanced-MFCC L1 1e-3, every gradient tensor 2e-3), the stateful forward to tests/test_gpu_stream.py's (1e-4 small, 1e-3 reference
 width).  Which plan ran is asserted through the launch counters (rsrgan_profile_read_kind): kind 1 the persistent forward launch
-(k_glstm_fwd_ri here), kind 2 the persistent BPTT.
+(k_glstm_fwd<..., RESX> here), kind 2 the persistent BPTT.
 
 RES_LSTM_I_MARGIN_OUT=<file>: the reference-width cases append their achieved errors to that JSON file (the way
 profiles/r7_stream_margin.json was written; DESIGN.md 6k says what has been recorded so far)."""
