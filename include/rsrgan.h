@@ -330,6 +330,39 @@ int rsrgan_op_lstm_colsums(int32_t nb, const float* const* dz, const float* cons
 int rsrgan_op_colsum(const float* a, int32_t lda, const float* b, int32_t ldb, float* out, int32_t rows, int32_t cols, int32_t tall,
                      void* stream);
 
+/* ---- the implicit-GEMM convolution of the R-CED generator (csrc/conv.hip).  Unit parity tests only (tests/test_gpu_conv_ops.py,
+ * tests/test_op_args.py); no trainer calls them.  Each goes through the host launch function Model::rced_forward / rced_backward
+ * call and never launches a kernel directly.  Layout: NHWC, `in` [R*S*W][ldc_in] (R frames of S rows x W columns, C channels; C = 1:
+ * ldc_in = 4 as the model's expanded input), kernel [S, fw] over the whole height, stride 1, SAME.  A null pointer, a leading dimension
+ * that is no multiple of 4 or shorter than its padded row, a misaligned pointer or bias (16 bytes for in, out, mask, bias, d and ws --
+ * the kernels move them as float4 --, 4 bytes for dW and db, which the reducer stores as scalars), R < 1, R > R_max, more than 2^24
+ * positions R*S*W (the entries' own limit: far above any test, far below the 32-bit offsets of the kernels) or a short workspace returns
+ * RSRGAN_ERR_INVALID before the first HIP call, rsrgan_last_error() naming it.  rsrgan_op_conv_fwd keeps one prepared-filter buffer per
+ * calling thread, grown on demand and never freed.  A shape the implicit kernels do not cover returns
+ * RSRGAN_OP_NOT_APPLICABLE with nothing launched and the outputs untouched (the model then takes the patch-matrix path).
+ *
+ * rsrgan_op_conv_fwd: launch_conv_prep into a private buffer, then launch_conv_fwd.  flip = 0: out[.., N] = conv(in[.., C], F) (+ bias)
+ * (relu), F [S*fw*C][ldf] with N columns as the model stores a layer C -> N.  flip = 1: the data gradient of a layer N -> C: `in` is the
+ * gradient of its output (C channels), F its filter [S*fw*N][ldf] with C columns, out the gradient of its input (N channels).
+ * mask (may be NULL) [R*S*W][ldc_out]: out = 0 where mask <= 0.  Columns [N, ldc_out) of out are never written. */
+int rsrgan_op_conv_fwd(const float* in, int32_t ldc_in, int32_t C, const float* F, int32_t ldf, int32_t flip, const float* bias, int32_t relu,
+                       const float* mask, float* out, int32_t ldc_out, int32_t N, int32_t R, int32_t S, int32_t W, int32_t fw, void* stream);
+/* dW [S*fw*C][ldw] = the weight gradient of a layer C -> N from its input `in` and output gradient d [R*S*W][ldc_d]; db (may be NULL)
+ * [N] = the column sums of d.  ws: a caller-owned workspace of ws_floats >= rsrgan_op_conv_ws_floats(C, R_max, S, W, fw) floats. */
+int rsrgan_op_conv_wgrad(const float* in, int32_t ldc_in, int32_t C, const float* d, int32_t ldc_d, int32_t N, float* dW, int32_t ldw, float* db,
+                         float* ws, int64_t ws_floats, int32_t R_max, int32_t R, int32_t S, int32_t W, int32_t fw, void* stream);
+/* conv_wgrad_ws_floats: the workspace for any frame count 1 .. R_max (negative: an argument error).  No device needed. */
+int64_t rsrgan_op_conv_ws_floats(int32_t C, int32_t R_max, int32_t S, int32_t W, int32_t fw);
+/* bit 0: conv_fwd_supported(C, N, S, W, fw), bit 1: conv_wgrad_supported (negative: an argument error).  No device needed. */
+int rsrgan_op_conv_supported(int32_t C, int32_t N, int32_t S, int32_t W, int32_t fw);
+/* what the calling thread's last rsrgan_op_conv_fwd / _wgrad launched: out[0] = launches (0: not applicable; forward: 1 or 2 = the
+ * row-aligned main launch and its remainder; weight gradient: 1), then 19 values per launch: kernel family (1 k_conv_fwd<RT, NT>,
+ * 2 k_conv_fwd4<G, NCG, KS>, 3 k_conv_wgrad<KT, NT, 16, DH>, 4 k_conv_wgrad4<NCG, 3, NWV>), its three template arguments in that order,
+ * branch (forward: 1 whole width, 2 row-aligned main, 3 remainder; weight gradient, the rule of wgrad_plan that set DH: 1 two k'-tile
+ * rounds, 2 six or four rows, 3 searched over 1..3), TW, FB, grid x, y, z, LDS bytes, DH, fpg, groups, nstrips, nkg, PS, waves, gmax
+ * (the last eight: weight gradient only) */
+int rsrgan_op_conv_last_plan(int32_t out[40]);
+
 /* ---- SEGAN-style conv G/D (models/segan.py:SEGAN with generator.py:AEGenerator, discriminator.py:discriminator, utils/bnorm.py:VBN;
  * BASELINE.json configs[4]).  The reference's trainer cannot run as shipped (segan.py:136 calls an undefined variables_on_gpu0(),
  * scripts/train_segan.py:20 imports a missing module); the graph it would build is fully specified and is what these entry

@@ -26,6 +26,7 @@ SYMBOLS = ["rsrgan_default_cfg", "rsrgan_create", "rsrgan_destroy", "rsrgan_last
            "rsrgan_profile_begin", "rsrgan_profile_read", "rsrgan_profile_read_kind", "rsrgan_profile_launches", "rsrgan_op_launch_floor", "rsrgan_device_status", "rsrgan_set_dropout",
            "rsrgan_op_gemm", "rsrgan_op_gemm2", "rsrgan_op_gemm_batch", "rsrgan_op_gemm16_batch", "rsrgan_op_gemm_last_plan",
            "rsrgan_op_lstm_colsums", "rsrgan_op_colsum", "rsrgan_version",
+           "rsrgan_op_conv_fwd", "rsrgan_op_conv_wgrad", "rsrgan_op_conv_ws_floats", "rsrgan_op_conv_supported", "rsrgan_op_conv_last_plan",
            "rsrgan_segan_default_cfg", "rsrgan_segan_create", "rsrgan_segan_destroy", "rsrgan_segan_set_scalar",
            "rsrgan_segan_num_tensors", "rsrgan_segan_tensor_info", "rsrgan_segan_param_count", "rsrgan_segan_get_params",
            "rsrgan_segan_set_params", "rsrgan_segan_forward_g", "rsrgan_segan_d_backward", "rsrgan_segan_g_backward",
@@ -110,6 +111,12 @@ def load():
     lib.rsrgan_op_gemm_last_plan.argtypes = [C.POINTER(i32)]
     lib.rsrgan_op_lstm_colsums.argtypes = [i32, pp, pp, pp, pp, pp, pp, pp, i32, i32, vp]
     lib.rsrgan_op_colsum.argtypes = [p, i32, p, i32, p, i32, i32, i32, vp]
+    lib.rsrgan_op_conv_fwd.argtypes = [p, i32, i32, p, i32, i32, p, i32, p, p, i32, i32, i32, i32, i32, i32, vp]
+    lib.rsrgan_op_conv_wgrad.argtypes = [p, i32, i32, p, i32, i32, p, i32, p, p, i64, i32, i32, i32, i32, i32, vp]
+    lib.rsrgan_op_conv_ws_floats.argtypes = [i32, i32, i32, i32, i32]
+    lib.rsrgan_op_conv_ws_floats.restype = i64
+    lib.rsrgan_op_conv_supported.argtypes = [i32, i32, i32, i32, i32]
+    lib.rsrgan_op_conv_last_plan.argtypes = [C.POINTER(i32)]
     lib.rsrgan_segan_default_cfg.argtypes = [C.POINTER(SeganCfg)]
     lib.rsrgan_segan_create.argtypes = [C.POINTER(SeganCfg), C.c_uint64, C.POINTER(vp)]
     lib.rsrgan_segan_destroy.argtypes = [vp]
@@ -136,6 +143,12 @@ GEMM_PLAN_FIELDS = ("cls", "bm", "bn", "W", "n_dp", "fixup", "splits", "Ur")
 # force_cfg of rsrgan_op_gemm2: (kernel class, BM, BN) of each tile form
 GEMM_FORMS = [("k_gemm", 128, 128), ("k_gemm", 96, 128), ("k_gemm", 128, 96), ("k_gemm", 256, 64), ("k_gemm", 256, 32),
               ("k_gemm_s", 256, 256), ("k_gemm_s", 128, 256), ("k_gemm_s", 256, 128)]
+# rsrgan_op_conv_last_plan: kernel families, branches and the 19 fields of each launch of the record
+CONV_FAMILIES = {0: "none", 1: "fwd", 2: "fwd4", 3: "wgrad", 4: "wgrad4"}
+CONV_FWD_BRANCHES = {1: "whole", 2: "main", 3: "rem"}
+CONV_WGRAD_BRANCHES = {1: "k2", 2: "rows", 3: "search"}
+CONV_PLAN_FIELDS = ("family", "a0", "a1", "a2", "branch", "TW", "FB", "gx", "gy", "gz", "lds", "DH", "fpg", "groups", "nstrips", "nkg",
+                    "PS", "waves", "gmax")
 
 
 def ptr_table(ptrs):

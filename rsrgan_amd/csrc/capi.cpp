@@ -658,4 +658,86 @@ int rsrgan_op_colsum(const float* a, int32_t lda, const float* b, int32_t ldb, f
   return RSRGAN_OK;
 }
 
+
+// ---- the implicit-GEMM convolution (conv.hip) through the launch functions Model::rced_forward / rced_backward call
+// the prepared filter Ft of one call: grow-only and kept for the life of the thread like op_ws() for the process (a test entry has no
+// handle to hang it on); per thread, as the plan record beside it, so two threads never share one
+static float* op_conv_ft(size_t floats) {
+  static thread_local float* ft = nullptr;
+  static thread_local size_t cap = 0;
+  if (floats > cap) {
+    if (ft) { (void)hipDeviceSynchronize(); (void)hipFree(ft); ft = nullptr; cap = 0; }
+    if (hipMalloc((void**)&ft, floats * sizeof(float)) != hipSuccess) { ft = nullptr; return nullptr; }
+    cap = floats;
+  }
+  return ft;
+}
+static inline int op_pad4(int n) { return (n + 3) & ~3; }
+#define OP_CONV_SHAPE(who) \
+  OP_REFUSE(C < 1 || N < 1 || S < 1 || W < 1 || fw < 1, who ": C, N, S, W, fw must be positive (got %d, %d, %d, %d, %d)", C, N, S, W, fw); \
+  OP_REFUSE(R < 1, who ": R = %d frames", R); \
+  OP_REFUSE((long long)R * S * W > (1 << 24), who ": R x S x W = %lld positions exceed the entry's 2^24", (long long)R * S * W)
+
+int rsrgan_op_conv_supported(int32_t C, int32_t N, int32_t S, int32_t W, int32_t fw) {
+  OP_REFUSE(C < 1 || N < 1 || S < 1 || W < 1 || fw < 1, "op_conv_supported: C, N, S, W, fw must be positive (got %d, %d, %d, %d, %d)", C, N, S, W, fw);
+  return (conv_fwd_supported(C, N, S, W, fw) ? 1 : 0) | (conv_wgrad_supported(C, N, S, W, fw) ? 2 : 0);
+}
+
+int64_t rsrgan_op_conv_ws_floats(int32_t C, int32_t R_max, int32_t S, int32_t W, int32_t fw) {
+  OP_REFUSE(C < 1 || R_max < 1 || S < 1 || W < 1 || fw < 1, "op_conv_ws_floats: C, R_max, S, W, fw must be positive (got %d, %d, %d, %d, %d)", C, R_max, S, W, fw);
+  return (int64_t)conv_wgrad_ws_floats(C, R_max, S, W, fw);
+}
+
+int rsrgan_op_conv_fwd(const float* in, int32_t ldc_in, int32_t C, const float* F, int32_t ldf, int32_t flip, const float* bias, int32_t relu,
+                       const float* mask, float* out, int32_t ldc_out, int32_t N, int32_t R, int32_t S, int32_t W, int32_t fw, void* stream) {
+  OP_REFUSE(!in || !F || !out, "op_conv_fwd: null pointer (in, F or out)");
+  OP_CONV_SHAPE("op_conv_fwd");
+  OP_REFUSE((ldc_in & 3) || (ldc_out & 3) || (ldf & 3), "op_conv_fwd: leading dimension not a multiple of 4 (ldc_in %d, ldc_out %d, ldf %d)", ldc_in, ldc_out, ldf);
+  OP_REFUSE(ldc_in < op_pad4(C) || ldc_out < op_pad4(N) || ldf < (flip ? C : N),
+            "op_conv_fwd: leading dimension below its row (ldc_in %d for C = %d, ldc_out %d for N = %d, ldf %d for %d filter columns)", ldc_in, C, ldc_out, N, ldf, flip ? C : N);
+  OP_REFUSE(((size_t)in & 15) || ((size_t)out & 15) || ((size_t)mask & 15), "op_conv_fwd: in, out or mask not 16-byte aligned");
+  OP_REFUSE((size_t)bias & 15, "op_conv_fwd: bias not 16-byte aligned (k_conv_fwd4 adds it as float4)");
+  g_conv_last_plan.n = 0;
+  if (!conv_fwd_supported(C, N, S, W, fw)) return RSRGAN_OP_NOT_APPLICABLE;      // (the model: the patch-matrix path)
+  float* Ft = op_conv_ft(conv_prep_floats(S, fw, C));
+  if (!Ft) { set_error("op_conv_fwd: hipMalloc failed"); return RSRGAN_ERR_HIP; }
+  // forward: the layer is C -> N; data gradient (flip): the layer is N -> C, F is its filter and `in` its output gradient
+  launch_conv_prep(F, ldf, S, fw, flip ? N : C, flip ? C : N, flip != 0, Ft, (hipStream_t)stream);
+  launch_conv_fwd(in, ldc_in, C, Ft, bias, relu != 0, out, ldc_out, N, R, S, W, fw, (hipStream_t)stream, mask);
+  if (hipGetLastError() != hipSuccess) { set_error("op_conv_fwd launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
+
+int rsrgan_op_conv_wgrad(const float* in, int32_t ldc_in, int32_t C, const float* d, int32_t ldc_d, int32_t N, float* dW, int32_t ldw, float* db,
+                         float* ws, int64_t ws_floats, int32_t R_max, int32_t R, int32_t S, int32_t W, int32_t fw, void* stream) {
+  OP_REFUSE(!in || !d || !dW || !ws, "op_conv_wgrad: null pointer (in, d, dW or ws)");
+  OP_CONV_SHAPE("op_conv_wgrad");
+  OP_REFUSE(R > R_max, "op_conv_wgrad: R = %d frames above R_max = %d the workspace is sized for", R, R_max);
+  OP_REFUSE((ldc_in & 3) || (ldc_d & 3) || (ldw & 3), "op_conv_wgrad: leading dimension not a multiple of 4 (ldc_in %d, ldc_d %d, ldw %d)", ldc_in, ldc_d, ldw);
+  OP_REFUSE(ldc_in < op_pad4(C) || ldc_d < op_pad4(N) || ldw < N,
+            "op_conv_wgrad: leading dimension below its row (ldc_in %d for C = %d, ldc_d %d and ldw %d for N = %d)", ldc_in, C, ldc_d, ldw, N);
+  OP_REFUSE(((size_t)in & 15) || ((size_t)d & 15) || ((size_t)ws & 15), "op_conv_wgrad: in, d or ws not 16-byte aligned");
+  OP_REFUSE(((size_t)dW & 3) || ((size_t)db & 3), "op_conv_wgrad: dW or db not 4-byte aligned");      // (k_conv_wgrad_red stores scalars)
+  g_conv_last_plan.n = 0;
+  if (!conv_wgrad_supported(C, N, S, W, fw)) return RSRGAN_OP_NOT_APPLICABLE;    // (the model: the patch matrix and a GEMM)
+  const size_t need = conv_wgrad_ws_floats(C, R_max, S, W, fw);
+  OP_REFUSE(ws_floats < 0 || (size_t)ws_floats < need, "op_conv_wgrad: workspace of %lld floats below the %zu that R_max = %d frames need", (long long)ws_floats, need, R_max);
+  launch_conv_wgrad(in, ldc_in, C, d, ldc_d, N, dW, ldw, ws, R, S, W, fw, (hipStream_t)stream, db);
+  if (hipGetLastError() != hipSuccess) { set_error("op_conv_wgrad launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
+
+int rsrgan_op_conv_last_plan(int32_t out[40]) {
+  OP_REFUSE(!out, "op_conv_last_plan: null pointer");
+  const ConvPlanRecord& p = g_conv_last_plan;
+  for (int i = 0; i < 40; ++i) out[i] = 0;
+  out[0] = p.n;
+  for (int i = 0; i < p.n && i < 2; ++i) {
+    const ConvLaunchRecord& r = p.l[i];
+    const int v[19] = {r.family, r.a0, r.a1, r.a2, r.branch, r.TW, r.FB, r.gx, r.gy, r.gz, r.lds, r.DH, r.fpg, r.groups, r.nstrips, r.nkg, r.PS, r.waves, r.gmax};
+    for (int j = 0; j < 19; ++j) out[1 + 19 * i + j] = v[j];
+  }
+  return RSRGAN_OK;
+}
+
 }  // extern "C"

@@ -887,6 +887,15 @@ __global__ __launch_bounds__(512) void k_conv_fwd4(const float* __restrict__ in,
   }
 }
 
+thread_local ConvPlanRecord g_conv_last_plan = {};    // what this host thread launched last (host-only; rsrgan_op_conv_last_plan)
+static ConvLaunchRecord* conv_record(int family, int a0, int a1, int a2, int branch, int TW, int FB, dim3 grid, size_t lds) {
+  ConvPlanRecord& p = g_conv_last_plan;
+  if (p.n >= 2) return nullptr;
+  ConvLaunchRecord& r = p.l[p.n++];
+  r = ConvLaunchRecord{family, a0, a1, a2, branch, TW, FB, (int)grid.x, (int)grid.y, (int)grid.z, (int)lds, 0, 0, 0, 0, 0, 0, 0, 0};
+  return &r;
+}
+
 void launch_conv_prep(const float* F, int ldf_src, int S, int fw, int Cin, int Cout, bool flip, float* Ft, hipStream_t s) {
   const size_t total = conv_prep_floats(S, fw, flip ? Cout : Cin);
   hipLaunchKernelGGL(k_conv_prep, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, F, ldf_src, S, fw, Cin, Cout, flip ? 1 : 0, Ft);
@@ -937,7 +946,8 @@ static bool launch_conv_fwd4(int G, int ncg, dim3 grid, size_t lds, hipStream_t 
 
 // one launch over the columns [wbase, wend) in strips of TW
 static void conv_fwd_range(int wbase, int wend, int TW, int RT, size_t lds, const float* in, int ldc_in, int C, const float* Ft, const float* bias,
-                           int rl, float* out, int ldc_out, int N, int R, int S, int W, int fw, hipStream_t s, const float* mask, int FB = 1) {
+                           int rl, float* out, int ldc_out, int N, int R, int S, int W, int fw, hipStream_t s, const float* mask, int FB = 1,
+                           int branch = CONV_BR_WHOLE) {
   const bool small = RT == 4;
   static bool attr = false;
   if (!attr) {
@@ -957,8 +967,12 @@ static void conv_fwd_range(int wbase, int wend, int TW, int RT, size_t lds, cons
     // four sets x k' halves at S = 11, measured slower: 566 vs 558 ms per step of the R-CED variant)
     const int G = small ? (switches().conv4_ks == 4 ? 4 : 2) : 3, ncg = N / 4;
     const size_t lds4 = std::max(lds, (size_t)8 * ncg * 1024 * (G == 3 ? 2 : G == 4 ? 2 : 1));      // the tree's widest round
-    if (lds4 <= 160 * 1024 && launch_conv_fwd4(G, ncg, grid, lds4, s, in, ldc_in, C, Ft, bias, rl, out, ldc_out, N, S, W, fw, TW, mask, wbase, wend, FB, R)) return;
+    if (lds4 <= 160 * 1024 && launch_conv_fwd4(G, ncg, grid, lds4, s, in, ldc_in, C, Ft, bias, rl, out, ldc_out, N, S, W, fw, TW, mask, wbase, wend, FB, R)) {
+      conv_record(CONV_FAM_FWD4, G, ncg, G == 4 ? 4 : 2, branch, TW, FB, grid, lds4);
+      return;
+    }
   }
+  conv_record(CONV_FAM_FWD, RT, N <= 16 ? 1 : 2, 0, branch, TW, FB, grid, lds);
   if (small && N <= 16) hipLaunchKernelGGL((k_conv_fwd<4, 1>), grid, dim3(512), lds, s, in, ldc_in, C, Ft, bias, rl, out, ldc_out, N, S, W, fw, TW, mask, wbase, wend, FB, R);
   else if (small) hipLaunchKernelGGL((k_conv_fwd<4, 2>), grid, dim3(512), lds, s, in, ldc_in, C, Ft, bias, rl, out, ldc_out, N, S, W, fw, TW, mask, wbase, wend, FB, R);
   else if (N <= 16) hipLaunchKernelGGL((k_conv_fwd<6, 1>), grid, dim3(512), lds, s, in, ldc_in, C, Ft, bias, rl, out, ldc_out, N, S, W, fw, TW, mask, wbase, wend, FB, R);
@@ -968,6 +982,7 @@ static void conv_fwd_range(int wbase, int wend, int TW, int RT, size_t lds, cons
 void launch_conv_fwd(const float* in, int ldc_in, int C, const float* Ft, const float* bias, bool relu, float* out, int ldc_out, int N,
                      int R, int S, int W, int fw, hipStream_t s, const float* mask) {
   int TW = W, RT = 4; size_t lds = 0;
+  g_conv_last_plan.n = 0;
   if (!conv_fwd_plan(C, S, W, fw, TW, RT, lds)) return;
   const int rl = relu ? 1 : 0;
   // Row-aligned strips (RSRGAN_CONV_ROWS=0 turns them off): with 64-column strips a 16- or 64-position group never straddles two
@@ -977,7 +992,7 @@ void launch_conv_fwd(const float* in, int ldc_in, int C, const float* Ft, const 
   const size_t lds64 = ((size_t)(S + 1) * ((64 + fw - 1) * conv_cpad(C) + 16) + (size_t)32 * conv_ldf(fw, C)) * sizeof(float);
   if (switches().conv_rows && W > 64 && S * 64 <= 8 * 6 * 16 && lds64 <= 160 * 1024) {
     const int wmain = W / 64 * 64;
-    conv_fwd_range(0, wmain, 64, 6, lds64, in, ldc_in, C, Ft, bias, rl, out, ldc_out, N, R, S, W, fw, s, mask);
+    conv_fwd_range(0, wmain, 64, 6, lds64, in, ldc_in, C, Ft, bias, rl, out, ldc_out, N, R, S, W, fw, s, mask, 1, CONV_BR_MAIN);
     if (wmain < W) {
       int TWr = W - wmain, RTr = 4; size_t ldsr = 0;
       if (!conv_fwd_plan(C, S, W - wmain, fw, TWr, RTr, ldsr)) return;
@@ -991,7 +1006,7 @@ void launch_conv_fwd(const float* in, int ldc_in, int C, const float* Ft, const 
         FB = std::max(1, std::min(std::min(cap, fit), 16));
         ldsr = ((size_t)FB * S + 1) * rowb + filt;
       }
-      conv_fwd_range(wmain, W, TWr, RTr, ldsr, in, ldc_in, C, Ft, bias, rl, out, ldc_out, N, R, S, W, fw, s, mask, FB);
+      conv_fwd_range(wmain, W, TWr, RTr, ldsr, in, ldc_in, C, Ft, bias, rl, out, ldc_out, N, R, S, W, fw, s, mask, FB, CONV_BR_REM);
     }
     return;
   }
@@ -1005,15 +1020,17 @@ static int wgrad_tw(int S, int W) {          // narrower strips than the forward
   const int ns = (W + 31) / 32;
   return (W + ns - 1) / ns;
 }
-static void wgrad_plan(int R, int S, int nstrips, int KP, int& DH, int& fpg, int& groups) {
+static void wgrad_plan(int R, int S, int nstrips, int KP, int& DH, int& fpg, int& groups, int* branch = nullptr, int* gmax_used = nullptr) {
   const int dhmax = switches().wgrad_dh;
   int best = 1 << 30;
+  auto tell = [&](int b, int g) { if (branch) *branch = b; if (gmax_used) *gmax_used = g; };      // (for the plan record only)
   DH = 1; fpg = R; groups = 1;
   // multi-strip frames with one k'-tile per wave (K' <= 256): 4 or 6 rows per workgroup in the rows-inside form (its accumulators
   // fit the 128 registers of a 16-wave workgroup); the measure is the LDS operand reads + staged frames per MFMA
   if (nstrips > 1 && KP > 16 * 16 && dhmax >= 3) {        // two k'-tile rounds: 3 rows (accumulators: 3 x 2 x NT tiles)
     const int ng = (S + 2) / 3, gmax = std::max(1, 256 / (ng * nstrips));
     DH = 3; fpg = std::max(1, (R + gmax - 1) / gmax); groups = (R + fpg - 1) / fpg;
+    tell(CONV_BR_WG_K2, gmax);
     return;
   }
   if (nstrips > 1 && KP <= 16 * 16 && dhmax > 3) {
@@ -1024,6 +1041,7 @@ static void wgrad_plan(int R, int S, int nstrips, int KP, int& DH, int& fpg, int
       const int gmax = std::max(1, 256 / (ng * nstrips));
       const int f = std::max(1, (R + gmax - 1) / gmax);
       DH = dhc; fpg = f; groups = (R + f - 1) / f;
+      tell(CONV_BR_WG_ROWS, gmax);
       return;
     }
   }
@@ -1033,7 +1051,7 @@ static void wgrad_plan(int R, int S, int nstrips, int KP, int& DH, int& fpg, int
     const int ng = (S + dhc - 1) / dhc;
     const int gmax = std::max(1, 256 / (ng * nstrips));
     const int f = std::max(1, (R + gmax - 1) / gmax);
-    if (f < best) { best = f; DH = dhc; fpg = f; groups = (R + f - 1) / f; }
+    if (f < best) { best = f; DH = dhc; fpg = f; groups = (R + f - 1) / f; tell(CONV_BR_WG_SEARCH, gmax); }
   }
 }
 // k_conv_wgrad4: position parts per (k' group, row set) of a 16-wave workgroup
@@ -1047,10 +1065,11 @@ static int wgrad4_waves(int KP, int DH, int& PS) {
 }
 // the plan of the 4x4x1 form: its 64-lane groups cover fw*C filter elements (no channel pads), and up to four of them take the
 // six-rows-per-workgroup plan whatever the padded K' is
-static void wgrad4_plan(int C, int R, int S, int nstrips, int fw, int& DH, int& fpg, int& groups, int& nkg, int& PS, int& nwv) {
+static void wgrad4_plan(int C, int R, int S, int nstrips, int fw, int& DH, int& fpg, int& groups, int& nkg, int& PS, int& nwv,
+                        int* branch = nullptr, int* gmax_used = nullptr) {
   nkg = (fw * C + 63) / 64;
   const int KP = conv_kp(fw, C);
-  wgrad_plan(R, S, nstrips, nkg <= 4 ? std::min(KP, 256) : KP, DH, fpg, groups);
+  wgrad_plan(R, S, nstrips, nkg <= 4 ? std::min(KP, 256) : KP, DH, fpg, groups, branch, gmax_used);
   nwv = wgrad4_waves(64 * nkg, DH, PS);
 }
 static size_t conv_wgrad_ws_floats_at(int C, int R, int S, int W, int fw) {
@@ -1124,12 +1143,17 @@ void launch_conv_wgrad(const float* in, int ldc_in, int C, const float* d, int l
   // widths that waste 16-wide MFMA columns; unlike the forward kernel it has no padded positions to pay for).  RSRGAN_WGRAD4: 0 =
   // never, 1 = widths that are no multiple of 16, 2 = all (default); RSRGAN_CONV4=0 alone turns both directions off.
   const int w4 = switches().wgrad4 >= 0 ? switches().wgrad4 : (switches().conv4 ? 2 : 0);
-  int nkg = 1, PS = 1, nwv4 = 8;
-  wgrad4_plan(C, R, S, nstrips, fw, DH, fpg, groups, nkg, PS, nwv4);
+  int nkg = 1, PS = 1, nwv4 = 8, branch = 0, gmax = 0;
+  wgrad4_plan(C, R, S, nstrips, fw, DH, fpg, groups, nkg, PS, nwv4, &branch, &gmax);
   const bool use4 = w4 && N % 4 == 0 && N <= 32 && (w4 > 1 || N % 16 != 0) && nkg * ((DH + 2) / 3) <= 12 &&
                     ((TW + fw - 1) * conv_cpad(C) + 16) / 4 <= 64 * nwv4;
-  if (!use4) { PS = 1; wgrad_plan(R, S, nstrips, KP, DH, fpg, groups); }
+  if (!use4) { PS = 1; wgrad_plan(R, S, nstrips, KP, DH, fpg, groups, &branch, &gmax); }
   dim3 grid((S + DH - 1) / DH, groups, nstrips);
+  g_conv_last_plan.n = 0;
+  if (ConvLaunchRecord* r = use4 ? conv_record(CONV_FAM_WGRAD4, N / 4, 3, nwv4, branch, TW, 1, grid, lds)
+                                 : conv_record(CONV_FAM_WGRAD, KP > 16 * 16 ? 2 : 1, N <= 16 ? 1 : 2, DH, branch, TW, 1, grid, lds)) {
+    r->DH = DH; r->fpg = fpg; r->groups = groups; r->nstrips = nstrips; r->nkg = use4 ? nkg : 0; r->PS = PS; r->waves = use4 ? nwv4 : 16; r->gmax = gmax;
+  }
   const int nparts = groups * nstrips * PS;
   float* bpart = db ? ws + (size_t)nparts * S * KP * 32 : nullptr;
   if (use4) {

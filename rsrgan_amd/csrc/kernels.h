@@ -367,6 +367,21 @@ size_t conv_wgrad_ws_floats(int C, int R, int S, int W, int fw);
 void launch_conv_wgrad(const float* in, int ldc_in, int C, const float* d, int ldc_d, int N, float* dW, int ldw, float* ws, int R, int S,
                        int W, int fw, hipStream_t s,
                        float* db = nullptr /* also the bias gradient colsum(d)[0:N] */);
+// What the convolution launch code of this host thread launched last (launch_conv_fwd: the main and the remainder launch; launch_conv_wgrad:
+// its one kernel launch), a few host stores per launch, read back by rsrgan_op_conv_last_plan so a unit test can assert WHICH kernel,
+// template arguments and planner branch computed its numbers.  Host-only: no kernel sees it.
+enum { CONV_FAM_NONE = 0, CONV_FAM_FWD = 1 /* k_conv_fwd<RT, NT> */, CONV_FAM_FWD4 = 2 /* k_conv_fwd4<G, NCG, KS> */,
+       CONV_FAM_WGRAD = 3 /* k_conv_wgrad<KT, NT, 16, DH> */, CONV_FAM_WGRAD4 = 4 /* k_conv_wgrad4<NCG, 3, NWV> */ };
+// branch of a forward launch: the whole width in equal strips, the row-aligned 64-column strips, the W % 64 columns behind them;
+// of the weight gradient: which rule of wgrad_plan set DH (two k'-tile rounds: 3; one round: 6 or 4; searched over 1..3)
+enum { CONV_BR_WHOLE = 1, CONV_BR_MAIN = 2, CONV_BR_REM = 3, CONV_BR_WG_K2 = 1, CONV_BR_WG_ROWS = 2, CONV_BR_WG_SEARCH = 3 };
+struct ConvLaunchRecord {
+  int family, a0, a1, a2;          // template arguments in the order of the comments above (k_conv_wgrad: KT, NT, DH)
+  int branch, TW, FB, gx, gy, gz, lds;
+  int DH, fpg, groups, nstrips, nkg, PS, waves, gmax;      // weight gradient only (0 in a forward record)
+};
+struct ConvPlanRecord { int n; ConvLaunchRecord l[2]; };
+extern thread_local ConvPlanRecord g_conv_last_plan;
 // R-CED patch matrix (conv2d SAME as GEMM) and its adjoint; col2im needs C % 4 == 0
 void launch_im2col(const float* src, size_t row_stride, int ldc, int C, int S, int W, int kh, int kw, float* col, int ldk, size_t M,
                    hipStream_t s);

@@ -493,6 +493,49 @@ class HipEngine:
         d["cls"] = GEMM_CLASSES[d["cls"]]
         return d
 
+    def op_conv_supported(self, C_, N, S, W, fw):
+        """(conv_fwd_supported, conv_wgrad_supported) of csrc/conv.hip"""
+        rc = self.lib.rsrgan_op_conv_supported(C_, N, S, W, fw)
+        if rc < 0:
+            check(rc)
+        return bool(rc & 1), bool(rc & 2)
+
+    def op_conv_ws_floats(self, C_, R_max, S, W, fw) -> int:
+        n = self.lib.rsrgan_op_conv_ws_floats(C_, R_max, S, W, fw)
+        if n < 0:
+            check(int(n))
+        return int(n)
+
+    def op_conv_fwd(self, x, C_, F, out, N, R, S, W, fw, flip=False, bias=None, relu=False, mask=None) -> bool:
+        """x [R*S*W][ldc_in], F as the model stores the layer's filter, out [R*S*W][ldc_out]; False: not applicable (nothing ran)"""
+        rc = self.lib.rsrgan_op_conv_fwd(_ptr(x), x.stride(0), C_, _ptr(F), F.stride(0), 1 if flip else 0, _ptr(bias), 1 if relu else 0,
+                                         _ptr(mask), _ptr(out), out.stride(0), N, R, S, W, fw, self._stream())
+        if rc == 1:
+            return False
+        check(rc)
+        return True
+
+    def op_conv_wgrad(self, x, C_, d, N, dW, ws, R_max, R, S, W, fw, db=None, ws_floats=None) -> bool:
+        rc = self.lib.rsrgan_op_conv_wgrad(_ptr(x), x.stride(0), C_, _ptr(d), d.stride(0), N, _ptr(dW), dW.stride(0), _ptr(db), _ptr(ws),
+                                           ws.numel() if ws_floats is None else ws_floats, R_max, R, S, W, fw, self._stream())
+        if rc == 1:
+            return False
+        check(rc)
+        return True
+
+    def op_conv_last_plan(self) -> list:
+        """one dict per launch of the calling thread's last op_conv_fwd / op_conv_wgrad (empty: not applicable)"""
+        from ._lib import CONV_FAMILIES, CONV_FWD_BRANCHES, CONV_PLAN_FIELDS, CONV_WGRAD_BRANCHES
+        out = (C.c_int32 * 40)()
+        check(self.lib.rsrgan_op_conv_last_plan(out))
+        plans = []
+        for i in range(out[0]):
+            d = dict(zip(CONV_PLAN_FIELDS, out[1 + 19 * i:1 + 19 * (i + 1)]))
+            d["family"] = CONV_FAMILIES[d["family"]]
+            d["branch"] = (CONV_FWD_BRANCHES if d["family"] in ("fwd", "fwd4") else CONV_WGRAD_BRANCHES)[d["branch"]]
+            plans.append(d)
+        return plans
+
     def op_lstm_colsums(self, dz, cprev, ccur, db, dwi, dwf, dwo, rows, H):
         """lists of nb tensors each: dz [rows][4H], cprev / ccur [rows][H], db [>= 4H], dwi / dwf / dwo [>= H]"""
         check(self.lib.rsrgan_op_lstm_colsums(len(dz), self._table(dz), self._table(cprev), self._table(ccur), self._table(db),

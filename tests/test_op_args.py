@@ -1,4 +1,4 @@
-"""The operator test entries (rsrgan_op_gemm2, _gemm_batch, _gemm16_batch, _lstm_colsums, _colsum, _gemm_last_plan) refuse every
+"""The operator test entries (rsrgan_op_gemm2, _gemm_batch, _gemm16_batch, _lstm_colsums, _colsum, _gemm_last_plan, _conv_*) refuse every
 argument error BEFORE their first HIP call, naming it in rsrgan_last_error(): so the refusals run here, without a device.  The
 pointers are made-up addresses: a refused call never reads them."""
 import ctypes as C
@@ -152,3 +152,90 @@ def test_existing_gemm_entry_still_refuses(lib):
     refused(lib, rc, "op_gemm")
     rc = lib.rsrgan_op_gemm(P, 62, 0, P, 64, 0, P, 64, 8, 8, 8, None, 0, 0.3, 0, None)
     refused(lib, rc, "multiple of 4")
+
+
+# ---- the convolution entries (csrc/conv.hip through launch_conv_prep / launch_conv_fwd / launch_conv_wgrad)
+def conv_fwd(lib, **kw):
+    a = dict(x=P, ldc_in=8, C=8, F=P, ldf=12, flip=0, bias=None, relu=0, mask=None, out=P, ldc_out=12, N=12, R=2, S=3, W=9, fw=3)
+    a.update(kw)
+    return lib.rsrgan_op_conv_fwd(a["x"], a["ldc_in"], a["C"], a["F"], a["ldf"], a["flip"], a["bias"], a["relu"], a["mask"], a["out"],
+                                  a["ldc_out"], a["N"], a["R"], a["S"], a["W"], a["fw"], None)
+
+
+def conv_wgrad(lib, **kw):
+    a = dict(x=P, ldc_in=8, C=8, d=P, ldc_d=12, N=12, dW=P, ldw=12, db=None, ws=P, ws_floats=1 << 30, R_max=4, R=2, S=3, W=9, fw=3)
+    a.update(kw)
+    return lib.rsrgan_op_conv_wgrad(a["x"], a["ldc_in"], a["C"], a["d"], a["ldc_d"], a["N"], a["dW"], a["ldw"], a["db"], a["ws"],
+                                    a["ws_floats"], a["R_max"], a["R"], a["S"], a["W"], a["fw"], None)
+
+
+@pytest.mark.parametrize("which", ["x", "F", "out"])
+def test_conv_fwd_null_pointer(lib, which):
+    refused(lib, conv_fwd(lib, **{which: None}), "op_conv_fwd", "null pointer")
+
+
+def test_conv_fwd_refusals(lib):
+    for which in ("ldc_in", "ldc_out", "ldf"):
+        refused(lib, conv_fwd(lib, **{which: 14}), "op_conv_fwd", "leading dimension", "multiple of 4")
+    refused(lib, conv_fwd(lib, ldc_in=4), "leading dimension below its row")
+    refused(lib, conv_fwd(lib, ldc_out=8), "leading dimension below its row")
+    refused(lib, conv_fwd(lib, ldf=8), "leading dimension below its row")
+    refused(lib, conv_fwd(lib, flip=1, C=12, N=8, ldc_in=12, ldc_out=8, ldf=8), "leading dimension below its row")     # flip: F has C columns
+    refused(lib, conv_fwd(lib, bias=P + 4), "bias not 16-byte aligned")
+    refused(lib, conv_fwd(lib, mask=P + 8), "not 16-byte aligned")
+    refused(lib, conv_fwd(lib, x=P + 4), "not 16-byte aligned")
+    refused(lib, conv_fwd(lib, R=0), "R = 0")
+    refused(lib, conv_fwd(lib, R=1 << 20, S=3, W=9), "positions exceed the entry's 2^24")
+    refused(lib, conv_fwd(lib, R=-2), "R = -2")
+    for which in ("C", "N", "S", "W", "fw"):
+        refused(lib, conv_fwd(lib, **{which: 0}), "positive")
+
+
+def test_conv_fwd_unsupported_shape_is_not_applicable_without_a_device(lib):
+    """the model's rule for the patch-matrix path: nothing is launched (no HIP call: this passes without a device)"""
+    assert conv_fwd(lib, S=4) == _lib.OP_NOT_APPLICABLE
+    assert conv_fwd(lib, fw=4) == _lib.OP_NOT_APPLICABLE
+    assert conv_fwd(lib, N=33, ldc_out=36, ldf=36) == _lib.OP_NOT_APPLICABLE
+    assert conv_fwd(lib, C=24, ldc_in=24, fw=13) == _lib.OP_NOT_APPLICABLE
+    out = (C.c_int32 * 40)(*([-7] * 40))
+    assert lib.rsrgan_op_conv_last_plan(out) == 0 and list(out) == [0] * 40
+
+
+@pytest.mark.parametrize("which", ["x", "d", "dW", "ws"])
+def test_conv_wgrad_null_pointer(lib, which):
+    refused(lib, conv_wgrad(lib, **{which: None}), "op_conv_wgrad", "null pointer")
+
+
+def test_conv_wgrad_refusals(lib):
+    for which in ("ldc_in", "ldc_d", "ldw"):
+        refused(lib, conv_wgrad(lib, **{which: 18}), "op_conv_wgrad", "leading dimension", "multiple of 4")
+    refused(lib, conv_wgrad(lib, ldc_in=4), "leading dimension below its row")
+    refused(lib, conv_wgrad(lib, ldc_d=8), "leading dimension below its row")
+    refused(lib, conv_wgrad(lib, ldw=8), "leading dimension below its row")
+    refused(lib, conv_wgrad(lib, R=0), "R = 0")
+    refused(lib, conv_wgrad(lib, R=5), "R = 5", "R_max = 4")
+    refused(lib, conv_wgrad(lib, ws=P + 4), "not 16-byte aligned")
+    refused(lib, conv_wgrad(lib, dW=P + 2), "dW or db not 4-byte aligned")
+    refused(lib, conv_wgrad(lib, db=P + 1), "dW or db not 4-byte aligned")
+    refused(lib, conv_wgrad(lib, R=4, R_max=4, S=11, W=257 * 2048), "positions exceed")
+    need = lib.rsrgan_op_conv_ws_floats(8, 4, 3, 9, 3)
+    assert need > 0
+    refused(lib, conv_wgrad(lib, ws_floats=need - 1), "workspace of %d floats" % (need - 1), "R_max = 4")
+    refused(lib, conv_wgrad(lib, ws_floats=-1), "workspace")
+    refused(lib, conv_wgrad(lib, ws_floats=lib.rsrgan_op_conv_ws_floats(8, 2, 3, 9, 3) - 1, R_max=4, R=2), "workspace")
+    assert conv_wgrad(lib, S=4) == _lib.OP_NOT_APPLICABLE
+    assert conv_wgrad(lib, N=33, ldc_d=36, ldw=36) == _lib.OP_NOT_APPLICABLE
+
+
+def test_conv_supported_and_ws_floats_answer_without_a_device(lib):
+    assert lib.rsrgan_op_conv_supported(12, 16, 11, 257, 13) == 3
+    assert lib.rsrgan_op_conv_supported(1, 12, 11, 257, 13) == 3
+    assert lib.rsrgan_op_conv_supported(24, 12, 3, 9, 13) == 0          # the filter slice exceeds 5 float4 per thread
+    assert lib.rsrgan_op_conv_supported(4, 4, 4, 9, 3) == 0 and lib.rsrgan_op_conv_supported(4, 4, 3, 9, 4) == 0
+    assert lib.rsrgan_op_conv_supported(4, 33, 3, 9, 3) == 0 and lib.rsrgan_op_conv_supported(6, 4, 3, 9, 3) == 0
+    refused(lib, lib.rsrgan_op_conv_supported(4, 4, 0, 9, 3), "op_conv_supported", "positive")
+    refused(lib, int(lib.rsrgan_op_conv_ws_floats(4, 0, 3, 9, 3)), "op_conv_ws_floats", "positive")
+    # the group count is not monotonic in the frame count (S = 5, W = 257: 9 strips, gmax = 28): the size covers the worst R' <= R
+    ws = [lib.rsrgan_op_conv_ws_floats(4, R, 5, 257, 3) for R in range(1, 61)]
+    assert all(b >= a for a, b in zip(ws, ws[1:])) and ws[27] > ws[26] and ws[59] == ws[27]
+    refused(lib, lib.rsrgan_op_conv_last_plan(None), "op_conv_last_plan", "null pointer")
