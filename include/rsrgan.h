@@ -363,6 +363,37 @@ int rsrgan_op_conv_supported(int32_t C, int32_t N, int32_t S, int32_t W, int32_t
  * (the last eight: weight gradient only) */
 int rsrgan_op_conv_last_plan(int32_t out[40]);
 
+/* ---- batch_norm(renorm=True) of the frame-level nets (csrc/bn.hip).  Unit parity tests only (tests/test_gpu_bn_ops.py,
+ * tests/test_op_args.py); no trainer calls them.  Each goes through the host launch function the model calls (launch_bn_forward,
+ * launch_bn_backward, launch_bn_commit_many, launch_bn_commit) on caller-owned buffers.  vars: the layer's eight device pointers in
+ * the order beta, gamma, moving_mean, moving_variance, renorm_mean, renorm_mean_weight [1], renorm_stddev, renorm_stddev_weight [1].
+ * z, y, dy: [calls * rows][ld] (the calls are consecutive row blocks); stat: [calls][6][ldc] (mean, stddev, r, d, a, b per call;
+ * training = 0 writes rows 4 and 5 only); sums: [2][ldc]; scratch: scratch_floats floats of partial sums.  Contract of the padding
+ * columns [cols, pad4(cols)): the caller keeps them 0 in z, dy and stat (the kernels never write them in stat or sums), sums may hold
+ * any FINITE value there (it is multiplied by a = 0), y and dz come out 0 there on the sliced and narrow routes and are not written
+ * on the small route.  RSRGAN_ERR_INVALID before the first HIP call, rsrgan_last_error() naming it, for: a null required pointer (dbeta
+ * and dgamma may both be NULL, not one of them); z, y, dy, stat or sums not 16-byte aligned (moved as float4) or any other pointer not
+ * 4-byte aligned; a leading dimension that is no multiple of 4 or below pad4(cols); rows, cols or calls < 1; calls * rows above
+ * 2^30; scratch_floats < 2 * cols (one slice of partial sums: with less the kernels would write past the buffer). */
+int rsrgan_op_bn_forward(const float* z, int32_t ldz, float* y, int32_t ldy, int32_t rows, int32_t cols, int32_t calls,
+                         float* const* vars, float* stat, int32_t ldc, int32_t training, int32_t relu, float* scratch,
+                         int64_t scratch_floats, void* stream);
+/* dy: the gradient of y (after its ReLU when relu), overwritten by the gradient of z.  accumulate: add to dbeta / dgamma. */
+int rsrgan_op_bn_backward(float* dy, int32_t ldd, const float* y, int32_t ldy, const float* z, int32_t ldz, int32_t rows, int32_t cols,
+                          int32_t calls, const float* stat, int32_t ldc, float* dbeta, float* dgamma, int32_t accumulate, int32_t relu,
+                          float* sums, float* scratch, int64_t scratch_floats, void* stream);
+/* the update ops of n = 1..24 layers in one launch (launch_bn_commit_many): entry i has vars[8 * i .. 8 * i + 7], stat[i] and
+ * dims[4 * i ..] = cols, ldc, times0, times1 (statistics slot 0 applied times0 times, then slot 1 times1 times).  single != 0: n = 1
+ * and times1 = 0 through launch_bn_commit.  Refused: n outside 1..24, a null pointer, negative times, cols < 1, ldc % 4 or
+ * ldc < pad4(cols), single with n != 1 or times1 != 0. */
+int rsrgan_op_bn_commit(int32_t n, float* const* vars, const float* const* stat, const int32_t* dims, int32_t single, void* stream);
+/* what the calling thread's last rsrgan_op_bn_forward / _backward launched: out = { route (1 small: k_bn_fwd_small / k_bn_bwd_small,
+ * 2 sliced: k_bn_stats1/2 + k_bn_apply, k_bn_bwd1/2/3, 3 narrow: k_bn_part_narrow + k_bn_elem_narrow; 0: none yet), 1 if backward,
+ * calls, kernel launches of all calls, slices, rows per slice, partial-sum grid x, y, elementwise grid, q = ld / 4 and R = 256 / q
+ * (narrow only), 0.. }; with calls > 1 launched call by call the fields are those of the call launched last (forward: call 0, launched
+ * after calls 1 .. n-1; backward: call n-1) */
+int rsrgan_op_bn_last_plan(int32_t out[16]);
+
 /* ---- SEGAN-style conv G/D (models/segan.py:SEGAN with generator.py:AEGenerator, discriminator.py:discriminator, utils/bnorm.py:VBN;
  * BASELINE.json configs[4]).  The reference's trainer cannot run as shipped (segan.py:136 calls an undefined variables_on_gpu0(),
  * scripts/train_segan.py:20 imports a missing module); the graph it would build is fully specified and is what these entry

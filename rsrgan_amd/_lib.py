@@ -27,6 +27,7 @@ SYMBOLS = ["rsrgan_default_cfg", "rsrgan_create", "rsrgan_destroy", "rsrgan_last
            "rsrgan_op_gemm", "rsrgan_op_gemm2", "rsrgan_op_gemm_batch", "rsrgan_op_gemm16_batch", "rsrgan_op_gemm_last_plan",
            "rsrgan_op_lstm_colsums", "rsrgan_op_colsum", "rsrgan_version",
            "rsrgan_op_conv_fwd", "rsrgan_op_conv_wgrad", "rsrgan_op_conv_ws_floats", "rsrgan_op_conv_supported", "rsrgan_op_conv_last_plan",
+           "rsrgan_op_bn_forward", "rsrgan_op_bn_backward", "rsrgan_op_bn_commit", "rsrgan_op_bn_last_plan",
            "rsrgan_segan_default_cfg", "rsrgan_segan_create", "rsrgan_segan_destroy", "rsrgan_segan_set_scalar",
            "rsrgan_segan_num_tensors", "rsrgan_segan_tensor_info", "rsrgan_segan_param_count", "rsrgan_segan_get_params",
            "rsrgan_segan_set_params", "rsrgan_segan_forward_g", "rsrgan_segan_d_backward", "rsrgan_segan_g_backward",
@@ -117,6 +118,10 @@ def load():
     lib.rsrgan_op_conv_ws_floats.restype = i64
     lib.rsrgan_op_conv_supported.argtypes = [i32, i32, i32, i32, i32]
     lib.rsrgan_op_conv_last_plan.argtypes = [C.POINTER(i32)]
+    lib.rsrgan_op_bn_forward.argtypes = [p, i32, p, i32, i32, i32, i32, pp, p, i32, i32, i32, p, i64, vp]
+    lib.rsrgan_op_bn_backward.argtypes = [p, i32, p, i32, p, i32, i32, i32, i32, p, i32, p, p, i32, i32, p, p, i64, vp]
+    lib.rsrgan_op_bn_commit.argtypes = [i32, pp, pp, C.POINTER(i32), i32, vp]
+    lib.rsrgan_op_bn_last_plan.argtypes = [C.POINTER(i32)]
     lib.rsrgan_segan_default_cfg.argtypes = [C.POINTER(SeganCfg)]
     lib.rsrgan_segan_create.argtypes = [C.POINTER(SeganCfg), C.c_uint64, C.POINTER(vp)]
     lib.rsrgan_segan_destroy.argtypes = [vp]
@@ -149,6 +154,10 @@ CONV_FWD_BRANCHES = {1: "whole", 2: "main", 3: "rem"}
 CONV_WGRAD_BRANCHES = {1: "k2", 2: "rows", 3: "search"}
 CONV_PLAN_FIELDS = ("family", "a0", "a1", "a2", "branch", "TW", "FB", "gx", "gy", "gz", "lds", "DH", "fpg", "groups", "nstrips", "nkg",
                     "PS", "waves", "gmax")
+# rsrgan_op_bn_last_plan: routes and the fields of the record; the order of the eight variables of a layer
+BN_ROUTES = {0: "none", 1: "small", 2: "sliced", 3: "narrow"}
+BN_PLAN_FIELDS = ("route", "backward", "calls", "launches", "slices", "per", "pgx", "pgy", "egrid", "q", "R")
+BN_VARS = ("beta", "gamma", "moving_mean", "moving_variance", "renorm_mean", "renorm_mean_weight", "renorm_stddev", "renorm_stddev_weight")
 
 
 def ptr_table(ptrs):

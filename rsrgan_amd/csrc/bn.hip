@@ -487,20 +487,35 @@ static int bn_slices(int rows, int cols, size_t scratch_floats, int* per) {
   return (rows + *per - 1) / *per;
 }
 
+thread_local BnPlanRecord g_bn_last_plan = {};        // what this host thread launched last (host-only; rsrgan_op_bn_last_plan)
+static thread_local int g_bn_depth = 0;               // > 0 inside the call-by-call recursion: the record is kept, not restarted
+struct BnNested { BnNested() { ++g_bn_depth; } ~BnNested() { --g_bn_depth; } };
+static void bn_record_begin(bool backward, int calls) {
+  if (g_bn_depth == 0) { g_bn_last_plan = BnPlanRecord{}; g_bn_last_plan.backward = backward ? 1 : 0; g_bn_last_plan.calls = calls; }
+}
+static void bn_record(int route, int launches, int slices, int per, int pgx, int pgy, int egrid, int ld) {
+  BnPlanRecord& p = g_bn_last_plan;
+  p.route = route; p.launches += launches; p.slices = slices; p.per = per; p.pgx = pgx; p.pgy = pgy; p.egrid = egrid;
+  p.q = route == BN_ROUTE_NARROW ? ld >> 2 : 0; p.R = route == BN_ROUTE_NARROW ? 256 / (ld >> 2) : 0;
+}
+
 // `calls` consecutive calls of `rows` rows each (statistics slots 0 .. calls-1 of `stat`)
 void launch_bn_forward(const float* z, int ldz, float* y, int ldy, int rows, int cols, const BnVars& v, float* stat, int ldc, bool training,
                        bool relu, float* scratch, size_t scratch_floats, hipStream_t s, int calls) {
+  bn_record_begin(false, calls);
   if (rows <= switches().bn_small_rows && cols >= 64) {
     hipLaunchKernelGGL(k_bn_fwd_small, dim3((cols + BNS_CW - 1) / BNS_CW), dim3(256), 0, s, z, ldz, y, ldy, rows, cols, calls, v, stat, ldc,
                        training ? 1 : 0, relu ? 1 : 0);
+    bn_record(BN_ROUTE_SMALL, 1, 0, 0, (cols + BNS_CW - 1) / BNS_CW, 1, 0, 0);
     return;
   }
+  BnNested nested;
   for (int k = 1; k < calls; ++k)
     launch_bn_forward(z + (size_t)k * rows * ldz, ldz, y + (size_t)k * rows * ldy, ldy, rows, cols, v, stat + (size_t)k * BN_STAT_ROWS * ldc, ldc,
                       training, relu, scratch, scratch_floats, s, 1);
+  int per = 0, slices = 0;
   if (training) {
-    int per;
-    const int slices = bn_slices(rows, cols, scratch_floats, &per);
+    slices = bn_slices(rows, cols, scratch_floats, &per);
     if (bn_narrow(rows, cols, ldz, ldy, ldz))
       hipLaunchKernelGGL(k_bn_part_narrow<false>, dim3(slices), dim3(256), 0, s, z, nullptr, nullptr, nullptr, 0, ldz, rows, cols, per, 0, scratch);
     else
@@ -515,9 +530,11 @@ void launch_bn_forward(const float* z, int ldz, float* y, int ldy, int rows, int
   if (bn_narrow(rows, cols, ldz, ldy, ldz)) {
     hipLaunchKernelGGL(k_bn_elem_narrow<false>, dim3(bn_narrow_grid(rows, ldz)), dim3(256), 0, s, z, y, nullptr, stat, ldc, nullptr, ldz, rows,
                        relu ? 1 : 0);
+    bn_record(BN_ROUTE_NARROW, training ? 3 : 2, slices, per, slices, training ? 1 : 0, bn_narrow_grid(rows, ldz), ldz);
     return;
   }
   hipLaunchKernelGGL(k_bn_apply, dim3(grid), dim3(256), 0, s, z, ldz, y, ldy, (size_t)rows, cp, stat + 4 * ldc, stat + 5 * ldc, relu ? 1 : 0);
+  bn_record(BN_ROUTE_SLICED, training ? 3 : 2, slices, per, training ? (cols + 63) / 64 : 0, slices, grid, 0);
 }
 
 // dy: gradient w.r.t. y (the layer's output AFTER its ReLU when relu) -> overwritten by the gradient w.r.t. z.
@@ -525,13 +542,16 @@ void launch_bn_forward(const float* z, int ldz, float* y, int ldy, int rows, int
 void launch_bn_backward(float* dy, int ldd, const float* y, int ldy, const float* z, int ldz, int rows, int cols, const float* stat, int ldc,
                         float* dbeta, float* dgamma, bool accumulate, bool relu, float* sums, float* scratch, size_t scratch_floats,
                         hipStream_t s, int calls) {
+  bn_record_begin(true, calls);
   if (rows <= switches().bn_small_rows && cols >= 64 && !accumulate) {
     hipLaunchKernelGGL(k_bn_bwd_small, dim3((cols + BNS_CW - 1) / BNS_CW), dim3(256), 0, s, dy, ldd, y, ldy, z, ldz, rows, cols, calls, stat, ldc, dbeta,
                        dgamma, relu ? 1 : 0);
+    bn_record(BN_ROUTE_SMALL, 1, 0, 0, (cols + BNS_CW - 1) / BNS_CW, 1, 0, 0);
     return;
   }
   // (call 0 assigns dbeta / dgamma, the later calls accumulate: the order of the small path)
   if (calls > 1) {
+    BnNested nested;
     launch_bn_backward(dy, ldd, y, ldy, z, ldz, rows, cols, stat, ldc, dbeta, dgamma, accumulate, relu, sums, scratch, scratch_floats, s, 1);
     for (int k = 1; k < calls; ++k)
       launch_bn_backward(dy + (size_t)k * rows * ldd, ldd, y + (size_t)k * rows * ldy, ldy, z + (size_t)k * rows * ldz, ldz, rows, cols,
@@ -553,9 +573,11 @@ void launch_bn_backward(float* dy, int ldd, const float* y, int ldy, const float
   const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
   if (narrow) {
     hipLaunchKernelGGL(k_bn_elem_narrow<true>, dim3(bn_narrow_grid(rows, ldz)), dim3(256), 0, s, z, dy, y, stat, ldc, sums, ldz, rows, relu ? 1 : 0);
+    bn_record(BN_ROUTE_NARROW, 3, slices, per, slices, 1, bn_narrow_grid(rows, ldz), ldz);
     return;
   }
   hipLaunchKernelGGL(k_bn_bwd3, dim3(grid), dim3(256), 0, s, dy, ldd, y, ldy, z, ldz, stat, ldc, sums, (size_t)rows, cp, relu ? 1 : 0);
+  bn_record(BN_ROUTE_SLICED, 3, slices, per, (cols + 63) / 64, slices, grid, 0);
 }
 
 void launch_bn_commit(int cols, const BnVars& v, const float* stat, int ldc, int times, hipStream_t s) {

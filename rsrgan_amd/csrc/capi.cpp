@@ -740,4 +740,77 @@ int rsrgan_op_conv_last_plan(int32_t out[40]) {
   return RSRGAN_OK;
 }
 
+// ---- batch_norm(renorm=True) (bn.hip) through the launch functions Model::dnn_forward / rced_forward and their backward passes call
+static bool op_bn_vars(float* const* vars, BnVars& v) {
+  for (int i = 0; i < 8; ++i) if (!vars[i] || ((size_t)vars[i] & 3)) return false;
+  v = BnVars{vars[0], vars[1], vars[2], vars[3], vars[4], vars[5], vars[6], vars[7]};
+  return true;
+}
+#define OP_BN_SHAPE(who, l0, l1, l2) \
+  OP_REFUSE(rows < 1 || cols < 1 || calls < 1, who ": rows, cols, calls must be positive (got %d, %d, %d)", rows, cols, calls); \
+  OP_REFUSE((long long)rows * calls > (1 << 30), who ": calls x rows = %lld above the entry's 2^30", (long long)rows * calls); \
+  OP_REFUSE((l0 & 3) || (l1 & 3) || (l2 & 3) || (ldc & 3), who ": leading dimension not a multiple of 4 (%d, %d, %d, ldc %d)", l0, l1, l2, ldc); \
+  OP_REFUSE(l0 < op_pad4(cols) || l1 < op_pad4(cols) || l2 < op_pad4(cols) || ldc < op_pad4(cols), \
+            who ": leading dimension below its padded row of %d (%d, %d, %d, ldc %d)", op_pad4(cols), l0, l1, l2, ldc); \
+  OP_REFUSE(scratch_floats < 2 * (int64_t)cols, who ": scratch of %lld floats below the 2 x cols = %d of one slice of partial sums", \
+            (long long)scratch_floats, 2 * cols)
+
+int rsrgan_op_bn_forward(const float* z, int32_t ldz, float* y, int32_t ldy, int32_t rows, int32_t cols, int32_t calls, float* const* vars,
+                         float* stat, int32_t ldc, int32_t training, int32_t relu, float* scratch, int64_t scratch_floats, void* stream) {
+  OP_REFUSE(!z || !y || !vars || !stat || !scratch, "op_bn_forward: null pointer (z, y, vars, stat or scratch)");
+  OP_BN_SHAPE("op_bn_forward", ldz, ldy, ldz);
+  OP_REFUSE(((size_t)z & 15) || ((size_t)y & 15) || ((size_t)stat & 15), "op_bn_forward: z, y or stat not 16-byte aligned");
+  OP_REFUSE((size_t)scratch & 3, "op_bn_forward: scratch not 4-byte aligned");
+  BnVars v;
+  OP_REFUSE(!op_bn_vars(vars, v), "op_bn_forward: a null or misaligned pointer among the eight variables");
+  launch_bn_forward(z, ldz, y, ldy, rows, cols, v, stat, ldc, training != 0, relu != 0, scratch, (size_t)scratch_floats, (hipStream_t)stream, calls);
+  if (hipGetLastError() != hipSuccess) { set_error("op_bn_forward launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
+
+int rsrgan_op_bn_backward(float* dy, int32_t ldd, const float* y, int32_t ldy, const float* z, int32_t ldz, int32_t rows, int32_t cols,
+                          int32_t calls, const float* stat, int32_t ldc, float* dbeta, float* dgamma, int32_t accumulate, int32_t relu,
+                          float* sums, float* scratch, int64_t scratch_floats, void* stream) {
+  OP_REFUSE(!dy || !y || !z || !stat || !sums || !scratch, "op_bn_backward: null pointer (dy, y, z, stat, sums or scratch)");
+  OP_REFUSE((dbeta == nullptr) != (dgamma == nullptr), "op_bn_backward: dbeta and dgamma must both be given or both be null");
+  OP_BN_SHAPE("op_bn_backward", ldd, ldy, ldz);
+  OP_REFUSE(((size_t)dy & 15) || ((size_t)y & 15) || ((size_t)z & 15) || ((size_t)stat & 15) || ((size_t)sums & 15),
+            "op_bn_backward: dy, y, z, stat or sums not 16-byte aligned");
+  OP_REFUSE(((size_t)scratch & 3) || ((size_t)dbeta & 3) || ((size_t)dgamma & 3), "op_bn_backward: scratch, dbeta or dgamma not 4-byte aligned");
+  launch_bn_backward(dy, ldd, y, ldy, z, ldz, rows, cols, stat, ldc, dbeta, dgamma, accumulate != 0, relu != 0, sums, scratch,
+                     (size_t)scratch_floats, (hipStream_t)stream, calls);
+  if (hipGetLastError() != hipSuccess) { set_error("op_bn_backward launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
+
+int rsrgan_op_bn_commit(int32_t n, float* const* vars, const float* const* stat, const int32_t* dims, int32_t single, void* stream) {
+  OP_REFUSE(n < 1 || n > 24, "op_bn_commit: n = %d outside the list (1 .. 24)", n);
+  OP_REFUSE(!vars || !stat || !dims, "op_bn_commit: null pointer table (vars, stat or dims)");
+  BnCommitList cl;
+  cl.n = n;
+  for (int i = 0; i < n; ++i) {
+    const int cols = dims[4 * i], ldc = dims[4 * i + 1], t0 = dims[4 * i + 2], t1 = dims[4 * i + 3];
+    BnCommit& e = cl.e[i];
+    OP_REFUSE(!op_bn_vars(vars + 8 * i, e.v), "op_bn_commit: a null or misaligned pointer among the variables of entry %d", i);
+    OP_REFUSE(!stat[i] || ((size_t)stat[i] & 3), "op_bn_commit: null or misaligned stat of entry %d", i);
+    OP_REFUSE(cols < 1, "op_bn_commit: cols = %d in entry %d", cols, i);
+    OP_REFUSE((ldc & 3) || ldc < op_pad4(cols), "op_bn_commit: ldc = %d of entry %d is no multiple of 4 or below its padded row of %d", ldc, i, op_pad4(cols));
+    OP_REFUSE(t0 < 0 || t1 < 0, "op_bn_commit: negative times (%d, %d) in entry %d", t0, t1, i);
+    e.stat = stat[i]; e.cols = cols; e.ldc = ldc; e.times0 = t0; e.times1 = t1;
+  }
+  OP_REFUSE(single && (n != 1 || cl.e[0].times1 != 0), "op_bn_commit: the single-entry form takes n = 1 and times1 = 0");
+  if (single) launch_bn_commit(cl.e[0].cols, cl.e[0].v, cl.e[0].stat, cl.e[0].ldc, cl.e[0].times0, (hipStream_t)stream);
+  else launch_bn_commit_many(cl, (hipStream_t)stream);
+  if (hipGetLastError() != hipSuccess) { set_error("op_bn_commit launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
+
+int rsrgan_op_bn_last_plan(int32_t out[16]) {
+  OP_REFUSE(!out, "op_bn_last_plan: null pointer");
+  const BnPlanRecord& p = g_bn_last_plan;
+  const int v[11] = {p.route, p.backward, p.calls, p.launches, p.slices, p.per, p.pgx, p.pgy, p.egrid, p.q, p.R};
+  for (int i = 0; i < 16; ++i) out[i] = i < 11 ? v[i] : 0;
+  return RSRGAN_OK;
+}
+
 }  // extern "C"

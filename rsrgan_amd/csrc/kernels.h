@@ -424,6 +424,14 @@ void launch_bn_commit(int cols, const BnVars& v, const float* stat, int ldc, int
 struct BnCommit { BnVars v; const float* stat; int cols, ldc, times0, times1; };   // update ops: call 0 x times0, then call 1 x times1
 struct BnCommitList { int n; BnCommit e[24]; };
 void launch_bn_commit_many(const BnCommitList& cl, hipStream_t s);
+// What this host thread's last launch_bn_forward / launch_bn_backward launched (host stores only; rsrgan_op_bn_last_plan).  With
+// calls > 1 on the route that launches call by call, the fields are those of the call launched last (forward: call 0, which
+// follows calls 1 .. n-1; backward: call n-1; all calls share one shape) and `launches` counts the kernels of all calls.  pgx x pgy: the grid of the partial-sum kernel (k_bn_stats1 / k_bn_bwd1: column blocks x slices;
+// k_bn_part_narrow: slices x 1; small route: the single launch's grid; training = false: 0 x 0, no partial sums);
+// egrid: the grid of k_bn_apply / k_bn_bwd3 / k_bn_elem_narrow (0 on the small route); q, R: quads per row and rows per pass (narrow).
+enum { BN_ROUTE_NONE = 0, BN_ROUTE_SMALL = 1, BN_ROUTE_SLICED = 2, BN_ROUTE_NARROW = 3 };
+struct BnPlanRecord { int route, backward, calls, launches, slices, per, pgx, pgy, egrid, q, R; };
+extern thread_local BnPlanRecord g_bn_last_plan;
 void launch_colsum(const float* a, int lda, const float* b, int ldb, float* out, int rows, int cols,
                    float* scratch /* >= 64*cols floats */, hipStream_t s);
 

@@ -536,6 +536,35 @@ class HipEngine:
             plans.append(d)
         return plans
 
+    def op_bn_forward(self, z, y, rows, cols, bn_vars, stat, scratch, calls=1, training=True, relu=True, scratch_floats=None):
+        """z, y [calls * rows][ld]; bn_vars: the eight tensors in _lib.BN_VARS order; stat [calls * 6][ldc]"""
+        check(self.lib.rsrgan_op_bn_forward(_ptr(z), z.stride(0), _ptr(y), y.stride(0), rows, cols, calls, self._table(bn_vars), _ptr(stat),
+                                            stat.stride(0), 1 if training else 0, 1 if relu else 0, _ptr(scratch),
+                                            scratch.numel() if scratch_floats is None else scratch_floats, self._stream()))
+
+    def op_bn_backward(self, dy, y, z, rows, cols, stat, sums, scratch, dbeta=None, dgamma=None, calls=1, accumulate=False, relu=True,
+                       scratch_floats=None):
+        """dy [calls * rows][ldd] is overwritten by dz; sums [2][ldc]"""
+        check(self.lib.rsrgan_op_bn_backward(_ptr(dy), dy.stride(0), _ptr(y), y.stride(0), _ptr(z), z.stride(0), rows, cols, calls, _ptr(stat),
+                                             stat.stride(0), _ptr(dbeta), _ptr(dgamma), 1 if accumulate else 0, 1 if relu else 0, _ptr(sums),
+                                             _ptr(scratch), scratch.numel() if scratch_floats is None else scratch_floats, self._stream()))
+
+    def op_bn_commit(self, entries, single=False):
+        """entries: (bn_vars, stat, cols, times0, times1) per layer; single: k_bn_commit instead of k_bn_commit_many"""
+        dims = []
+        for _, st, cols, t0, t1 in entries:
+            dims += [cols, st.stride(0), t0, t1]
+        check(self.lib.rsrgan_op_bn_commit(len(entries), self._table([t for e in entries for t in e[0]]), self._table([e[1] for e in entries]),
+                                           (C.c_int32 * len(dims))(*dims), 1 if single else 0, self._stream()))
+
+    def op_bn_last_plan(self) -> dict:
+        from ._lib import BN_PLAN_FIELDS, BN_ROUTES
+        out = (C.c_int32 * 16)()
+        check(self.lib.rsrgan_op_bn_last_plan(out))
+        d = dict(zip(BN_PLAN_FIELDS, list(out)))
+        d["route"] = BN_ROUTES[d["route"]]
+        return d
+
     def op_lstm_colsums(self, dz, cprev, ccur, db, dwi, dwf, dwo, rows, H):
         """lists of nb tensors each: dz [rows][4H], cprev / ccur [rows][H], db [>= 4H], dwi / dwf / dwo [>= H]"""
         check(self.lib.rsrgan_op_lstm_colsums(len(dz), self._table(dz), self._table(cprev), self._table(ccur), self._table(db),

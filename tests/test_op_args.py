@@ -1,4 +1,4 @@
-"""The operator test entries (rsrgan_op_gemm2, _gemm_batch, _gemm16_batch, _lstm_colsums, _colsum, _gemm_last_plan, _conv_*) refuse every
+"""The operator test entries (rsrgan_op_gemm2, _gemm_batch, _gemm16_batch, _lstm_colsums, _colsum, _gemm_last_plan, _conv_*, _bn_*) refuse every
 argument error BEFORE their first HIP call, naming it in rsrgan_last_error(): so the refusals run here, without a device.  The
 pointers are made-up addresses: a refused call never reads them."""
 import ctypes as C
@@ -239,3 +239,106 @@ def test_conv_supported_and_ws_floats_answer_without_a_device(lib):
     ws = [lib.rsrgan_op_conv_ws_floats(4, R, 5, 257, 3) for R in range(1, 61)]
     assert all(b >= a for a, b in zip(ws, ws[1:])) and ws[27] > ws[26] and ws[59] == ws[27]
     refused(lib, lib.rsrgan_op_conv_last_plan(None), "op_conv_last_plan", "null pointer")
+
+
+# ---- the batch-renorm entries (csrc/bn.hip through launch_bn_forward / launch_bn_backward / launch_bn_commit_many / launch_bn_commit)
+def bn_vars(null_at=None, odd_at=None, n=1):
+    return _lib.ptr_table([None if i == null_at else P + 4096 * i + (2 if i == odd_at else 0) for i in range(8 * n)])
+
+
+def bn_fwd(lib, **kw):
+    a = dict(z=P, ldz=68, y=P, ldy=72, rows=16, cols=65, calls=1, vars=bn_vars(), stat=P, ldc=68, training=1, relu=1, scratch=P,
+             scratch_floats=130)
+    a.update(kw)
+    return lib.rsrgan_op_bn_forward(a["z"], a["ldz"], a["y"], a["ldy"], a["rows"], a["cols"], a["calls"], a["vars"], a["stat"], a["ldc"],
+                                    a["training"], a["relu"], a["scratch"], a["scratch_floats"], None)
+
+
+def bn_bwd(lib, **kw):
+    a = dict(dy=P, ldd=76, y=P, ldy=72, z=P, ldz=68, rows=16, cols=65, calls=1, stat=P, ldc=68, dbeta=P, dgamma=P, acc=0, relu=1, sums=P,
+             scratch=P, scratch_floats=130)
+    a.update(kw)
+    return lib.rsrgan_op_bn_backward(a["dy"], a["ldd"], a["y"], a["ldy"], a["z"], a["ldz"], a["rows"], a["cols"], a["calls"], a["stat"],
+                                     a["ldc"], a["dbeta"], a["dgamma"], a["acc"], a["relu"], a["sums"], a["scratch"], a["scratch_floats"], None)
+
+
+def bn_commit(lib, n=1, vars="t", stat="t", dims=None, single=0):
+    m = max(n, 1)
+    d = [65, 68, 1, 0] * m if dims is None else dims
+    return lib.rsrgan_op_bn_commit(n, bn_vars(n=m) if isinstance(vars, str) else vars, tab(m) if isinstance(stat, str) else stat,
+                                   (C.c_int32 * len(d))(*d), single, None)
+
+
+@pytest.mark.parametrize("which", ["z", "y", "vars", "stat", "scratch"])
+def test_bn_forward_null_pointer(lib, which):
+    refused(lib, bn_fwd(lib, **{which: None}), "op_bn_forward", "null pointer")
+
+
+def test_bn_forward_refusals(lib):
+    for which in ("ldz", "ldy", "ldc"):
+        refused(lib, bn_fwd(lib, **{which: 70}), "op_bn_forward", "leading dimension", "multiple of 4")
+        refused(lib, bn_fwd(lib, **{which: 64}), "leading dimension below its padded row of 68")
+    for which in ("rows", "cols", "calls"):
+        refused(lib, bn_fwd(lib, **{which: 0}), "positive")
+        refused(lib, bn_fwd(lib, **{which: -3}), "positive")
+    refused(lib, bn_fwd(lib, rows=1 << 20, calls=1 << 11), "above the entry's 2^30")
+    # one slice of partial sums is 2 x cols floats: bn_slices answers 1 slice for anything less and the kernels would write past it
+    refused(lib, bn_fwd(lib, scratch_floats=129), "scratch of 129 floats", "2 x cols = 130")
+    refused(lib, bn_fwd(lib, scratch_floats=0), "scratch of 0 floats")
+    refused(lib, bn_fwd(lib, scratch_floats=-1), "scratch")
+    refused(lib, bn_fwd(lib, training=0, scratch_floats=129), "scratch")            # (the same rule without partial sums: one contract)
+    for which in ("z", "y", "stat"):
+        refused(lib, bn_fwd(lib, **{which: P + 4}), "not 16-byte aligned")
+    refused(lib, bn_fwd(lib, scratch=P + 2), "scratch not 4-byte aligned")
+    for i in range(8):
+        refused(lib, bn_fwd(lib, vars=bn_vars(null_at=i)), "op_bn_forward", "eight variables")
+        refused(lib, bn_fwd(lib, vars=bn_vars(odd_at=i)), "eight variables")
+
+
+@pytest.mark.parametrize("which", ["dy", "y", "z", "stat", "sums", "scratch"])
+def test_bn_backward_null_pointer(lib, which):
+    refused(lib, bn_bwd(lib, **{which: None}), "op_bn_backward", "null pointer")
+
+
+def test_bn_backward_refusals(lib):
+    refused(lib, bn_bwd(lib, dbeta=None), "dbeta and dgamma")
+    refused(lib, bn_bwd(lib, dgamma=None), "dbeta and dgamma")
+    for which in ("ldd", "ldy", "ldz", "ldc"):
+        refused(lib, bn_bwd(lib, **{which: 74}), "op_bn_backward", "leading dimension", "multiple of 4")
+        refused(lib, bn_bwd(lib, **{which: 64}), "leading dimension below its padded row of 68")
+    for which in ("rows", "cols", "calls"):
+        refused(lib, bn_bwd(lib, **{which: 0}), "positive")
+    refused(lib, bn_bwd(lib, scratch_floats=129), "scratch of 129 floats", "2 x cols = 130")
+    refused(lib, bn_bwd(lib, acc=1, scratch_floats=64), "scratch of 64 floats")
+    for which in ("dy", "y", "z", "stat", "sums"):
+        refused(lib, bn_bwd(lib, **{which: P + 8}), "not 16-byte aligned")
+    for which in ("scratch", "dbeta", "dgamma"):
+        refused(lib, bn_bwd(lib, **{which: P + 1}), "not 4-byte aligned")
+
+
+def test_bn_commit_refusals(lib):
+    for n in (0, 25, -1):
+        refused(lib, bn_commit(lib, n=n), "op_bn_commit", "n = %d" % n, "1 .. 24")
+    refused(lib, bn_commit(lib, vars=None), "null pointer table")
+    refused(lib, bn_commit(lib, stat=None), "null pointer table")
+    refused(lib, lib.rsrgan_op_bn_commit(1, bn_vars(), tab(1), None, 0, None), "null pointer table")
+    refused(lib, bn_commit(lib, n=3, vars=bn_vars(null_at=8 * 2 + 5, n=3)), "variables of entry 2")
+    refused(lib, bn_commit(lib, n=2, stat=tab(2, null_at=1)), "stat of entry 1")
+    refused(lib, bn_commit(lib, dims=[65, 68, -1, 0]), "negative times (-1, 0) in entry 0")
+    refused(lib, bn_commit(lib, n=2, dims=[65, 68, 1, 0, 65, 68, 2, -2]), "negative times (2, -2) in entry 1")
+    refused(lib, bn_commit(lib, dims=[0, 68, 1, 0]), "cols = 0")
+    refused(lib, bn_commit(lib, dims=[65, 64, 1, 0]), "ldc = 64")
+    refused(lib, bn_commit(lib, dims=[65, 70, 1, 0]), "ldc = 70")
+    refused(lib, bn_commit(lib, n=2, single=1), "single-entry form")
+    refused(lib, bn_commit(lib, dims=[65, 68, 1, 1], single=1), "single-entry form")
+
+
+def test_bn_last_plan_null_and_initial_record(lib):
+    refused(lib, lib.rsrgan_op_bn_last_plan(None), "op_bn_last_plan", "null pointer")
+    out = (C.c_int32 * 16)(*([-7] * 16))
+    assert lib.rsrgan_op_bn_last_plan(out) == 0
+    # (the record is per thread and outlives a test: all zero in a fresh process, the last launch's plan after tests/test_gpu_bn_ops.py)
+    assert out[0] in _lib.BN_ROUTES and all(v >= 0 for v in out) and list(out[11:]) == [0] * 5
+    refused(lib, bn_fwd(lib, rows=0), "positive")
+    again = (C.c_int32 * 16)(*([-7] * 16))
+    assert lib.rsrgan_op_bn_last_plan(again) == 0 and list(again) == list(out)   # a refused call launches nothing and records nothing
