@@ -120,6 +120,19 @@ enum {
                                   g_loss = mse_lambda*g_mse + g_l2, no discriminator pass; rsrgan_d_step is an error */
   RSRGAN_FLAG_OVERLAP = 4,     /* weight-gradient GEMMs on a side stream, chunked over time, concurrent with the backward
                                   wave (measured SLOWER on MI355X: 12.77 vs 12.20 ms/step; off by default) */
+  RSRGAN_FLAG_INFER = 64,      /* GAN_RNN(..., infer=True) (models/gan_rnn_placeholder.py:133-135): a generator-only, forward-only handle.  No
+                                  discriminator (RSRGAN_NET_D's tensor table is empty), no gradients, optimizer moments or EMA shadows, no
+                                  BPTT stash: the recurrent state buffers hold min(max_frames, 64) + 1 steps and the persistent forward
+                                  launches run without their stash stores (csrc/gpersist.hip LEAN), a batch longer than one launch as
+                                  consecutive launches that carry the state.  RSRGAN_NET_G's tensor table is the training handle's (names,
+                                  order, offsets), so a checkpoint loads.  For the sequence generators lstm, res_lstm_l, res_lstm_base,
+                                  res_lstm_i (with RSRGAN_FLAG_SUPERVISED, as always) and the unprojected stack; dnn, rced and bnlstm:
+                                  RSRGAN_ERR_INVALID ("not built").  Work: rsrgan_forward_g, rsrgan_forward_g_stream, rsrgan_g_state_*,
+                                  rsrgan_set_params / rsrgan_get_params with what = 0 on RSRGAN_NET_G, the tensor-table calls,
+                                  rsrgan_device_status, rsrgan_device_bytes, the profile counters, rsrgan_destroy.  Refused before the first
+                                  HIP call, rsrgan_last_error() naming the inference-only handle: rsrgan_d_step, rsrgan_g_step,
+                                  rsrgan_*_backward, rsrgan_apply, rsrgan_grad_buffer, rsrgan_grad_bucket_*, rsrgan_get_grads and
+                                  rsrgan_set_dropout with RSRGAN_ERR_STATE, get / set_params with what = 1, 2, 3 with RSRGAN_ERR_INVALID. */
   RSRGAN_FLAG_BATCH_NORM = 32  /* args.batch_norm (run_gan_dnn.sh:134, run_dnn.sh:134): the hidden fully_connected layers of the
                                   frame-level generator (models/dnn.py:56-61) and of discriminator_dnn (:36-41) are
                                   relu(batch_norm(x.W, is_training = !cross_validation, scale=True, renorm=True)) without biases;
@@ -265,6 +278,11 @@ int rsrgan_profile_read_kind(rsrgan_handle h, int32_t kind, int32_t* launches, d
  * away after rsrgan_create, which asks the device how many it can hold: csrc/gpersist.hip resident_probe): the handle re-arms its
  * hand-off rings and takes the launch-per-phase path for that recurrence from then on.  Nothing in the reference corresponds to this. */
 int rsrgan_device_status(rsrgan_handle h, int32_t* code);
+
+/* The device memory this handle owns, in bytes: the sum of its device allocations (parameters, activations and stashes, workspaces,
+ * hand-off rings, control blocks, chunk tables).  Works on every handle; hipMemGetInfo is device-wide and says nothing about one
+ * handle on a shared device. */
+int rsrgan_device_bytes(rsrgan_handle h, int64_t* bytes);
 
 /* tf.nn.dropout(h, keep_prob) after every hidden ReLU of the frame-level nets (models/dnn.py:86,99,116-121 and
  * models/discriminator_dnn.py:68,81,100-105; `--keep_prob` of scripts/train_gan_dnn.py).  0 < keep_prob <= 1.  As in the

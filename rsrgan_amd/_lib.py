@@ -9,6 +9,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "librsrgan_hip.so")
 
 G_TYPES = {"lstm": 0, "res_lstm_l": 1, "res_lstm_base": 2, "dnn": 3, "rced": 4, "bnlstm": 5, "res_lstm_i": 6}
 FLAG_BATCH_NORM = 32          # include/rsrgan.h RSRGAN_FLAG_BATCH_NORM
+FLAG_INFER = 64               # include/rsrgan.h RSRGAN_FLAG_INFER: a generator-only, forward-only handle
 D_TYPES = {"lstm": 0, "dnn": 1}
 NET_G, NET_D = 0, 1
 SCALARS = {"g_learning_rate": 0, "d_learning_rate": 1, "mse_lambda": 2, "d_real": 3, "d_fake": 4,
@@ -23,7 +24,7 @@ SYMBOLS = ["rsrgan_default_cfg", "rsrgan_create", "rsrgan_destroy", "rsrgan_last
            "rsrgan_d_step",
            "rsrgan_g_step", "rsrgan_d_backward", "rsrgan_g_backward", "rsrgan_apply", "rsrgan_grad_buffer",
            "rsrgan_grad_bucket_count", "rsrgan_grad_bucket_info", "rsrgan_grad_bucket_wait",
-           "rsrgan_profile_begin", "rsrgan_profile_read", "rsrgan_profile_read_kind", "rsrgan_profile_launches", "rsrgan_op_launch_floor", "rsrgan_device_status", "rsrgan_set_dropout",
+           "rsrgan_profile_begin", "rsrgan_profile_read", "rsrgan_profile_read_kind", "rsrgan_profile_launches", "rsrgan_op_launch_floor", "rsrgan_device_status", "rsrgan_device_bytes", "rsrgan_set_dropout",
            "rsrgan_op_gemm", "rsrgan_op_gemm2", "rsrgan_op_gemm_batch", "rsrgan_op_gemm16_batch", "rsrgan_op_gemm_last_plan",
            "rsrgan_op_lstm_colsums", "rsrgan_op_colsum", "rsrgan_version",
            "rsrgan_op_conv_fwd", "rsrgan_op_conv_wgrad", "rsrgan_op_conv_ws_floats", "rsrgan_op_conv_supported", "rsrgan_op_conv_last_plan",
@@ -101,6 +102,7 @@ def load():
     lib.rsrgan_profile_read.argtypes = [vp, C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.rsrgan_profile_read_kind.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.rsrgan_device_status.argtypes = [vp, C.POINTER(i32)]
+    lib.rsrgan_device_bytes.argtypes = [vp, C.POINTER(i64)]
     lib.rsrgan_set_dropout.argtypes = [vp, f32, C.c_uint64]
     lib.rsrgan_profile_launches.argtypes = [vp, C.POINTER(i64)]
     lib.rsrgan_op_launch_floor.argtypes = [i32, i32, C.POINTER(C.c_double), vp]

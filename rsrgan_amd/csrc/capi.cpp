@@ -13,6 +13,11 @@ struct rsrgan_handle_s { Model m; };
 #define CHECK_H(h)                                                    \
   if (!(h)) { set_error("null handle"); return RSRGAN_ERR_INVALID; }
 
+// An inference-only handle (RSRGAN_FLAG_INFER) has no discriminator, no gradients and no optimizer state: what needs them is refused
+// before the first HIP call.
+#define REFUSE_INFER(h, what, rc)                                                                                   \
+  if ((h)->m.infer()) { set_error("%s: the handle is inference-only (RSRGAN_FLAG_INFER)", what); return rc; }
+
 // Nothing may throw across the C ABI (include/rsrgan.h): every entry point that can allocate host memory runs its body
 // through guard(), which turns std::bad_alloc / any other exception into RSRGAN_ERR_INVALID with a message.
 template <class F>
@@ -186,6 +191,8 @@ static int copy_params(rsrgan_handle h, int net, int what, float* dense, bool to
   CHECK_H(h);
   ParamSet* p = pset(h, net);
   if (!p || !dense) { set_error("bad net / null pointer"); return RSRGAN_ERR_INVALID; }
+  if (what >= 1 && what <= 3) REFUSE_INFER(h, "rsrgan_get_params / rsrgan_set_params with what = 1, 2, 3 (optimizer moments, EMA shadows)", RSRGAN_ERR_INVALID);
+  if (what == 4) REFUSE_INFER(h, "rsrgan_get_grads", RSRGAN_ERR_STATE);
   float* buf = which_buf(p, what);
   if (!buf) { set_error("buffer %d not present for net %d", what, net); return RSRGAN_ERR_INVALID; }
   StreamScope sc(h->m, stream);
@@ -222,6 +229,7 @@ int rsrgan_forward_g(rsrgan_handle h, const float* x, const int32_t* lengths, in
     if (rc) return rc;
     m.bn_eval_call = false;     // the graph of THIS model: is_training unless it was built with cross_validation
     m.g_forward(T, s);
+    if (m.inf_failed) { m.inf_failed = false; return RSRGAN_ERR_HIP; }
     m.g_fwd_valid = false;      // labels were not packed: the stash is not a valid training forward
     launch_unpack_bm(m.y_tm, m.ldDout, y, m.B, T, m.Dout, s, m.Bt);      // (the caller's Bt rows of a padded model)
     if (hipGetLastError() != hipSuccess) { set_error("kernel launch failed in forward_g"); return RSRGAN_ERR_HIP; }
@@ -285,9 +293,11 @@ int rsrgan_forward_g_stream(rsrgan_handle h, const float* x, const int32_t* leng
     m.gstate_xfer(0, 0, m.B, nullptr, s);           // slot 0 of every layer's c / mst <- the carried state (padding rows: zeros)
     struct Carry { Model& m; explicit Carry(Model& m_) : m(m_) { m.g_carry = true; } ~Carry() { m.g_carry = false; } };
     { Carry on(m); m.g_forward(T, s); }
+    if (m.inf_failed) { m.inf_failed = false; return RSRGAN_ERR_HIP; }
     m.g_fwd_valid = false;
     // a row past its length copies its state through, so slot T holds every row's state after its lengths[b] frames
-    m.gstate_xfer(1, T, m.Bt, nullptr, s);
+    // (an inference handle: the slot its last window left it in, Model::infer_forward)
+    m.gstate_xfer(1, m.infer() ? m.inf_slot : T, m.Bt, nullptr, s);
     launch_unpack_bm(m.y_tm, m.ldDout, y, m.B, T, m.Dout, s, m.Bt);
     if (hipGetLastError() != hipSuccess) { set_error("kernel launch failed in forward_g_stream"); return RSRGAN_ERR_HIP; }
     return RSRGAN_OK;
@@ -297,6 +307,7 @@ int rsrgan_forward_g_stream(rsrgan_handle h, const float* x, const int32_t* leng
 int rsrgan_d_backward(rsrgan_handle h, const float* x, const float* labels, const int32_t* lengths, int32_t T,
                       const float* nr, const float* nf, float* out_losses, void* stream) {
   CHECK_H(h);
+  REFUSE_INFER(h, "rsrgan_d_backward", RSRGAN_ERR_STATE);
   return guard("rsrgan_d_backward", [&]() -> int {
     StreamScope sc(h->m, stream);
     return h->m.d_backward(x, labels, lengths, T, nr, nf, out_losses, true, sc.work);
@@ -305,6 +316,7 @@ int rsrgan_d_backward(rsrgan_handle h, const float* x, const float* labels, cons
 int rsrgan_g_backward(rsrgan_handle h, const float* x, const float* labels, const int32_t* lengths, int32_t T,
                       const float* nf, float* out_losses, int32_t reuse, void* stream) {
   CHECK_H(h);
+  REFUSE_INFER(h, "rsrgan_g_backward", RSRGAN_ERR_STATE);
   return guard("rsrgan_g_backward", [&]() -> int {
     StreamScope sc(h->m, stream);
     return h->m.g_backward(x, labels, lengths, T, nf, out_losses, true, reuse != 0, sc.work);
@@ -312,6 +324,7 @@ int rsrgan_g_backward(rsrgan_handle h, const float* x, const float* labels, cons
 }
 int rsrgan_apply(rsrgan_handle h, int32_t net, void* stream) {
   CHECK_H(h);
+  REFUSE_INFER(h, "rsrgan_apply", RSRGAN_ERR_STATE);
   return guard("rsrgan_apply", [&]() -> int {
     StreamScope sc(h->m, stream);
     return h->m.apply(net, sc.work);
@@ -321,6 +334,7 @@ int rsrgan_apply(rsrgan_handle h, int32_t net, void* stream) {
 int rsrgan_d_step(rsrgan_handle h, const float* x, const float* labels, const int32_t* lengths, int32_t T,
                   const float* nr, const float* nf, float* out_losses, int32_t train, void* stream) {
   CHECK_H(h);
+  REFUSE_INFER(h, "rsrgan_d_step", RSRGAN_ERR_STATE);
   return guard("rsrgan_d_step", [&]() -> int {
     StreamScope sc(h->m, stream);
     struct Fused { Model& m; Fused(Model& m_, bool on) : m(m_) { m.fused_apply = on; } ~Fused() { m.fused_apply = false; m.apply_inlined = 0; } } fused(h->m, train != 0);
@@ -332,6 +346,7 @@ int rsrgan_d_step(rsrgan_handle h, const float* x, const float* labels, const in
 int rsrgan_g_step(rsrgan_handle h, const float* x, const float* labels, const int32_t* lengths, int32_t T,
                   const float* nf, float* out_losses, int32_t train, int32_t reuse, void* stream) {
   CHECK_H(h);
+  REFUSE_INFER(h, "rsrgan_g_step", RSRGAN_ERR_STATE);
   return guard("rsrgan_g_step", [&]() -> int {
     StreamScope sc(h->m, stream);
     struct Fused { Model& m; Fused(Model& m_, bool on) : m(m_) { m.fused_apply = on; } ~Fused() { m.fused_apply = false; m.apply_inlined = 0; } } fused(h->m, train != 0);
@@ -343,6 +358,7 @@ int rsrgan_g_step(rsrgan_handle h, const float* x, const float* labels, const in
 
 int rsrgan_grad_buffer(rsrgan_handle h, int32_t net, float** ptr, int64_t* count) {
   CHECK_H(h);
+  REFUSE_INFER(h, "rsrgan_grad_buffer", RSRGAN_ERR_STATE);
   ParamSet* p = pset(h, net);
   if (!p || !ptr || !count) { set_error("bad argument"); return RSRGAN_ERR_INVALID; }
   *ptr = p->g;
@@ -352,10 +368,12 @@ int rsrgan_grad_buffer(rsrgan_handle h, int32_t net, float** ptr, int64_t* count
 
 int rsrgan_grad_bucket_count(rsrgan_handle h, int32_t net) {
   if (!h || (net != RSRGAN_NET_G && net != RSRGAN_NET_D)) return 0;
+  REFUSE_INFER(h, "rsrgan_grad_bucket_count", RSRGAN_ERR_STATE);
   return (int)h->m.gbk[net].size();
 }
 int rsrgan_grad_bucket_info(rsrgan_handle h, int32_t net, int32_t i, int64_t* offset, int64_t* count) {
   CHECK_H(h);
+  REFUSE_INFER(h, "rsrgan_grad_bucket_info", RSRGAN_ERR_STATE);
   Model* m = &h->m;
   if ((net != RSRGAN_NET_G && net != RSRGAN_NET_D) || i < 0 || i >= (int)m->gbk[net].size() || !offset || !count) {
     set_error("bad bucket index"); return RSRGAN_ERR_INVALID;
@@ -366,6 +384,7 @@ int rsrgan_grad_bucket_info(rsrgan_handle h, int32_t net, int32_t i, int64_t* of
 }
 int rsrgan_grad_bucket_wait(rsrgan_handle h, int32_t net, int32_t i, void* stream) {
   CHECK_H(h);
+  REFUSE_INFER(h, "rsrgan_grad_bucket_wait", RSRGAN_ERR_STATE);
   Model* m = &h->m;
   if ((net != RSRGAN_NET_G && net != RSRGAN_NET_D) || i < 0 || i >= (int)m->gbk[net].size()) { set_error("bad bucket index"); return RSRGAN_ERR_INVALID; }
   if (hipStreamWaitEvent((hipStream_t)stream, m->gbk[net][i].ev, 0) != hipSuccess) { set_error("hipStreamWaitEvent failed"); return RSRGAN_ERR_HIP; }
@@ -381,6 +400,7 @@ int rsrgan_profile_begin(rsrgan_handle h) {
 }
 int rsrgan_set_dropout(rsrgan_handle h, float keep_prob, uint64_t seed) {
   CHECK_H(h);
+  REFUSE_INFER(h, "rsrgan_set_dropout", RSRGAN_ERR_STATE);
   if (!(keep_prob > 0.f && keep_prob <= 1.f)) { set_error("keep_prob=%g outside (0, 1]", (double)keep_prob); return RSRGAN_ERR_INVALID; }
   Model& m = h->m;
   if (keep_prob < 1.f && m.g_bnl()) { set_error("g_type bnlstm: DropoutWrapper (keep_prob < 1) is not built"); return RSRGAN_ERR_INVALID; }
@@ -423,6 +443,12 @@ int rsrgan_device_status(rsrgan_handle h, int32_t* code) {
       if (ctl[DP_CTL_ERR] != 0) m.persist_disable(k);                // (its workgroups were not all resident: this handle stops trying)
     }
   }
+  return RSRGAN_OK;
+}
+int rsrgan_device_bytes(rsrgan_handle h, int64_t* bytes) {
+  CHECK_H(h);
+  if (!bytes) { set_error("null output pointer"); return RSRGAN_ERR_INVALID; }
+  *bytes = (int64_t)h->m.alloc_bytes;
   return RSRGAN_OK;
 }
 int rsrgan_profile_launches(rsrgan_handle h, int64_t* n) {

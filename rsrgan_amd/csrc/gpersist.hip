@@ -258,7 +258,11 @@ struct GpLds {
 // RESX (with RES; models/res_lstm_i.py:101-190): the residual is the stack's input at EVERY layer, never a running sum -- layer l + 1 reads
 // out_l + x, the output FC out_{L-1} + x.  The reducer adds its masked m(t) to its half chunk of x(t), read from the stack's input rows in
 // memory as RES does for layer 0; nothing is polled from the layer below.  res_out and the second region of gran2 as under RES.
-template <int NT, bool RES, bool TAG, bool CARRY = false, bool RESX = false>
+// LEAN: the forward of an inference handle (RSRGAN_FLAG_INFER): nothing reads a stash, so the per-step stash stores are not compiled in --
+// the same arithmetic in the same order, the R waves leave c after the last step in slot 1 of the c stash, the reducers the carried m in
+// slot 1 of mst, and out / res_out are written where the pointer is not null (the top layer: the layers below publish through gran2 alone).
+// Slot 0 is read under CARRY and never written.  A variant of its own, as CARRY is.
+template <int NT, bool RES, bool TAG, bool CARRY = false, bool RESX = false, bool LEAN = false>
 __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S, const unsigned c1, const unsigned bid) {
   static_assert(RES || !RESX, "RESX is a form of RES");
   constexpr int NR = GP_NR, NU = NT * NR, CW = 4 * NT;
@@ -438,10 +442,11 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
         gp_signal(&S.cnt_h[r], lane);
         GPT(6 * r + 5);
         if (!gp_wait(&S.cnt_h[r], 4u * ((unsigned)t + 1u), dead)) return;     // every cell of the tile is in the stage
-        if ((a.sched & 2) && !gp_wait(&S.cnt_j[r], 2u * ((unsigned)t + 1u), dead)) return;   // (the lane's partial projections have left first)
+        if (!LEAN && (a.sched & 2) && !gp_wait(&S.cnt_j[r], 2u * ((unsigned)t + 1u), dead)) return;   // (the lane's partial projections have left first)
         // the tile's stash (gate activations, c, h: 7.5 KB) from the LDS stage, a quarter per R wave: NT consecutive lanes write one
         // 16 NT-byte row piece.  The R waves do it: they have nothing in the vector-memory queue that it could delay (the X waves'
         // sweeps queued behind these stores, and a wave that publishes or polls must not have them in front of its hand-off traffic)
+        if (!LEAN) {
 #pragma unroll
         for (int it = 0; it < (6 * 16 * NT + 255) / 256; ++it) {
           const int e = it * 256 + w * 64 + lane;
@@ -451,13 +456,23 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
           float* dst = (k < 4 ? L.gates + rowg * H4 + k * H : k == 4 ? L.c + (rowg + N) * H : L.h + rowg * L.ldH) + cell0 + 4 * cq;
           if (e < 6 * 16 * NT && cell0 + 4 * cq < H) gp_stash_store(dst, v);
         }
-        gp_signal(&S.cnt_s[r], lane);
+        }
+        gp_signal(&S.cnt_s[r], lane);                                    // (LEAN: the stage is free as soon as the tile's cells are in it and h has been read)
         // This workgroup's G waves summed the partial projections of step t-1 before they gathered m(t-1) (the wait at the top):
         // re-arm those ring slots, here, where the wave has nothing urgent to do.  The stores are acknowledged before the wave
         // signals its cells of step t+1, i.e. before this workgroup's partials of step t+1 leave, without which no m(t+1) and
         // hence no partial of step t+2 -- the next write to these slots -- exists.
         if (!TAG && reducer && t > 0) gp_rearm(b1, slot1((t - 1) % GP_R1, r, jbr, 0) + (unsigned)hh * 512u, NC, w, lane);
       }
+    }
+    if (LEAN) {                                                          // c after the last step (a finished row's: frozen at its last frame) -> slot 1
+#pragma unroll
+      for (int r = 0; r < NR; ++r)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const int cell = cell0 + 4 * (w + 4 * s) + q;
+          if (r < nrt && w + 4 * s < NT && cell < H) L.c[((size_t)N + row0 + 16 * r + lr) * H + cell] = cprev[r][s];
+        }
     }
     if (!TAG && reducer) {                                               // the last step's partials: leave every ring slot armed for the next launch
 #pragma unroll
@@ -585,7 +600,7 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
       const float4 v = *reinterpret_cast<const float4*>(L.mst + (size_t)rrow * ldP + rcol);
       mcar = f32x4{v.x, v.y, v.z, v.w};
     }
-  } else {
+  } else if (!LEAN) {
     // slot 0 of the carried states is zero (cell.zero_state)
     for (int e = gw * 64 + lane; e < GP_ROWS * NT; e += 256) {
       const int row = e / NT, cq = e - row * NT;
@@ -670,8 +685,8 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
       const bool live = t < rlen;
       mcar = live ? tot : mcar;
       if (rcol < ldP) {
-        *reinterpret_cast<float4*>(L.mst + ((size_t)(t + 1) * N + rrow) * ldP + rcol) = make_float4(mcar[0], mcar[1], mcar[2], mcar[3]);
-        *reinterpret_cast<float4*>(L.out + ((size_t)t * N + rrow) * ldP + rcol) = live ? make_float4(tot[0], tot[1], tot[2], tot[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!LEAN) *reinterpret_cast<float4*>(L.mst + ((size_t)(t + 1) * N + rrow) * ldP + rcol) = make_float4(mcar[0], mcar[1], mcar[2], mcar[3]);
+        if (!LEAN || L.out) *reinterpret_cast<float4*>(L.out + ((size_t)t * N + rrow) * ldP + rcol) = live ? make_float4(tot[0], tot[1], tot[2], tot[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
     if (RES && reducer && gp == 1) {
@@ -700,27 +715,30 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
         sb = f32x4{__uint_as_float(y[0]), __uint_as_float(y[1]), __uint_as_float(y[2]), __uint_as_float(y[3])};
       }
       const f32x4 s4 = (t < rlen ? tot : f32x4{0.f, 0.f, 0.f, 0.f}) + sb;
-      if (act && rcol < ldP) *reinterpret_cast<float4*>(L.res_out + ((size_t)t * N + rrow) * ldP + rcol) = make_float4(s4[0], s4[1], s4[2], s4[3]);
+      if (act && rcol < ldP && (!LEAN || L.res_out)) *reinterpret_cast<float4*>(L.res_out + ((size_t)t * N + rrow) * ldP + rcol) = make_float4(s4[0], s4[1], s4[2], s4[3]);
       if (act && (l + 1 < a.nl || a.fwd_trail)) gp_store(b2s, off, s4);      // (the top layer's: for the FC workgroups of k_glstm_fwd_dt)
     }
   }
+  // (LEAN) the carried m after the last step -> slot 1, once
+  if (LEAN && reducer && gp == 1 && lane < 32 && rcol < ldP)
+    *reinterpret_cast<float4*>(L.mst + ((size_t)N + rrow) * ldP + rcol) = make_float4(mcar[0], mcar[1], mcar[2], mcar[3]);
 #ifdef GP_TRACE
   if (gw == 0) { const int i0_ = 12, i1_ = 18; GPT_FLUSH(); }
 #endif
 }
 
 constexpr unsigned GP_GEN_WRAP = 1u << 21;      // the generator's control block: generation 2^21 - 1 is followed by 1
-template <int NT, bool RES, bool TAG, bool CARRY = false, bool RESX = false>
+template <int NT, bool RES, bool TAG, bool CARRY = false, bool RESX = false, bool LEAN = false>
 __global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_fwd(const GPersistArgs a) {
   __shared__ __attribute__((aligned(16))) GpLds<NT> S;
   gu32* ctl = (gu32*)a.ctl;
   const unsigned gen = __hip_atomic_load(ctl + DP_CTL_GEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (counts launches; nothing depends on it)
   // (TAG) steps written to the hop-1 ring by the launches so far, mod 2 GP_R1: every workgroup reads it here, the last one to finish moves it on
   const unsigned c1 = TAG ? __hip_atomic_load(ctl + GP_CTL_C1 + GP_CIDX(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-  gp_fwd_body<NT, RES, TAG, CARRY, RESX>(a, S, c1, blockIdx.x);
+  gp_fwd_body<NT, RES, TAG, CARRY, RESX, LEAN>(a, S, c1, blockIdx.x);
   __syncthreads();                                                 // (every wave leaves the body on every path)
   if (threadIdx.x == 0)
-    persist_last_out(ctl, gen, [&] { return gridDim.x; }, [&] { return a.L[a.nl - 1].out; }, GP_GEN_WRAP, [&] {
+    persist_last_out(ctl, gen, [&] { return gridDim.x; }, [&] { return LEAN && !a.L[a.nl - 1].out ? a.L[a.nl - 1].res_out : a.L[a.nl - 1].out; }, GP_GEN_WRAP, [&] {
       if (TAG) __hip_atomic_store(ctl + GP_CTL_C1 + GP_CIDX(a), (c1 + (unsigned)a.T) % (2u * GP_R1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     });
 }
@@ -1553,7 +1571,7 @@ struct NpLds {
   unsigned cnt_x[GP_NR][4], cnt_p[GP_NR], cnt_h[GP_NR], cnt_m[GP_NR], cnt_s[GP_NR], dead, pad_[15];
 };
 
-template <int NT, int KR, int KX, bool CARRY = false>      // CARRY: as gp_fwd_body's
+template <int NT, int KR, int KX, bool CARRY = false, bool LEAN = false>      // CARRY, LEAN: as gp_fwd_body's
 __device__ __forceinline__ void np_fwd_body(const GPersistArgs& a, NpLds<NT, KR, KX>& S) {
   static_assert(sizeof(NpLds<NT, KR, KX>) <= 160 * 1024, "LDS of the unprojected forward kernel");
   constexpr int NR = GP_NR, NU = NT * NR, CW = 4 * NT;
@@ -1693,6 +1711,7 @@ __device__ __forceinline__ void np_fwd_body(const GPersistArgs& a, NpLds<NT, KR,
         gp_signal(&S.cnt_h[r], lane);
         if (!gp_wait(&S.cnt_h[r], 4u * ((unsigned)t + 1u), dead)) return;     // every cell of the tile is in the stage
         // the tile's stash (gate activations, c, h) from the LDS stage, a quarter per R wave: 4 lanes write one 64-byte row piece
+        if (!LEAN) {
 #pragma unroll
         for (int it = 0; it < (6 * 16 * NT + 255) / 256; ++it) {
           const int e = it * 256 + w * 64 + lane;
@@ -1702,8 +1721,13 @@ __device__ __forceinline__ void np_fwd_body(const GPersistArgs& a, NpLds<NT, KR,
           float* dst = (k < 4 ? L.gates + rowg * H4 + k * H : k == 4 ? L.c + (rowg + N) * H : L.h + rowg * L.ldH) + cell0 + 4 * cq;
           if (e < 6 * 16 * NT && cell0 + 4 * cq < H) gp_stash_store(dst, v);
         }
+        }
         gp_signal(&S.cnt_s[r], lane);
       }
+    }
+    if (LEAN && cellw) {                                               // c after the last step -> slot 1
+#pragma unroll
+      for (int r = 0; r < NR; ++r) L.c[((size_t)N + row0 + 16 * r + lr) * H + cell0 + 4 * w + q] = cprev[r];
     }
     return;
   }
@@ -1807,7 +1831,7 @@ __device__ __forceinline__ void np_fwd_body(const GPersistArgs& a, NpLds<NT, KR,
       const float4 v = *reinterpret_cast<const float4*>(L.mst + (size_t)srow * ldP + scol);
       mcar = f32x4{v.x, v.y, v.z, v.w};
     }
-  } else {
+  } else if (!LEAN) {
     for (int e = gw * 64 + lane; e < GP_ROWS * NT; e += 256) {         // slot 0 of the carried states is zero (cell.zero_state)
       const int row = e / NT, cq = e - row * NT;
       if (cell0 + 4 * cq < H) {
@@ -1834,20 +1858,22 @@ __device__ __forceinline__ void np_fwd_body(const GPersistArgs& a, NpLds<NT, KR,
     if (gp == 1 && pubq && scol < H) {                                 // this workgroup's columns of the carried state / masked output, behind the hand-off
       const bool live = t < lenr;
       mcar = live ? hv : mcar;
-      *reinterpret_cast<float4*>(L.mst + ((size_t)(t + 1) * N + srow) * ldP + scol) = make_float4(mcar[0], mcar[1], mcar[2], mcar[3]);
+      if (!LEAN) *reinterpret_cast<float4*>(L.mst + ((size_t)(t + 1) * N + srow) * ldP + scol) = make_float4(mcar[0], mcar[1], mcar[2], mcar[3]);
       if (L.out) *reinterpret_cast<float4*>(L.out + ((size_t)t * N + srow) * ldP + scol) = make_float4(hv[0], hv[1], hv[2], hv[3]);
     }
   }
+  if (LEAN && gp == 1 && pubq && scol < H)                             // the carried h after the last step -> slot 1, once
+    *reinterpret_cast<float4*>(L.mst + ((size_t)N + srow) * ldP + scol) = make_float4(mcar[0], mcar[1], mcar[2], mcar[3]);
 }
 
-template <int NT, int KR, int KX, bool CARRY = false>
+template <int NT, int KR, int KX, bool CARRY = false, bool LEAN = false>
 __global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_np_fwd(const GPersistArgs a) {
   __shared__ __attribute__((aligned(16))) NpLds<NT, KR, KX> S;
   gu32* ctl = (gu32*)a.ctl;
   const unsigned gen = __hip_atomic_load(ctl + DP_CTL_GEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  np_fwd_body<NT, KR, KX, CARRY>(a, S);
+  np_fwd_body<NT, KR, KX, CARRY, LEAN>(a, S);
   __syncthreads();
-  if (threadIdx.x == 0) persist_last_out(ctl, gen, [] { return gridDim.x; }, [&] { return a.L[a.nl - 1].h; }, GP_GEN_WRAP, [] {});
+  if (threadIdx.x == 0) persist_last_out(ctl, gen, [] { return gridDim.x; }, [&] { return LEAN ? a.L[a.nl - 1].out : a.L[a.nl - 1].h; }, GP_GEN_WRAP, [] {});
 }
 
 
@@ -2265,10 +2291,10 @@ static void gp_static(F&& f, bool v, B... more) {
 void launch_glstm_fwd(const GPersistArgs& a, hipStream_t s) {
   gp_arm_gran2(a, s);
   const dim3 g(gp_grid(a)), b(GP_WAVES * 64);
-  // (a.res == 2, res_lstm_i: out_l + x at every layer, gp_fwd_body RESX; a.carry: the stateful forward)
-  gp_static([&](auto res, auto tag, auto carry, auto resx) {
-    if constexpr (res.value || !resx.value) hipLaunchKernelGGL((k_glstm_fwd<5, res.value, tag.value, carry.value, resx.value>), g, b, 0, s, a);
-  }, a.res != 0, a.tags != 0, a.carry != 0, a.res == 2);
+  // (a.res == 2, res_lstm_i: out_l + x at every layer, gp_fwd_body RESX; a.carry: the stateful forward; a.lean: an inference handle's)
+  gp_static([&](auto res, auto tag, auto carry, auto resx, auto lean) {
+    if constexpr (res.value || !resx.value) hipLaunchKernelGGL((k_glstm_fwd<5, res.value, tag.value, carry.value, resx.value, lean.value>), g, b, 0, s, a);
+  }, a.res != 0, a.tags != 0, a.carry != 0, a.res == 2, a.lean != 0);
   ++g_chain_launches;
 }
 // ---- the unprojected form: plan, sizes, launch ----
@@ -2295,10 +2321,10 @@ size_t gpersist_np_lds_bytes() { return sizeof(NpLds<4, 7, 6>); }
 void launch_glstm_np_fwd(const GPersistArgs& a, hipStream_t s) {
   gpersist_arm_bytes(a.gran2, gpersist_np_gran2_bytes(a), s);
   const dim3 g(gp_grid(a)), b(GP_WAVES * 64);
-  gp_static([&](auto nt2, auto carry) {
-    if constexpr (nt2.value) hipLaunchKernelGGL((k_glstm_np_fwd<2, 8, 8, carry.value>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_glstm_np_fwd<4, 7, 6, carry.value>), g, b, 0, s, a);
-  }, a.NT == 2, a.carry != 0);
+  gp_static([&](auto nt2, auto carry, auto lean) {
+    if constexpr (nt2.value) hipLaunchKernelGGL((k_glstm_np_fwd<2, 8, 8, carry.value, lean.value>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_glstm_np_fwd<4, 7, 6, carry.value, lean.value>), g, b, 0, s, a);
+  }, a.NT == 2, a.carry != 0, a.lean != 0);
   ++g_chain_launches;
 }
 // (the unprojected BPTT: 8 cells per workgroup only; gran1 / gran3 = its two rings, armed once)

@@ -252,6 +252,9 @@ struct GPersistArgs {
   // the stateful forward (rsrgan_forward_g_stream): every row starts from slot 0 of the layers' c / mst stash as the host left it
   // (Model::gstate_load) instead of cell.zero_state; the forward launches only (k_glstm_fwd / k_glstm_np_fwd, their CARRY variants)
   int carry;
+  // an inference handle's forward (RSRGAN_FLAG_INFER; gpersist.hip LEAN): no per-step stash stores -- the final c / m go to slot 1 of the
+  // c / mst buffers (two slots are all they have), out / res_out are written where the pointer is not null; the forward launches only
+  int lean;
 };
 constexpr int GP_TMAX = 2046;                     // longest launch (slot offsets are 32-bit; a longer batch takes the launch-per-phase path)
 bool gpersist_plan(GPersistArgs& a);              // fills NT / NC; false: shape not supported
@@ -393,6 +396,8 @@ void launch_col2im(const float* dcol, int ldk, int C, int S, int W, int kh, int 
 struct GStateLayer { float *c, *mst; int H, P, ldP, off; };
 struct GStateArgs { GStateLayer L[GP_MAXL]; int nl, SF, rows, dir; float* state; size_t slot; const int* mask; };
 void launch_gstate(const GStateArgs& a, hipStream_t s);
+// the row lengths of window [t0, t0 + Tw) of a batch: dst[b] = clamp(len[b] - t0, 0, Tw)  (Model::infer_forward)
+void launch_window_len(const int* len, int* dst, int n, int t0, int Tw, hipStream_t s);
 struct ZeroList { int n; float* p[32]; unsigned len[32]; };        // many small buffers zeroed by ONE launch
 void launch_zero_many(const ZeroList& zl, hipStream_t s);
 struct ColsumsBatch { const float* dz[4]; const float* cprev[4]; const float* ccur[4]; float* db[4]; float* dwi[4]; float* dwf[4]; float* dwo[4]; int n; };

@@ -1421,6 +1421,15 @@ void launch_gstate(const GStateArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_gstate, dim3(a.rows), dim3(256), 0, s, a);
 }
 
+__global__ void k_window_len(const int* __restrict__ len, int* __restrict__ dst, int n, int t0, int Tw) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < n) dst[b] = min(max(len[b] - t0, 0), Tw);
+}
+void launch_window_len(const int* len, int* dst, int n, int t0, int Tw, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_window_len, dim3((n + 255) / 256), dim3(256), 0, s, len, dst, n, t0, Tw);
+}
+
 __global__ void k_zero_many(ZeroList zl) {
   const int j = blockIdx.y;
   if (j >= zl.n) return;

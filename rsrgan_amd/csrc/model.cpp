@@ -98,6 +98,7 @@ T* Model::alloc(size_t n) {
   if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) return nullptr;
   (void)hipMemset(p, 0, n * sizeof(T));
   allocs.push_back(p);
+  alloc_bytes += n * sizeof(T);
   return reinterpret_cast<T*>(p);
 }
 
@@ -155,6 +156,15 @@ static void alloc_stash(Model& M, LstmStash& S, const LstmLayer& L, int N, int T
   S.dmst = M.alloc<float>((size_t)N * L.ldP);
 }
 
+// An inference handle's stash (RSRGAN_FLAG_INFER): the carried states of W + 1 steps and the layer's outputs -- of W steps, or of all T
+// where the output FC reads them (out_T).  gates / h, which only the launch-per-phase path touches, come with its first use
+// (Model::infer_fallback_stash); nothing of the backward pass exists.
+static void alloc_stash_infer(Model& M, LstmStash& S, const LstmLayer& L, int N, int W, int out_T) {
+  S.c = M.alloc<float>((size_t)(W + 1) * N * L.H);
+  S.mst = M.alloc<float>((size_t)(W + 1) * N * L.ldP);
+  S.out = M.alloc<float>((size_t)out_T * N * L.ldP);
+}
+
 // the control block of a persistent launch (kernels.h DP_CTL_*) in its initial state: generation 1, no workgroup finished, no error
 static hipError_t ctl_reset(unsigned* ctl) {
   const unsigned ctl0[DP_CTL_WORDS] = {1u, 0u, 0u, 0u};
@@ -168,6 +178,10 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   if (B <= 0 || Tmax <= 0 || Din <= 0 || Dout <= 0 || c.g_layers <= 0 || c.d_layers <= 0 || c.g_cells <= 0 ||
       c.d_cells <= 0 || (c.g_layers > MAXJ && !g_dnn()) || c.d_layers > MAXJ) {
     set_error("invalid sizes in rsrgan_cfg");
+    return RSRGAN_ERR_INVALID;
+  }
+  if (infer() && (g_dnn() || g_bnl())) {
+    set_error("RSRGAN_FLAG_INFER: an inference-only handle for g_type %d is not built (the sequence generators lstm, res_lstm_l, res_lstm_base, res_lstm_i only)", c.g_type);
     return RSRGAN_ERR_INVALID;
   }
   if (c.d_type != RSRGAN_D_LSTM && c.d_type != RSRGAN_D_DNN) { set_error("Unrecognized D type %d", c.d_type); return RSRGAN_ERR_INVALID; }
@@ -277,7 +291,9 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     set_error("Unrecognized G type %d", c.g_type);                       // gan_rnn_placeholder.py:131-132
     return RSRGAN_ERR_INVALID;
   }
-  if (d_dnn()) {                                                         // models/discriminator_dnn.py:61-92
+  if (infer()) {
+    // gan_rnn_placeholder.py:133-135: the generator alone -- RSRGAN_NET_D's table stays empty
+  } else if (d_dnn()) {                                                  // models/discriminator_dnn.py:61-92
     int in = c.d_joint_dim + Dout;
     for (int l = 0; l < c.d_layers; ++l) { add_fc(D, dfc, fc_name("d_model", l), in, c.d_cells, bn_on()); in = c.d_cells; }
     add_fc(D, dfc, fc_name("d_model", c.d_layers), in, 1);
@@ -300,14 +316,18 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     }
   }
   // ---- device buffers ----
-  const bool ema_on = c.ema_decay > 0.f;
-  G.w = alloc<float>(G.padded); G.g = alloc<float>(G.padded); G.m = alloc<float>(G.padded); G.v = alloc<float>(G.padded);
-  G.ema = ema_on ? alloc<float>(G.padded) : nullptr;
-  D.w = alloc<float>(D.padded); D.g = alloc<float>(D.padded);
-  if (d_adam()) { D.m = alloc<float>(D.padded); D.v = alloc<float>(D.padded); }
-  D.ema = ema_on ? alloc<float>(D.padded) : nullptr;
-  if (!G.w || !G.g || !G.m || !G.v || !D.w || !D.g) { set_error("hipMalloc failed (parameters)"); return RSRGAN_ERR_HIP; }
-  if (build_chunks(*this, G) || build_chunks(*this, D)) { set_error("hipMalloc failed (chunk tables)"); return RSRGAN_ERR_HIP; }
+  const bool ema_on = c.ema_decay > 0.f && !infer();
+  const bool inf = infer();                                 // (the variables and their copies only: no gradients, moments, shadows, no discriminator)
+  G.w = alloc<float>(G.padded);
+  if (!inf) {
+    G.g = alloc<float>(G.padded); G.m = alloc<float>(G.padded); G.v = alloc<float>(G.padded);
+    G.ema = ema_on ? alloc<float>(G.padded) : nullptr;
+    D.w = alloc<float>(D.padded); D.g = alloc<float>(D.padded);
+    if (d_adam()) { D.m = alloc<float>(D.padded); D.v = alloc<float>(D.padded); }
+    D.ema = ema_on ? alloc<float>(D.padded) : nullptr;
+  }
+  if (!G.w || (!inf && (!G.g || !G.m || !G.v || !D.w || !D.g))) { set_error("hipMalloc failed (parameters)"); return RSRGAN_ERR_HIP; }
+  if (!inf && (build_chunks(*this, G) || build_chunks(*this, D))) { set_error("hipMalloc failed (chunk tables)"); return RSRGAN_ERR_HIP; }
   for (auto* layers : {&gl, &dl})
     for (auto& L : *layers) {
       L.KxT = alloc<float>((size_t)4 * L.H * L.ldI);
@@ -317,15 +337,21 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
       L.Wg_full = alloc<float>(swizzle_floats(4 * ncb, kbI));
       L.Wg_h = alloc<float>(swizzle_floats(4 * ncb, kbP));
       L.WpT_sw = L.has_proj ? alloc<float>(swizzle_floats((L.P + 15) / 16, kbH)) : nullptr;
+      if (inf) continue;                                    // (the backward phases' copies)
       L.Wp_sw = L.has_proj ? alloc<float>(swizzle_floats(ncb, kbP)) : nullptr;
       L.Kb_full = alloc<float>(swizzle_floats((L.I + L.P + 15) / 16, kb4));
       L.Kb_rec = alloc<float>(swizzle_floats((L.P + 15) / 16, kb4));
     }
   const size_t TB = (size_t)Tmax * B;
-  x_tm = alloc<float>(TB * ldDin); lab_tm = alloc<float>(TB * ldDout); y_tm = alloc<float>(TB * ldDout);
+  x_tm = alloc<float>(TB * ldDin); lab_tm = inf ? nullptr : alloc<float>(TB * ldDout); y_tm = alloc<float>(TB * ldDout);
   const int ldP = g_dnn() ? 4 : pad4(P);
   g_st.resize(gl.size());
-  for (size_t l = 0; l < gl.size(); ++l) alloc_stash(*this, g_st[l], gl[l], B, Tmax);
+  const bool res_sums = c.g_type == RSRGAN_G_RES_LSTM_L || c.g_type == RSRGAN_G_RES_LSTM_I;      // (the output FC reads g_res, not the top layer's out)
+  inf_W = std::min(Tmax, (int)INFER_WINDOW);
+  for (size_t l = 0; l < gl.size(); ++l) {
+    if (inf) alloc_stash_infer(*this, g_st[l], gl[l], B, inf_W, l + 1 == gl.size() && !res_sums ? Tmax : inf_W);
+    else alloc_stash(*this, g_st[l], gl[l], B, Tmax);
+  }
   if (!g_dnn() && !g_bnl() && !gl.empty() && gl.size() <= (size_t)GP_MAXL) {      // the carried state of the stateful forward
     for (auto& L : gl) g_state_sf += L.H + L.P;
     g_state = alloc<float>((size_t)B * g_state_sf);
@@ -393,7 +419,7 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     g_ins[0] = x_tm;
     for (size_t l = 0; l < gl.size(); ++l) {
       if (c.g_type == RSRGAN_G_RES_LSTM_L || c.g_type == RSRGAN_G_RES_LSTM_I) {      // (res_lstm_i: g_res[l] = out_l + x)
-        g_res.push_back(alloc<float>(TB * ldP));
+        g_res.push_back(alloc<float>((inf && l + 1 < gl.size() ? (size_t)inf_W * B : TB) * ldP));      // (an inference handle: one window below the top layer)
         g_ins[l + 1] = g_res.back();
       } else {
         g_ins[l + 1] = g_st[l].out;
@@ -402,11 +428,11 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   }
   const int gmaxld = std::max(std::max(ldP, ldDin), ldDout);      // (g_dB / g_dC also carry dy [T*B][ldDout]: an output wider than the generator's
                                                                   //  layers overflowed them -- found by __graft_entry__.smoke()'s second configuration)
-  g_dA = alloc<float>(TB * gmaxld); g_dB = alloc<float>(TB * gmaxld); g_dC = alloc<float>(TB * gmaxld);
+  if (!inf) { g_dA = alloc<float>(TB * gmaxld); g_dB = alloc<float>(TB * gmaxld); g_dC = alloc<float>(TB * gmaxld); }
   const size_t TB2 = TB * 2;
   const int ldPd = d_dnn() ? 4 : pad4(dR);
-  xd = alloc<float>(TB2 * ldDout); logits = alloc<float>(TB2 * 4); dlogits = alloc<float>(TB2 * 4);
-  if (d_dnn()) {
+  if (!inf) { xd = alloc<float>(TB2 * ldDout); logits = alloc<float>(TB2 * 4); dlogits = alloc<float>(TB2 * 4); }
+  if (d_dnn() && !inf) {
     ldJ = pad4(c.d_joint_dim + Dout);
     if (c.d_joint_dim > 0) joint = alloc<float>(TB2 * ldJ);
     d_act.push_back(c.d_joint_dim > 0 ? joint : xd);
@@ -414,7 +440,7 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     d_act.push_back(logits);
     dy_buf = alloc<float>(TB * ldDout);
   }
-  if (g_dnn() || d_dnn()) {
+  if ((g_dnn() || d_dnn()) && !inf) {
     int mx = std::max(ldJ, ldDin);
     for (auto& F : gfc) mx = std::max(mx, std::max(F.ld_in, F.ld_out));
     for (auto& F : dfc) mx = std::max(mx, std::max(F.ld_in, F.ld_out));
@@ -507,7 +533,7 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
         gp_gran2 = (unsigned long long*)alloc<float>(gp_gran2_bytes / sizeof(float));
         gp_ctl = (unsigned*)alloc<float>(16);
         // the BPTT form exists for 8 cells per workgroup only: its two rings (state gradient, input gradient between layers)
-        if (gp_np_nt == 2 && (gp_live & 2) && switches().gp_np_bwd) {
+        if (gp_np_nt == 2 && (gp_live & 2) && switches().gp_np_bwd && !inf) {
           gp_gran1 = (unsigned long long*)alloc<float>(gpersist_np_gran1_bytes(ga) / sizeof(float));
           gp_gran3 = (unsigned long long*)alloc<float>(gpersist_np_gran3_bytes(ga) / sizeof(float));
           if (!gp_gran1 || !gp_gran3) { gp_gran1 = gp_gran3 = nullptr; }
@@ -525,7 +551,7 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
       gp_ctl = (unsigned*)alloc<float>(16);
       // the BPTT launch's hand-offs time out when a layer's recurrent width is a single 16-column block (P <= 16: seen at H = 64 and
       // 128, the bounded waits expire and the step is poisoned): such a stack keeps the persistent forward, its BPTT takes the launch path
-      bool bwd_ok = (gp_live & 2) != 0;
+      bool bwd_ok = (gp_live & 2) != 0 && !inf;
       for (auto& L : gl) bwd_ok = bwd_ok && L.P > 16;
       if (bwd_ok) gp_gran3 = (unsigned long long*)alloc<float>(gpersist_gran3_bytes(ga) / sizeof(float));
       if (gp_gran1 && gp_gran2 && gp_ctl) {
@@ -547,10 +573,11 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   drop_ctr = (unsigned long long*)alloc<float>(4);
   HIPC(hipMemset(drop_ctr, 0, 16));
   const int dmaxld = std::max(ldPd, ldDout);
-  d_dA = alloc<float>(TB2 * dmaxld); d_dB = alloc<float>(TB2 * dmaxld);
+  if (!inf) { d_dA = alloc<float>(TB2 * dmaxld); d_dB = alloc<float>(TB2 * dmaxld); }
   len_dev = alloc<int>(2 * B);
+  if (inf) len_win = alloc<int>(B);                         // a window's row lengths (infer_forward)
   zeros = alloc<float>(64);
-  noise_r_buf = alloc<float>((size_t)B * Dout); noise_f_buf = alloc<float>((size_t)B * Dout);
+  if (!inf) { noise_r_buf = alloc<float>((size_t)B * Dout); noise_f_buf = alloc<float>((size_t)B * Dout); }
   if (hipStreamCreateWithFlags(&main_s, hipStreamNonBlocking) != hipSuccess) main_s = nullptr;
   if (main_s && (hipEventCreateWithFlags(&ev_in, hipEventDisableTiming) != hipSuccess ||
                  hipEventCreateWithFlags(&ev_out, hipEventDisableTiming) != hipSuccess)) { (void)hipStreamDestroy(main_s); main_s = nullptr; }
@@ -560,10 +587,12 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   maxcols = std::max(maxcols, (size_t)Din + 4);
   maxcols = std::max(maxcols, (size_t)std::max(ldP, ldDin));
   scratch_floats = std::max<size_t>(4 * 64 * maxcols, 16384);            // (x 4: the column sums of up to four layers in one launch)
-  scratch = alloc<float>(scratch_floats);
-  scratch2 = alloc<float>(std::max<size_t>(4 * 64 * maxcols, 1024));
-  g_fc_out_wT = g_dnn() ? nullptr : alloc<float>((size_t)Dout * ldP);
-  if (hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess) side = nullptr;
+  if (!inf) {                                               // (column sums and loss partials; the per-step FC stage of the fused training launches)
+    scratch = alloc<float>(scratch_floats);
+    scratch2 = alloc<float>(std::max<size_t>(4 * 64 * maxcols, 1024));
+    g_fc_out_wT = g_dnn() ? nullptr : alloc<float>((size_t)Dout * ldP);
+  }
+  if (inf || hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess) side = nullptr;
   if (hipEventCreateWithFlags(&ev_last, hipEventDisableTiming) != hipSuccess) ev_last = nullptr;
   {
     if (sw.dpipe > 0 && trail_fits && side && !d_dnn() && dp_max_grid >= dpersist_grid((int)dl.size(), B)) {
@@ -584,21 +613,25 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   gemm_ws_floats = (size_t)32 << 20;          // 128 MiB of split-K partial tiles / stream-K pieces (two 192 x 256 pieces per worker: 100 MB)
   gemm_ws = alloc<float>(gemm_ws_floats);
   if (!gemm_ws) gemm_ws_floats = 0;
-  bwdb_ws_floats = (size_t)8 << 20;
-  bwdb_ws = alloc<float>(bwdb_ws_floats);
-  gemm_ws2 = alloc<float>(gemm_ws_floats ? gemm_ws_floats : 1);
-  if (switches().dk_pad && !gl.empty() && gl[0].has_proj && gl[0].I % 4 != 0 && gl[0].ldI % 4 == 0 && gl.size() <= (size_t)GEMM_MAXB) {
+  bwdb_ws_floats = inf ? 0 : (size_t)8 << 20;
+  if (!inf) {
+    bwdb_ws = alloc<float>(bwdb_ws_floats);
+    gemm_ws2 = alloc<float>(gemm_ws_floats ? gemm_ws_floats : 1);
+  }
+  if (!inf && switches().dk_pad && !gl.empty() && gl[0].has_proj && gl[0].I % 4 != 0 && gl[0].ldI % 4 == 0 && gl.size() <= (size_t)GEMM_MAXB) {
     dk_tmp_per = (size_t)(gl[0].ldI + gl[0].P) * 4 * gl[0].H;
     dk_tmp = alloc<float>(dk_tmp_per * gl.size());
     if (!dk_tmp) dk_tmp_per = 0;
   }
   if (!gemm_ws2) side = nullptr;
   if (!side) dpipe = false;
-  if (!scratch || !d_dB || !g_dB || !xd) { set_error("hipMalloc failed (activations)"); return RSRGAN_ERR_HIP; }
+  if (inf ? (!x_tm || !y_tm || !len_win || !g_st.back().out || !g_st.back().c || !g_st.back().mst || (res_sums && !g_res.back()))
+          : (!scratch || !d_dB || !g_dB || !xd)) { set_error("hipMalloc failed (activations)"); return RSRGAN_ERR_HIP; }
 
   // ---- initial values: xavier_initializer() uniform / zeros (models/lstm.py:86-87,93) ----
   std::mt19937_64 rng(seed);
   for (ParamSet* ps : {&G, &D}) {
+    if (ps == &D && inf) continue;
     std::vector<float> host((size_t)ps->padded, 0.f);
     if (ps == &G && g_bnl()) bnl_init(host, seed);
     else for (auto& t : ps->t) {
@@ -625,8 +658,10 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   hdyn[DYN_EPS] = c.adam_eps; hdyn[DYN_EMA] = c.ema_decay;
   HIPC(hipMemcpy(dyn, hdyn, sizeof(hdyn), hipMemcpyHostToDevice));
   refresh_transposes(RSRGAN_NET_G, nullptr);
-  refresh_transposes(RSRGAN_NET_D, nullptr);
-  { int rc = build_buckets(); if (rc) return rc; }
+  if (!inf) {
+    refresh_transposes(RSRGAN_NET_D, nullptr);
+    int rc = build_buckets(); if (rc) return rc;
+  }
   HIPC(hipDeviceSynchronize());
   HIPC(hipGetLastError());
   return RSRGAN_OK;
@@ -1156,6 +1191,20 @@ bool Model::persist_forward_g(int T, hipStream_t s) {
   if (!gpersist_args(a, T) || (gp_noproj ? gpersist_np_gran2_bytes(a) : gpersist_gran2_bytes(a)) > gp_gran2_bytes) return false;
   a.L[0].in = g_ins[0];                                // (layer 0's input product runs inside the launch as well)
   a.carry = g_carry ? 1 : 0;                           // (the stateful forward: the CARRY variants of the same launches, counted alike)
+  if (infer()) {
+    // the stash-free variants (gpersist.hip LEAN) on window [inf_t0, inf_t0 + T): this window's lengths, its rows of the stack's input and of
+    // the top layer's outputs; below the top layer nothing is written (the layers publish through gran2)
+    a.lean = 1; a.len = len_win;
+    a.L[0].in = g_ins[0] + (size_t)inf_t0 * B * gl[0].ldI;
+    const size_t top = gl.size() - 1;
+    for (size_t l = 0; l < gl.size(); ++l) {
+      GPersistLayer& G_ = a.L[l];
+      G_.gates = G_.h = G_.dmt = nullptr;
+      const size_t o = (size_t)inf_t0 * B * gl[l].ldP;
+      G_.out = l == top && !a.res ? g_st[l].out + o : nullptr;
+      G_.res_out = l == top && a.res ? g_res[l] + o : nullptr;
+    }
+  }
   if (gp_noproj) {                                     // num_proj=None: the single-hop form (no event bracket: bench.py's dominant-kernel timing is the projected form's)
     for (size_t l = 0; l < gl.size(); ++l) a.L[l].Wp = nullptr;
     launch_glstm_np_fwd(a, s);
@@ -1756,7 +1805,7 @@ Chain Model::d_chain(int N, int Ns, int row0) {
 
 void Model::gstate_xfer(int dir, int T, int rows, const int* mask, hipStream_t s) {
   GStateArgs a{};
-  a.nl = (int)gl.size(); a.SF = g_state_sf; a.rows = rows; a.dir = dir; a.state = g_state; a.slot = (size_t)T * B; a.mask = mask;
+  a.nl = (int)gl.size(); a.SF = g_state_sf; a.rows = rows; a.dir = dir; a.state = g_state; a.slot = (size_t)T * B; a.mask = mask;      // (T: the slot of c / mst that holds the final state)
   int off = 0;
   for (size_t l = 0; l < gl.size(); ++l) {
     a.L[l] = GStateLayer{g_st[l].c, g_st[l].mst, gl[l].H, gl[l].P, gl[l].ldP, off};
@@ -1780,12 +1829,84 @@ void Model::g_forward(int T, hipStream_t s, Chain* extra) {
   if (g_dnn()) { bn_eval_call = false; g_frame_forward(T * B, s); g_fwd_valid = true; return; }
   if (g_bnl()) { bnl_forward(T, false, s); return; }      // (rsrgan_forward_g: decode normalises with the moving statistics)
   g_forward_head(T, s);
+  if (infer()) { infer_forward(T, s); g_forward_tail(T, s); return; }
   if (!extra && persist_forward_g(T, s)) { g_forward_tail(T, s); return; }
   std::vector<Chain> chains;
   chains.push_back(g_chain(T));
   if (extra) chains.push_back(*extra);
   rnn_forward(chains, T, s);
   g_forward_tail(T, s);
+}
+
+// The recurrence of an inference handle (RSRGAN_FLAG_INFER) over T frames, in windows that hand the state on: one persistent launch of the
+// stash-free variants per <= GP_TMAX frames (normally one), or -- shapes the persistent plans do not take, RSRGAN_FLAG_WAVEFRONT off,
+// persist_disable -- the launch-per-phase path in windows of <= INFER_WINDOW frames, which is all the stashes hold.  A window reads its
+// initial state in slot 0 of c / mst (the first one: zeros, or the caller's carried state under g_carry) and leaves its final state in
+// slot inf_slot (1 behind a persistent launch, the window's length behind the launch path): copied to slot 0 for the next window, read by
+// gstate_xfer behind the last.  Rows get the window's own lengths clamp(len - t0, 0, Tw): a row that ended earlier copies its state
+// through and outputs zeros, as dynamic_rnn does.  Only the top layer's outputs go to the full-length buffer.
+bool Model::infer_fallback_stash() {
+  for (size_t l = 0; l < gl.size(); ++l) {
+    LstmStash& S = g_st[l];
+    if (!S.gates) S.gates = alloc<float>((size_t)inf_W * B * 4 * gl[l].H);
+    if (!S.h) S.h = alloc<float>((size_t)inf_W * B * gl[l].ldH);
+    if (!S.gates || !S.h) return false;
+  }
+  return true;
+}
+// one window on the launch-per-phase path: every layer sees stashes and inputs one window long, the top layer's outputs land in place in
+// the full-length buffer
+void Model::infer_window_launches(int t0, int Tw, hipStream_t s) {
+  const bool res_l = cfg.g_type == RSRGAN_G_RES_LSTM_L, res_any = res_l || g_resi();
+  const size_t top = gl.size() - 1;
+  const float* x0 = g_ins[0] + (size_t)t0 * B * gl[0].ldI;
+  std::vector<LstmStash> st(g_st);
+  Chain ch;
+  for (size_t l = 0; l < gl.size(); ++l) {
+    const size_t o = l == top ? (size_t)t0 * B * gl[l].ldP : 0;
+    if (!res_any) st[l].out += o;
+    LayerRun R;
+    R.ps = &G; R.L = &gl[l]; R.S = &st[l]; R.in = l == 0 ? x0 : g_ins[l];
+    R.N = B; R.Ns = B; R.row0 = 0; R.len = len_win;
+    R.zx_batched = (l == 0);
+    R.carry = g_carry;
+    if (res_l) { R.res_in = R.in; R.res_out = g_res[l] + o; }       // inputs_{l+1} = outputs_l + inputs_l
+    if (g_resi()) { R.res_in = x0; R.res_out = g_res[l] + o; }       // inputs_{l+1} = outputs_l + x
+    ch.push_back(R);
+  }
+  std::vector<Chain> chains{ch};
+  rnn_forward(chains, Tw, s);
+}
+void Model::infer_forward(int T, hipStream_t s) {
+  const bool carry_in = g_carry;
+  bool persist = gp_fwd_on() && wavefront();
+  for (int t0 = 0; t0 < T;) {
+    const int Tw = std::min(T - t0, persist ? gp_Tcap : inf_W);
+    g_carry = carry_in || t0 > 0;
+    inf_t0 = t0;
+    launch_window_len(len_dev, len_win, B, t0, Tw, s);
+    if (persist && persist_forward_g(Tw, s)) {
+      inf_slot = 1;
+    } else if (persist) {
+      persist = false;                                   // (no persistent plan takes this shape: the same frames again, in the launch path's windows)
+      continue;
+    } else {
+      if (!infer_fallback_stash()) { set_error("hipMalloc failed (the launch path's stash of an inference handle)"); inf_failed = true; break; }
+      infer_window_launches(t0, Tw, s);
+      inf_slot = Tw;
+    }
+    t0 += Tw;
+    if (t0 < T) infer_state_to_slot0(s);
+  }
+  g_carry = carry_in;
+  inf_t0 = 0;
+}
+void Model::infer_state_to_slot0(hipStream_t s) {
+  for (size_t l = 0; l < gl.size(); ++l) {
+    const size_t nc = (size_t)B * gl[l].H, nm = (size_t)B * gl[l].ldP;
+    (void)hipMemcpyAsync(g_st[l].c, g_st[l].c + (size_t)inf_slot * nc, nc * sizeof(float), hipMemcpyDeviceToDevice, s);
+    (void)hipMemcpyAsync(g_st[l].mst, g_st[l].mst + (size_t)inf_slot * nm, nm * sizeof(float), hipMemcpyDeviceToDevice, s);
+  }
 }
 
 void Model::d_logits(int N, int T, hipStream_t s) {

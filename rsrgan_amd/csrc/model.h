@@ -216,7 +216,7 @@ struct Model {
   unsigned* gp_ctl = nullptr;
   size_t gp_gran2_bytes = 0;
   int gp_live = sw.gpersist;                              // RSRGAN_GPERSIST's bits (0 forward, 1 backward) until persist_disable clears them
-  int gp_Tcap = 0;                                        // the rings are sized for min(max_frames, GP_TMAX) steps; longer batches take the launch path
+  int gp_Tcap = 0;                                        // the rings are sized for min(max_frames, GP_TMAX) steps; longer batches take the launch path (an inference handle: consecutive launches)
   // the discriminator's weight gradients inside its stand-alone BPTT launch (dpersist.hip dp_dw_body; RSRGAN_DW_INKERNEL=0: the GEMM /
   // column-sum launches behind it): per-(layer, tile) partial sums, progress words, the tensors' offsets inside a record (device)
   float* dw_ws = nullptr; unsigned* dw_flag = nullptr; long long* dw_src = nullptr; size_t dw_stride = 0;
@@ -277,7 +277,7 @@ struct Model {
   void g_frame_backward(int rows, float* dy, hipStream_t s);            // parameter gradients from d(output)
   void rced_forward(int rows, hipStream_t s);
   void rced_backward(int rows, float* dy, hipStream_t s);
-  bool d_dnn() const { return cfg.d_type == RSRGAN_D_DNN; }
+  bool d_dnn() const { return cfg.d_type == RSRGAN_D_DNN && !(cfg.flags & RSRGAN_FLAG_INFER); }   // (an inference handle has no discriminator of either kind)
   bool d_adam() const { return g_dnn(); }     // models/gan.py:125 (Adam) vs gan_rnn_placeholder.py:144 (SGD)
   // `calls` = how many batch-norm calls the `rows` rows are (1, or 2 = the discriminator's real | fake halves, each with its own
   // batch moments); row0 = first row of act[] / pre to work on (the fake half alone in the G-run's backward pass)
@@ -323,6 +323,7 @@ struct Model {
   int cur_T = 0;
   bool d_grads_ready = false, g_grads_ready = false;
   std::vector<void*> allocs;
+  size_t alloc_bytes = 0;          // bytes behind allocs (rsrgan_device_bytes)
 
   int init(const rsrgan_cfg& c, uint64_t seed);
   void destroy();
@@ -409,6 +410,18 @@ struct Model {
   void gemm(const float* A, int lda, bool a_kc, const float* B, int ldb, bool b_kc, float* C, int ldc, int M, int N,
             int K, const float* bias, int act, float alpha, bool accumulate, hipStream_t s);
   bool supervised() const { return (cfg.flags & RSRGAN_FLAG_SUPERVISED) != 0; }
+  // ---- RSRGAN_FLAG_INFER: a generator-only, forward-only handle.  init allocates the variables and their forward copies,
+  // x_tm / y_tm / g_h0, the top layer's outputs, g_state, the forward launch's rings and gemm_ws; the c / mst stashes hold inf_W + 1 steps
+  bool infer() const { return (cfg.flags & RSRGAN_FLAG_INFER) != 0; }
+  static constexpr int INFER_WINDOW = 64;          // frames per window of the launch-per-phase fallback: memory against launches, not tuned
+  int inf_W = 0;                                   // min(max_frames, INFER_WINDOW)
+  int* len_win = nullptr;                          // [B] the running window's row lengths
+  int inf_t0 = 0, inf_slot = 0;                    // first frame of the running window; the slot of c / mst that holds the state behind the last one
+  bool inf_failed = false;                         // the launch path's stash could not be allocated (reported by the calling entry point)
+  bool infer_fallback_stash();                     // gates / h of one window, with the launch path's first use
+  void infer_forward(int T, hipStream_t s);
+  void infer_window_launches(int t0, int Tw, hipStream_t s);
+  void infer_state_to_slot0(hipStream_t s);
   bool wavefront() const { return (cfg.flags & RSRGAN_FLAG_WAVEFRONT) != 0; }
   float* g_fc_out_wT = nullptr;   // [Dout][ldP] transposed copy of the output FC weights (per-step FC stage)
   float* bwdb_ws = nullptr;        // split-K partial tiles of backward phase B

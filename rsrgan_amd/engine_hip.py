@@ -37,7 +37,8 @@ class HipEngine:
                  d_proj: Optional[int] = None, d_type: Optional[str] = None, d_joint_off: Optional[int] = None,
                  d_joint_dim: Optional[int] = None, clip_norm: Optional[float] = None, g_splice: Optional[int] = None,
                  l2_scale: float = 0.0, cross_validation: bool = False, batch_norm: bool = False,
-                 ema_decay: float = 0.9999, seed: int = 4321, device: Optional[torch.device] = None, flags: int = 3):
+                 ema_decay: float = 0.9999, seed: int = 4321, device: Optional[torch.device] = None, flags: int = 3,
+                 inference: bool = False):
         if g_type not in _lib.G_TYPES:
             raise ValueError("Unrecognized G type {}".format(g_type))      # gan_rnn_placeholder.py:131-132
         self.lib = _lib.load()
@@ -71,7 +72,10 @@ class HipEngine:
         cfg.l2_scale = l2_scale
         cfg.cross_validation = 1 if cross_validation else 0
         cfg.ema_decay = ema_decay
-        cfg.flags = flags | (_lib.FLAG_BATCH_NORM if batch_norm else 0)
+        # inference: a generator-only, forward-only handle (include/rsrgan.h RSRGAN_FLAG_INFER): no discriminator, no optimizer
+        # state, no BPTT stash; forward_g, forward_g_stream, the g_state_* calls and the generator's variables only
+        self.inference = bool(inference)
+        cfg.flags = flags | (_lib.FLAG_BATCH_NORM if batch_norm else 0) | (_lib.FLAG_INFER if inference else 0)
         self.cfg = cfg
         self.batch_size, self.max_frames = batch_size, max_frames
         self.input_dim, self.output_dim = input_dim, output_dim
@@ -89,7 +93,7 @@ class HipEngine:
         # this stream instead and pay nothing
         self.stream = torch.cuda.Stream(device=self.device)
         self.d_has_adam = g_type in ("dnn", "rced")
-        self.ema_enabled = ema_decay > 0          # no EMA shadow buffers in the library otherwise (WHAT['ema'] is absent)
+        self.ema_enabled = ema_decay > 0 and not inference      # no EMA shadow buffers in the library otherwise (WHAT['ema'] is absent)
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:
@@ -101,6 +105,17 @@ class HipEngine:
             self.close()
         except Exception:
             pass
+
+    def _training_only(self, what: str):
+        if self.inference:
+            raise _lib.RsrganError("%s: this engine is inference-only (HipEngine(inference=True)): it has no discriminator, "
+                                   "gradients or optimizer state" % what)
+
+    def device_bytes(self) -> int:
+        """bytes of device memory the library's handle owns (rsrgan_device_bytes); torch's own tensors are not in it"""
+        n = C.c_int64()
+        check(self.lib.rsrgan_device_bytes(self.h, C.byref(n)))
+        return n.value
 
     # -- plumbing ----------------------------------------------------------------------
     @contextlib.contextmanager
@@ -245,12 +260,14 @@ class HipEngine:
         torch.cuda.current_stream(self.device).synchronize()        # `t` may be a temporary
 
     def get_grads(self, net: int) -> torch.Tensor:
+        self._training_only('get_grads')
         out = torch.empty(self.param_count(net), dtype=torch.float32, device=self.device)
         check(self.lib.rsrgan_get_grads(self.h, net, _ptr(out), self._stream()))
         return out
 
     def grad_view(self, net: int) -> torch.Tensor:
         """Zero-copy torch view of the library's (padded, flat) gradient buffer."""
+        self._training_only('grad_view')
         if net not in self._grad_views:
             p, n = C.c_void_p(), C.c_int64()
             check(self.lib.rsrgan_grad_buffer(self.h, net, C.byref(p), C.byref(n)))
@@ -259,6 +276,7 @@ class HipEngine:
 
     def grad_buckets(self, net: int) -> List[Tuple[int, int]]:
         """(offset, count) float ranges of the gradient buffer in the order the backward completes them."""
+        self._training_only('grad_buckets')
         out = []
         for i in range(self.lib.rsrgan_grad_bucket_count(self.h, net)):
             off, cnt = C.c_int64(), C.c_int64()
@@ -374,6 +392,7 @@ class HipEngine:
         return y
 
     def d_backward(self, x, lab, lengths, noise_real=None, noise_fake=None, train=True, apply=False) -> torch.Tensor:
+        self._training_only("d_backward")
         if os.environ.get("RSRGAN_DPIPE", "0") not in ("", "0"):      # the library reads labels / lengths ahead of the stream: hand it complete ones
             lab = self.upload_ready(lab)
             lengths = self.upload_ready(lengths, int32=True) if lengths is not None else None
@@ -392,6 +411,7 @@ class HipEngine:
         return out
 
     def g_backward(self, x, lab, lengths, noise_fake=None, train=True, reuse=False, apply=False) -> torch.Tensor:
+        self._training_only("g_backward")
         x, lab = self._f32(x), self._f32(lab)
         ln = self._i32(lengths) if lengths is not None else None
         nf = self._noise(noise_fake)
@@ -407,6 +427,7 @@ class HipEngine:
         return out
 
     def apply(self, net: int):
+        self._training_only('apply')
         check(self.lib.rsrgan_apply(self.h, net, self._stream()))
 
     def profile_begin(self):
@@ -435,6 +456,7 @@ class HipEngine:
 
     def set_dropout(self, keep_prob, seed=0):
         """tf.nn.dropout(h, keep_prob) after every hidden ReLU of the frame-level nets (dnn.py:116-121); `seed` = mask stream"""
+        self._training_only("set_dropout")
         check(self.lib.rsrgan_set_dropout(self.h, float(keep_prob), int(seed) & 0xFFFFFFFFFFFFFFFF))
 
     def profile_launches(self):

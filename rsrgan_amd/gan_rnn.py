@@ -83,8 +83,16 @@ class Model(object):
         host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
         return model_summaries([float(v) for v in list(host(d).reshape(-1)) + list(host(g).reshape(-1))], host(x), host(lab), host(y))
 
+    inference_only = False           # GAN_RNN(..., inference_only=True): the generator's variables only, forward calls only
+
+    def _training_only(self, what):
+        if self.inference_only:
+            raise RuntimeError("%s: this model is inference-only (inference_only=True): it holds the generator's variables alone, "
+                               "no discriminator, no optimizer state" % what)
+
     def save(self, save_dir, step):
         """rank 0 writes; every rank returns once the checkpoint exists (or raises if rank 0 could not write it)"""
+        self._training_only("save")
         os.makedirs(save_dir, exist_ok=True)
         return rdist.run_on_rank0(lambda: self._save_rank0(save_dir, step), self.process_group)
 
@@ -140,6 +148,19 @@ class Model(object):
         if not os.path.exists(path):
             return False
         data = np.load(path)
+        if self.inference_only:
+            # the G variables alone (their shadow names with moving_average, as below); D, Adam and EMA keys of the file are not read
+            table = self.engine.tensor_table(NET_G)
+            key = lambda name: name + "/ExponentialMovingAverage" if moving_average and not _bn_statistic(name) else name
+            if moving_average and not all(key(name) in data for name, _, _ in table):
+                print("[!] {} holds no ExponentialMovingAverage variables".format(ckpt_name))
+                return False
+            flat = np.zeros(self.engine.param_count(NET_G), np.float32)
+            for name, shape, off in table:
+                flat[off:off + int(np.prod(shape))] = data[key(name)].reshape(-1)
+            self.engine.set_params(NET_G, flat, "variables")
+            print("[*] Read {}".format(ckpt_name))
+            return True
         if moving_average and not all((name + "/ExponentialMovingAverage") in data
                                       for net in (NET_G, NET_D) for name, _, _ in self.engine.tensor_table(net)):
             print("[!] {} holds no ExponentialMovingAverage variables".format(ckpt_name))
@@ -186,9 +207,17 @@ class GAN_RNN(Model):
 
     def __init__(self, sess, args, devices, cross_validation=False, infer=False, name="GAN_RNN", *,
                  max_frames: Optional[int] = None, engine=None, process_group=None, seed: int = 4321,
-                 net_overrides: Optional[dict] = None, share_engine_from: Optional["GAN_RNN"] = None):
+                 net_overrides: Optional[dict] = None, share_engine_from: Optional["GAN_RNN"] = None,
+                 inference_only: bool = False):
         super(GAN_RNN, self).__init__(name)
         self.sess = sess
+        # inference_only: the decode model as the reference builds it with infer=True (gan_rnn_placeholder.py:133-135: the generator
+        # alone) -- an engine without discriminator, optimizer state and BPTT stash (HipEngine(inference=True)); forward, forward_stream
+        # and load work, save / d_step / g_step raise.  (`infer` alone keeps building the full model: DESIGN.md 6n.)
+        self.inference_only = bool(inference_only)
+        if self.inference_only and share_engine_from is not None:
+            raise ValueError("inference_only: an inference-only model does not share a training model's engine")
+        cross_validation = cross_validation or self.inference_only
         self.cross_validation = cross_validation
         self.MOVING_AVERAGE_DECAY = 0.9999
         self.max_grad_norm = 15
@@ -224,7 +253,8 @@ class GAN_RNN(Model):
             from .engine_hip import HipEngine                # raises if the HIP library / GPU is missing
             self.engine = HipEngine(batch_size=self.batch_size, max_frames=max_frames or 1000, input_dim=din,
                                     output_dim=self.output_dim, g_type=self.g_type, l2_scale=self.l2_scale,
-                                    cross_validation=cross_validation, seed=seed, **(net_overrides or {}))
+                                    cross_validation=cross_validation, seed=seed,
+                                    **dict(net_overrides or {}, **({"inference": True} if self.inference_only else {})))
         self.ema_enabled = getattr(self.engine, "ema_enabled", True)
         self._scalars = {}
         if share_engine_from is None:
@@ -302,6 +332,7 @@ class GAN_RNN(Model):
             return self._d_step(inputs, labels, lengths, noise_real, noise_fake, train, sync, gather)
 
     def _d_step(self, inputs, labels, lengths, noise_real, noise_fake, train, sync, gather):
+        self._training_only("d_step")
         x, lab, ln = self._shard(inputs), self._shard(labels), self._shard(lengths)
         nr = self._shard(noise_real) if noise_real is not None else self._draw_noise()
         nf = self._shard(noise_fake) if noise_fake is not None else self._draw_noise()
@@ -326,6 +357,7 @@ class GAN_RNN(Model):
             return self._g_step(inputs, labels, lengths, noise_fake, train, reuse_g_forward, sync, gather)
 
     def _g_step(self, inputs, labels, lengths, noise_fake, train, reuse_g_forward, sync, gather):
+        self._training_only("g_step")
         x, lab, ln = self._shard(inputs), self._shard(labels), self._shard(lengths)
         nf = self._shard(noise_fake) if noise_fake is not None else self._draw_noise()
         train = train and not self.cross_validation
@@ -374,6 +406,8 @@ class GAN_RNN(Model):
         """d_vars / g_vars split by name prefix with the reference's asserts (:301-317)."""
         self.g_vars_dict, self.d_vars_dict = {}, {}
         for net, dst, pre in ((NET_G, self.g_vars_dict, "g_"), (NET_D, self.d_vars_dict, "d_")):
+            if net == NET_D and self.inference_only:
+                continue
             flat = self.engine.get_params(net, "variables").cpu().numpy()
             for name, shape, off in self.engine.tensor_table(net):
                 assert name.startswith(pre), name
@@ -385,7 +419,7 @@ class GAN_RNN(Model):
         restarts from the injected values, as ExponentialMovingAverage.apply initialises it from the
         variable's initial value (:185-186)."""
         for net, vals in ((NET_G, g_vars), (NET_D, d_vars)):
-            if vals is None:
+            if vals is None or (net == NET_D and self.inference_only):
                 continue
             flat = np.zeros(self.engine.param_count(net), np.float32)
             for name, shape, off in self.engine.tensor_table(net):

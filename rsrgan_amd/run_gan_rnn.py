@@ -63,6 +63,8 @@ def build_parser():
                    "in chunks that carry the generator's state (0: one whole utterance per call, at most max_frames)")
     p.add_argument("--decode_streams", type=int, default=1, help="decode with --decode_chunk: utterances decoded side by side, one per "
                    "batch row")
+    p.add_argument("--decode_lean", default=False, action="store_true", help="decode on an inference-only model (inference_only=True: "
+                   "the generator alone, no BPTT stash)")
     return p
 
 
@@ -165,7 +167,8 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
     # (--decode_chunk N: the handle holds N frames of `streams` rows; an utterance is a sequence of calls that carry the state)
     mk = model_factory or (lambda: GAN_RNN(None, argparse.Namespace(**dict(vars(FLAGS), batch_size=streams if chunk > 0 else 1)),
                                            ["gpu:%d" % rdist.rank()], cross_validation=True, infer=True,
-                                           max_frames=chunk if chunk > 0 else FLAGS.max_frames, net_overrides=net_overrides))
+                                           max_frames=chunk if chunk > 0 else FLAGS.max_frames, net_overrides=net_overrides,
+                                           **({"inference_only": True} if getattr(FLAGS, "decode_lean", False) else {})))
     model = mk()
     if model.load(model.save_dir, moving_average=False):
         log("[*] Load SUCCESS")

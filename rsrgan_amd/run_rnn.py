@@ -52,6 +52,8 @@ def build_parser():
     p.add_argument("--max_frames", type=int, default=3000, help="capacity of the padded time axis")
     p.add_argument("--decode_chunk", type=int, default=0, help="decode: frames per forward call (run_gan_rnn --decode_chunk)")
     p.add_argument("--decode_streams", type=int, default=1, help="decode with --decode_chunk: utterances decoded side by side")
+    p.add_argument("--decode_lean", default=False, action="store_true", help="decode on an inference-only model (inference_only=True: "
+                   "the generator alone, no BPTT stash)")
     return p
 
 
@@ -167,7 +169,8 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
     """decode (:89-176) = run_gan_rnn.decode on an RNNTrainer: batch 1 (or --decode_streams rows of --decode_chunk frames)"""
     chunk, streams = int(getattr(FLAGS, "decode_chunk", 0) or 0), max(1, int(getattr(FLAGS, "decode_streams", 1) or 1))
     mk = model_factory or (lambda: _model(argparse.Namespace(**dict(vars(FLAGS), batch_size=streams if chunk > 0 else 1)), True, None,
-                                          net_overrides, max_frames=chunk if chunk > 0 else FLAGS.max_frames))
+                                          net_overrides, max_frames=chunk if chunk > 0 else FLAGS.max_frames,
+                                          **({"inference_only": True} if getattr(FLAGS, "decode_lean", False) else {})))
     return gan_loop.decode(FLAGS, model_factory=mk, log=log)
 
 

@@ -37,7 +37,7 @@ class RNNTrainer(GAN_RNN):
 
     def __init__(self, sess, args, devices, inputs=None, labels=None, lengths=None, cross_validation=False,
                  name="RNNTrainer", *, max_frames: Optional[int] = None, engine=None, process_group=None, seed: int = 4321,
-                 net_overrides: Optional[dict] = None, share_engine_from=None):
+                 net_overrides: Optional[dict] = None, share_engine_from=None, inference_only: bool = False):
         if getattr(args, "g_type", None) == "bnlstm":
             if getattr(args, "batch_norm", False):
                 raise NotImplementedError("bnlstm: the input FC's batch_norm (renorm) is not built")
@@ -49,7 +49,7 @@ class RNNTrainer(GAN_RNN):
         ov["flags"] = ov.get("flags", FLAG_WAVEFRONT) | FLAG_SUPERVISED
         super(RNNTrainer, self).__init__(sess, _Args(args, init_mse_weight=1.0), devices, cross_validation=cross_validation,
                                          name=name, max_frames=max_frames, engine=engine, process_group=process_group, seed=seed,
-                                         net_overrides=ov, share_engine_from=share_engine_from)
+                                         net_overrides=ov, share_engine_from=share_engine_from, inference_only=inference_only)
 
     def d_step(self, *a, **k):
         raise RuntimeError("RNNTrainer has no discriminator (models/rnn_trainer.py)")

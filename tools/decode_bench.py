@@ -2,7 +2,7 @@
 """Decode throughput and streaming latency of the sequence generators, one JSON line per configuration.
 
     python tools/decode_bench.py [--g_type res_lstm_l] [--utts 256] [--min_frames 200] [--max_frames 1500] [--repeats 3]
-                                 [--configs a,b,c,d,live] [--lib path/to/librsrgan_hip.so]
+                                 [--configs a,b,c,d,live] [--lib path/to/librsrgan_hip.so] [--lean]
 
 A seeded synthetic test set (utterance lengths uniform in [min_frames, max_frames], N(0,1) features, the handle's initial
 variables) goes through
@@ -16,7 +16,8 @@ variables) goes through
 
 and reports utterances/s and frames/s of every repeat (host wall clock around the whole set, device drained at the end: the
 copies of the inputs and outputs are part of decoding).  `--lib`: time another build of the library (configuration a only
-makes sense for a build without the stateful forward)."""
+makes sense for a build without the stateful forward).  `--lean`: every configuration on an inference-only model
+(GAN_RNN(inference_only=True): the generator alone, no BPTT stash); the records carry "lean": true."""
 from __future__ import annotations
 
 import argparse
@@ -33,11 +34,11 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def build(g_type, batch, frames, din, dout):
+def build(g_type, batch, frames, din, dout, lean=False):
     from rsrgan_amd import GAN_RNN
     args = SimpleNamespace(batch_size=batch, input_dim=din, output_dim=dout, left_context=0, right_context=0, g_type=g_type,
                            keep_prob=1.0, batch_norm=False, num_gpu=1, save_dir=None, l2_scale=0.0)
-    return GAN_RNN(None, args, ["gpu:0"], cross_validation=True, infer=True, max_frames=frames)
+    return GAN_RNN(None, args, ["gpu:0"], cross_validation=True, infer=True, max_frames=frames, **({"inference_only": True} if lean else {}))
 
 
 def main(argv=None):
@@ -53,6 +54,7 @@ def main(argv=None):
     p.add_argument("--output_dim", type=int, default=40)
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--lib", default=None)
+    p.add_argument("--lean", default=False, action="store_true", help="run the configurations on an inference-only model")
     a = p.parse_args(argv)
     if a.lib:
         from rsrgan_amd import _lib
@@ -60,13 +62,13 @@ def main(argv=None):
         import ctypes
 
         class OlderBuild(ctypes.CDLL):
-            """a build from before the stateful forward lacks its entry points: the binding may still set their argtypes (on a stand-in
-            that nothing calls: configuration a uses rsrgan_forward_g only)"""
+            """a build from before the stateful forward (or before rsrgan_device_bytes) lacks those entry points: the binding may still set
+            their argtypes (on a stand-in that nothing calls: configuration a uses rsrgan_forward_g only)"""
             def __getattr__(self, name):
                 try:
                     return super().__getattr__(name)
                 except AttributeError:
-                    if name.startswith("rsrgan_g_state_") or name == "rsrgan_forward_g_stream":
+                    if name.startswith("rsrgan_g_state_") or name in ("rsrgan_forward_g_stream", "rsrgan_device_bytes"):
                         return SimpleNamespace()
                     raise
         _lib.C.CDLL = OlderBuild
@@ -76,7 +78,7 @@ def main(argv=None):
     utts = [rng.standard_normal((int(n), a.input_dim)).astype(np.float32) for n in lens]
     frames = int(lens.sum())
     base = dict(g_type=a.g_type, utterances=a.utts, frames=frames, min_frames=a.min_frames, max_frames=a.max_frames,
-                device=torch.cuda.get_device_name(0), lib=a.lib or "built")
+                device=torch.cuda.get_device_name(0), lib=a.lib or "built", lean=bool(a.lean))
 
     def report(name, extra, secs):
         rec = dict(base, config=name, **extra)
@@ -99,7 +101,7 @@ def main(argv=None):
 
     for name in [c.strip() for c in a.configs.split(",") if c.strip()]:
         if name == "a":
-            model = build(a.g_type, 1, a.max_frames, a.input_dim, a.output_dim)
+            model = build(a.g_type, 1, a.max_frames, a.input_dim, a.output_dim, a.lean)
 
             def whole():
                 for u in utts:
@@ -108,7 +110,7 @@ def main(argv=None):
         elif name in ("b", "c", "d"):
             from rsrgan_amd.stream import decode_streams
             streams = {"b": 1, "c": 32, "d": 64}[name]
-            model = build(a.g_type, streams, a.chunk, a.input_dim, a.output_dim)
+            model = build(a.g_type, streams, a.chunk, a.input_dim, a.output_dim, a.lean)
 
             def chunked():
                 n = sum(1 for _ in decode_streams(model, iter(utts), a.chunk, streams))
@@ -116,7 +118,7 @@ def main(argv=None):
             report(name, dict(batch_size=streams, chunk=a.chunk, streams=streams), timed(chunked))
         elif name == "live":
             from rsrgan_amd.stream import StreamEnhancer
-            model = build(a.g_type, 1, 100, a.input_dim, a.output_dim)
+            model = build(a.g_type, 1, 100, a.input_dim, a.output_dim, a.lean)
             enh = StreamEnhancer(model, None, 0, 0, chunk=100)
             long_utt = rng.standard_normal((3000, a.input_dim)).astype(np.float32)
             out = {}
