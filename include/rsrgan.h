@@ -412,6 +412,66 @@ int rsrgan_op_bn_commit(int32_t n, float* const* vars, const float* const* stat,
  * after calls 1 .. n-1; backward: call n-1) */
 int rsrgan_op_bn_last_plan(int32_t out[16]);
 
+/* ---- the SEGAN operators (csrc/segan.hip and the window-GEMM primitives of csrc/segan.cpp).  Unit parity tests only
+ * (tests/test_gpu_segan_ops.py, tests/test_op_args.py); no trainer calls them.  Each goes through the host function SeganModel calls
+ * and never launches a kernel directly.  One entry per family: op selects the launcher; ptrs is a HOST table of device pointers,
+ * dims a HOST table of sizes and fl of float parameters, in the order listed ("?" = may be NULL; fl may be NULL where none is listed).
+ * Tensors are channels-last [rows = batch x position][channels] fp32.  A null table or required pointer, a misaligned pointer
+ * (16 bytes where a kernel moves float4: X, W, Z, dZ, dW, pad, t0, t1, Wt of conv2; z, dz of conv1; S of tconv1; a, b, coef, scratch of
+ * colred; pad_rows and interleave operands; 4 bytes elsewhere), a size below 1 (or below 0 for offsets and pads) or above the entry's
+ * limit, a leading dimension below its row, a channel count the kernel cannot take, or a scratch below the launcher's need returns
+ * RSRGAN_ERR_INVALID before the first HIP call, rsrgan_last_error() naming it: a shape a launcher would abort on is never launched.
+ *
+ * rsrgan_op_segan_sizes (no device): kind 0, dims Bn, L, C, k: out[0] = the pad floats SeganModel::init gives a conv2_fwd / conv2_wgrad
+ * of that layer (its + 64 included).  kind 1, dims Bn, Ls, Cs, Lt, Ct, k (tconv2): out = pad floats, t0 / t1 floats, Wt[0] floats,
+ * Wt[1] floats, pl, i0[0], i0[1], Q[0], Q[1], pf, pb.  kind 2, dims k, C: out[0] = 1 if launch_conv1_wgrad's kernel takes the shape
+ * (k * C <= 1024, C % 4 == 0), out[1] = its dynamic LDS in bytes.  kind 3, dims C, P: the least scratch of launch_colred. */
+int rsrgan_op_segan_sizes(int32_t kind, const int64_t* dims, int64_t out[12]);
+/* a bare SeganModel holding exactly pad, t0, t1 and the GEMM workspace (16 Mi floats, the model's), then the method itself.
+ * op 0 conv2_fwd:   ptrs X, W, bias?, Z, pad;  dims Bn, L, Cin, k, Cout, ldw, pad_floats.  Z [Bn * ceil(L/2)][Cout] = stride-2 SAME conv.
+ * op 1 conv2_wgrad: ptrs X, dZ, dW, pad;  dims Bn, L, Cin, k, Cout, ldz, ldw, pad_floats.  dW [k * Cin][ldw].
+ * op 2 tconv2:      ptrs S, W, bias?, T, pad, t0, t1, Wt0, Wt1;  dims Bn, Ls, Cs, Lt, k, Ct, ldw, pad_floats, t_floats, wt0_floats,
+ *                   wt1_floats.  W [k * Ct][ldw] with Cs columns is the filter of the downconv Ct -> Cs whose data gradient (= the
+ *                   deconv Cs -> Ct) T [Bn * Lt][Ct] is; Wt0 / Wt1 are prepared from it by launch_prep_tconv_many as refresh_weights
+ *                   does.  Lt is 2 Ls or 2 Ls - 1.  pad_floats, t_floats, wt*_floats at least rsrgan_op_segan_sizes'. */
+int rsrgan_op_segan_conv2(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream);
+/* the single-channel ends.
+ * op 0 launch_conv1_fwd:   ptrs x, W, bias?, z;  dims B, L, k, C, ldx, ldw, ldz (C % 16 == 0).
+ * op 1 launch_conv1_wgrad: ptrs x, dz, dW, scratch;  dims B, L, k, C, ldx, ldz, ldw, scratch_floats (>= B * k * C; k * C <= 1024;
+ *                          refused too when the kernel's LDS exceeds the device's, asked once after the argument checks).
+ * op 2 launch_tconv1:      ptrs S, W, bias?, t;  dims B, Ls, C, Lt, k, lds, ldw, ldt. */
+int rsrgan_op_segan_conv1(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream);
+/* launch_colred, mode 0..3: ptrs a, b?, coef?, out, scratch;  dims lda, coff, ldb, C, rows_per, P, ldcoef, ldo, accumulate,
+ * scratch_floats (>= P * 2 * C: refused below, the chunk doubles above);  fl leak.  b: modes 1, 3; coef [P * 8][ldcoef]: mode 3. */
+int rsrgan_op_segan_colred(int32_t mode, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream);
+/* what the calling thread's last launch_colred launched: out = { 1 if the 16-byte form k_colred_part4 (0: k_colred_part), mode, rows per
+ * chunk, chunks per pass, grid of the partial kernel, 0.. } */
+int rsrgan_op_segan_last_plan(int32_t out[8]);
+/* virtual batch norm; every op: dims C, rows_per, P, ldc, then its own.
+ * op 0 launch_vbn_coef:      ptrs sums, gamma, beta, ref_coef?, coef;  dims .., lds, B;  fl eps
+ * op 1 launch_vbn_apply:     ptrs h, coef, y;  fl leak
+ * op 2 launch_vbn_bwd_coef:  ptrs sums, gamma, coef, dgamma?, dbeta? (both or none);  dims .., lds, B, first_live, accumulate
+ * op 3 launch_vbn_bwd_apply: ptrs h, dy, coef, dh;  fl leak */
+int rsrgan_op_segan_vbn(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream);
+/* layout, elementwise, losses, optimizer.
+ * op 0 launch_pad_rows:     ptrs src, dst;  dims B, L, C, pf, pb
+ * op 1 launch_prep_tconv:   ptrs W, dst;  dims 1, ldw, nb, na, e, ne, ldd
+ * op 2 launch_prep_tconv_many, 44 jobs to a launch as refresh_weights: ptrs (W, dst) per job;  dims n, then ldw, nb, na, e, ne, ldd per job
+ * op 3 launch_interleave:   ptrs T0, T1, bias?, T;  dims Q0, Q1, i00, i01, pl, B, Lt, C (i0 and Q must agree with pl and Lt)
+ * op 4 launch_act_fwd:      ptrs z, alpha? (NULL: leaky), out;  dims C, ldo, coff, rows;  fl leak
+ * op 5 launch_act_bwd:      ptrs dy, z, alpha?, extra?, dz;  dims ldy, coff, C, rows;  fl leak
+ * op 6 launch_copy_cols:    ptrs src, dst;  dims lds, soff, ldd, doff, C, rows, accumulate
+ * op 7 launch_build_joint1: ptrs x, tail, noise?, joint;  dims Lx, U, B
+ * op 8 launch_sum_all:      ptrs src, out, scratch (256 floats);  dims rows, cols, ld
+ * op 9 launch_segan_lsgan:  ptrs logits, dlogits?, loss3;  dims B, mode, fake_pass, P
+ * op 10 launch_segan_l1:    ptrs G, labels, lambda, dG?, loss3;  dims n, accumulate
+ * op 11 launch_rmsprop:     ptrs w, g, ms, lr;  dims n;  fl decay, eps */
+int rsrgan_op_segan_elem(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream);
+/* the discriminator's head; dims R, Ld, C, k, ldfc.
+ * op 0 launch_dhead_fwd: ptrs h, W, wfc, bfc, conv_out, logits
+ * op 1 launch_dhead_bwd: ptrs dlogit, h, conv_out, W, wfc, dW?, dwfc?, dbfc? (all three or none), dh */
+int rsrgan_op_segan_dhead(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream);
+
 /* ---- SEGAN-style conv G/D (models/segan.py:SEGAN with generator.py:AEGenerator, discriminator.py:discriminator, utils/bnorm.py:VBN;
  * BASELINE.json configs[4]).  The reference's trainer cannot run as shipped (segan.py:136 calls an undefined variables_on_gpu0(),
  * scripts/train_segan.py:20 imports a missing module); the graph it would build is fully specified and is what these entry

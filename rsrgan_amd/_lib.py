@@ -29,6 +29,8 @@ SYMBOLS = ["rsrgan_default_cfg", "rsrgan_create", "rsrgan_destroy", "rsrgan_last
            "rsrgan_op_lstm_colsums", "rsrgan_op_colsum", "rsrgan_version",
            "rsrgan_op_conv_fwd", "rsrgan_op_conv_wgrad", "rsrgan_op_conv_ws_floats", "rsrgan_op_conv_supported", "rsrgan_op_conv_last_plan",
            "rsrgan_op_bn_forward", "rsrgan_op_bn_backward", "rsrgan_op_bn_commit", "rsrgan_op_bn_last_plan",
+           "rsrgan_op_segan_sizes", "rsrgan_op_segan_conv2", "rsrgan_op_segan_conv1", "rsrgan_op_segan_colred", "rsrgan_op_segan_last_plan",
+           "rsrgan_op_segan_vbn", "rsrgan_op_segan_elem", "rsrgan_op_segan_dhead",
            "rsrgan_segan_default_cfg", "rsrgan_segan_create", "rsrgan_segan_destroy", "rsrgan_segan_set_scalar",
            "rsrgan_segan_num_tensors", "rsrgan_segan_tensor_info", "rsrgan_segan_param_count", "rsrgan_segan_get_params",
            "rsrgan_segan_set_params", "rsrgan_segan_forward_g", "rsrgan_segan_d_backward", "rsrgan_segan_g_backward",
@@ -124,6 +126,11 @@ def load():
     lib.rsrgan_op_bn_backward.argtypes = [p, i32, p, i32, p, i32, i32, i32, i32, p, i32, p, p, i32, i32, p, p, i64, vp]
     lib.rsrgan_op_bn_commit.argtypes = [i32, pp, pp, C.POINTER(i32), i32, vp]
     lib.rsrgan_op_bn_last_plan.argtypes = [C.POINTER(i32)]
+    lib.rsrgan_op_segan_sizes.argtypes = [i32, C.POINTER(i64), C.POINTER(i64)]
+    for f in (lib.rsrgan_op_segan_conv2, lib.rsrgan_op_segan_conv1, lib.rsrgan_op_segan_colred, lib.rsrgan_op_segan_vbn, lib.rsrgan_op_segan_elem,
+              lib.rsrgan_op_segan_dhead):
+        f.argtypes = [i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_float), vp]
+    lib.rsrgan_op_segan_last_plan.argtypes = [C.POINTER(i32)]
     lib.rsrgan_segan_default_cfg.argtypes = [C.POINTER(SeganCfg)]
     lib.rsrgan_segan_create.argtypes = [C.POINTER(SeganCfg), C.c_uint64, C.POINTER(vp)]
     lib.rsrgan_segan_destroy.argtypes = [vp]
@@ -159,6 +166,13 @@ CONV_PLAN_FIELDS = ("family", "a0", "a1", "a2", "branch", "TW", "FB", "gx", "gy"
 # rsrgan_op_bn_last_plan: routes and the fields of the record; the order of the eight variables of a layer
 BN_ROUTES = {0: "none", 1: "small", 2: "sliced", 3: "narrow"}
 BN_PLAN_FIELDS = ("route", "backward", "calls", "launches", "slices", "per", "pgx", "pgy", "egrid", "q", "R")
+# rsrgan_op_segan_*: the op codes of each family and the fields of the column-reduction record
+SEGAN_OPS = {"conv2": ("conv2_fwd", "conv2_wgrad", "tconv2"), "conv1": ("conv1_fwd", "conv1_wgrad", "tconv1"),
+             "colred": ("sum", "dalpha", "moments", "vbn_bwd"), "vbn": ("coef", "apply", "bwd_coef", "bwd_apply"),
+             "elem": ("pad_rows", "prep_tconv", "prep_tconv_many", "interleave", "act_fwd", "act_bwd", "copy_cols", "build_joint1", "sum_all",
+                      "lsgan", "l1", "rmsprop"),
+             "dhead": ("fwd", "bwd")}
+SEGAN_PLAN_FIELDS = ("vec", "mode", "chunk", "chunks_per", "grid")
 BN_VARS = ("beta", "gamma", "moving_mean", "moving_variance", "renorm_mean", "renorm_mean_weight", "renorm_stddev", "renorm_stddev_weight")
 
 

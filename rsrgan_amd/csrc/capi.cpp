@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "model.h"
+#include "segan.h"
 
 using namespace rsr;
 
@@ -838,5 +839,351 @@ int rsrgan_op_bn_last_plan(int32_t out[16]) {
   for (int i = 0; i < 16; ++i) out[i] = i < 11 ? v[i] : 0;
   return RSRGAN_OK;
 }
+
+// ---- the SEGAN operators (segan.hip, and the window-GEMM primitives of segan.cpp) through the host functions SeganModel calls, on
+// caller-owned buffers (tests/test_gpu_segan_ops.py).  One entry per family: op selects the launcher, ptrs is a HOST table of device
+// pointers, dims a host table of sizes, fl of float parameters, each in the order include/rsrgan.h lists.
+#define SG_DIM(name, v, lo) OP_REFUSE((v) < (lo) || (v) > ((int64_t)1 << 30), WHO ": %s = %lld outside %d .. 2^30", name, (long long)(v), (int)(lo))
+#define SG_PTR(name, ptr, align) do { OP_REFUSE(!(ptr), WHO ": null pointer (%s)", name); \
+                                      OP_REFUSE((size_t)(ptr) & ((align) - 1), WHO ": %s not %d-byte aligned", name, (int)(align)); } while (0)
+#define SG_OPT(name, ptr, align) OP_REFUSE((size_t)(ptr) & ((align) - 1), WHO ": %s not %d-byte aligned", name, (int)(align))
+#define SG_LD(name, ld, need) OP_REFUSE((ld) < (need) || (ld) > ((int64_t)1 << 30), WHO ": leading dimension %s = %lld below its row of %lld (or above 2^30)", name, (long long)(ld), (long long)(need))
+#define SG_FLAG(name, v) OP_REFUSE((v) < 0 || (v) > 1, WHO ": %s = %lld is neither 0 nor 1", name, (long long)(v))
+#define SG_MUL4(name, v) OP_REFUSE((v) & 3, WHO ": %s = %lld is not a multiple of 4", name, (long long)(v))
+#define SG_TABLES(nf) OP_REFUSE(!ptrs || !dims || ((nf) && !fl), WHO ": null table (ptrs, dims, or fl for an op that takes floats)")
+#define SG_LAUNCHED() do { if (hipGetLastError() != hipSuccess) { set_error(WHO " launch failed"); return RSRGAN_ERR_HIP; } return RSRGAN_OK; } while (0)
+#define FP(i) ((float*)ptrs[i])
+static const size_t g_segan_ws_floats = (size_t)16 << 20;        // SeganModel::gemm_ws_floats
+
+#define WHO "op_segan_sizes"
+int rsrgan_op_segan_sizes(int32_t kind, const int64_t* dims, int64_t out[12]) {
+  OP_REFUSE(!dims || !out, WHO ": null pointer");
+  OP_REFUSE(kind < 0 || kind > 3, WHO ": kind = %d outside 0 .. 3", kind);
+  for (int i = 0; i < 12; ++i) out[i] = 0;
+  const int64_t* d = dims;
+  if (kind == 0) {                                       // conv2_fwd / conv2_wgrad: Bn, L, C, k
+    for (int i = 0; i < 4; ++i) SG_DIM("a size", d[i], 1);
+    out[0] = (int64_t)(conv2_pad_floats((int)d[0], (int)d[1], (int)d[2], (int)d[3]) + SEGAN_SCRATCH_SLACK);
+  } else if (kind == 1) {                                // tconv2: Bn, Ls, Cs, Lt, Ct, k
+    for (int i = 0; i < 6; ++i) SG_DIM("a size", d[i], 1);
+    SG_DIM("k", d[5], 2);
+    const int Bn = (int)d[0], Ls = (int)d[1], Cs = (int)d[2], Lt = (int)d[3], Ct = (int)d[4], k = (int)d[5];
+    OP_REFUSE(Ls != (Lt + 1) / 2, WHO ": Ls = %d is not ceil(Lt / 2) of Lt = %d", Ls, Lt);
+    const TGeom g = tgeom(Ls, Lt, k);
+    out[0] = (int64_t)(tconv2_pad_floats(Bn, Ls, Cs, Lt, k) + SEGAN_SCRATCH_SLACK);
+    out[1] = (int64_t)(tconv2_t_floats(Bn, Ls, Lt, Ct, k) + SEGAN_SCRATCH_SLACK);
+    out[2] = (int64_t)g.ne[0] * Cs * pad4(Ct); out[3] = (int64_t)g.ne[1] * Cs * pad4(Ct);
+    out[4] = g.pl; out[5] = g.i0[0]; out[6] = g.i0[1]; out[7] = g.Q[0]; out[8] = g.Q[1]; out[9] = g.pf; out[10] = g.pb;
+  } else if (kind == 2) {                                // launch_conv1_wgrad: k, C -> shape accepted, LDS bytes (no device)
+    SG_DIM("k", d[0], 1); SG_DIM("C", d[1], 1);
+    out[0] = conv1_wgrad_shape_ok((int)d[0], (int)d[1]) ? 1 : 0;
+    out[1] = (int64_t)conv1_wgrad_lds_bytes((int)d[0], (int)d[1]);
+  } else {                                               // launch_colred: C, P -> the least scratch
+    SG_DIM("C", d[0], 1); SG_DIM("P", d[1], 1);
+    out[0] = (int64_t)colred_min_scratch((int)d[0], (int)d[1]);
+  }
+  return RSRGAN_OK;
+}
+#undef WHO
+
+#define WHO "op_segan_conv2"
+int rsrgan_op_segan_conv2(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream) {
+  (void)fl;
+  SG_TABLES(0);
+  OP_REFUSE(op < 0 || op > 2, WHO ": op = %d outside 0 (conv2_fwd), 1 (conv2_wgrad), 2 (tconv2)", op);
+  const int64_t* d = dims;
+  hipStream_t s = (hipStream_t)stream;
+  if (op == 0 || op == 1) {
+    // 0: ptrs X, W, bias (may be NULL), Z, pad;  dims Bn, L, Cin, k, Cout, ldw, pad_floats
+    // 1: ptrs X, dZ, dW, pad;                    dims Bn, L, Cin, k, Cout, ldz, ldw, pad_floats
+    SG_DIM("Bn", d[0], 1); SG_DIM("L", d[1], 1); SG_DIM("Cin", d[2], 1); SG_DIM("k", d[3], 1); SG_DIM("Cout", d[4], 1);
+    const int Bn = (int)d[0], L = (int)d[1], Cin = (int)d[2], k = (int)d[3], Cout = (int)d[4];
+    SG_MUL4("Cin", Cin); SG_MUL4("Cout", Cout);
+    OP_REFUSE((int64_t)Bn * (L + 2 * k) * Cin > (1 << 28) || (int64_t)k * Cin > (1 << 20), WHO ": Bn x (L + 2 k) x Cin above the entry's 2^28");
+    const int64_t pad_floats = op == 0 ? d[6] : d[7];
+    const size_t need = conv2_pad_floats(Bn, L, Cin, k) + SEGAN_SCRATCH_SLACK;
+    OP_REFUSE(pad_floats < 0 || (size_t)pad_floats < need, WHO ": pad of %lld floats below the %zu the model gives this layer", (long long)pad_floats, need);
+    if (op == 0) {
+      SG_PTR("X", ptrs[0], 16); SG_PTR("W", ptrs[1], 16); SG_OPT("bias", ptrs[2], 16); SG_PTR("Z", ptrs[3], 16); SG_PTR("pad", ptrs[4], 16);
+      SG_MUL4("ldw", d[5]); SG_LD("ldw", d[5], Cout);
+    } else {
+      SG_PTR("X", ptrs[0], 16); SG_PTR("dZ", ptrs[1], 16); SG_PTR("dW", ptrs[2], 16); SG_PTR("pad", ptrs[3], 16);
+      SG_MUL4("ldz", d[5]); SG_LD("ldz", d[5], Cout); SG_MUL4("ldw", d[6]); SG_LD("ldw", d[6], Cout);
+    }
+    float* ws = op_ws();
+    if (!ws) { set_error(WHO ": hipMalloc failed"); return RSRGAN_ERR_HIP; }
+    SeganModel m;                                          // bare: the primitives use pad, t0, t1 and the GEMM workspace only
+    m.gemm_ws = ws; m.gemm_ws_floats = g_segan_ws_floats;
+    m.pad = FP(op == 0 ? 4 : 3); m.pad_floats = (size_t)pad_floats;
+    if (op == 0) m.conv2_fwd(FP(0), Bn, L, Cin, k, FP(1), (int)d[5], FP(2), Cout, FP(3), s);
+    else m.conv2_wgrad(FP(0), Bn, L, Cin, k, FP(1), (int)d[5], Cout, FP(2), (int)d[6], s);
+    SG_LAUNCHED();
+  }
+  // 2: ptrs S, W, bias (may be NULL), T, pad, t0, t1, Wt0, Wt1;  dims Bn, Ls, Cs, Lt, k, Ct, ldw, pad_floats, t_floats, wt0_floats, wt1_floats
+  //    W [k * Ct][ldw] with Cs columns: the filter of the downconv Ct -> Cs whose data gradient this is (= a deconv Cs -> Ct)
+  SG_DIM("Bn", d[0], 1); SG_DIM("Ls", d[1], 1); SG_DIM("Cs", d[2], 1); SG_DIM("Lt", d[3], 1); SG_DIM("k", d[4], 2); SG_DIM("Ct", d[5], 1);
+  const int Bn = (int)d[0], Ls = (int)d[1], Cs = (int)d[2], Lt = (int)d[3], k = (int)d[4], Ct = (int)d[5];
+  SG_MUL4("Cs", Cs); SG_MUL4("Ct", Ct);
+  OP_REFUSE(Ls != (Lt + 1) / 2, WHO ": Ls = %d is not ceil(Lt / 2) of Lt = %d", Ls, Lt);
+  OP_REFUSE((int64_t)Bn * (Ls + 2 * k) * std::max(Cs, Ct) > (1 << 28) || (int64_t)k * Cs * Ct > (1 << 28), WHO ": Bn x (Ls + 2 k) x C above the entry's 2^28");
+  SG_MUL4("ldw", d[6]); SG_LD("ldw", d[6], Cs);
+  const char* names[9] = {"S", "W", "bias", "T", "pad", "t0", "t1", "Wt0", "Wt1"};
+  for (int i = 0; i < 9; ++i) { if (i == 2) SG_OPT(names[i], ptrs[i], 16); else SG_PTR(names[i], ptrs[i], 16); }
+  const TGeom g = tgeom(Ls, Lt, k);
+  const size_t need_pad = tconv2_pad_floats(Bn, Ls, Cs, Lt, k) + SEGAN_SCRATCH_SLACK, need_t = tconv2_t_floats(Bn, Ls, Lt, Ct, k) + SEGAN_SCRATCH_SLACK;
+  OP_REFUSE(d[7] < 0 || (size_t)d[7] < need_pad, WHO ": pad of %lld floats below the %zu the model gives this layer", (long long)d[7], need_pad);
+  OP_REFUSE(d[8] < 0 || (size_t)d[8] < need_t, WHO ": t0 / t1 of %lld floats below the %zu the model gives this layer", (long long)d[8], need_t);
+  for (int e = 0; e < 2; ++e)
+    OP_REFUSE(d[9 + e] < (int64_t)g.ne[e] * Cs * pad4(Ct), WHO ": Wt%d of %lld floats below ne x Cs x Ct = %lld", e, (long long)d[9 + e], (long long)g.ne[e] * Cs * pad4(Ct));
+  float* ws = op_ws();
+  if (!ws) { set_error(WHO ": hipMalloc failed"); return RSRGAN_ERR_HIP; }
+  SeganModel m;
+  m.gemm_ws = ws; m.gemm_ws_floats = g_segan_ws_floats;
+  m.pad = FP(4); m.pad_floats = (size_t)d[7]; m.t0 = FP(5); m.t1 = FP(6); m.t_floats = (size_t)d[8];
+  float* Wt[2] = {FP(7), FP(8)};
+  PrepTconvBatch pb(s);                                   // as SeganModel::refresh_weights prepares a downconv's data gradient
+  for (int e = 0; e < 2; ++e) pb.add(FP(1), (int)d[6], Ct, Cs, e, g.ne[e], Wt[e], pad4(Ct));
+  pb.flush();
+  m.tconv2(FP(0), Bn, Ls, Cs, Lt, k, Wt, g.ne, Ct, FP(2), FP(3), s);
+  SG_LAUNCHED();
+}
+#undef WHO
+
+#define WHO "op_segan_conv1"
+int rsrgan_op_segan_conv1(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream) {
+  (void)fl;
+  SG_TABLES(0);
+  OP_REFUSE(op < 0 || op > 2, WHO ": op = %d outside 0 (conv1_fwd), 1 (conv1_wgrad), 2 (tconv1)", op);
+  const int64_t* d = dims;
+  hipStream_t s = (hipStream_t)stream;
+  if (op == 0) {                                         // ptrs x, W, bias (may be NULL), z;  dims B, L, k, C, ldx, ldw, ldz
+    SG_DIM("B", d[0], 1); SG_DIM("L", d[1], 1); SG_DIM("k", d[2], 1); SG_DIM("C", d[3], 1);
+    OP_REFUSE(d[3] & 15, WHO ": C = %lld is not a multiple of 16 (k_conv1_fwd writes 16 channels at a time)", (long long)d[3]);
+    OP_REFUSE((d[2] + 1) * d[3] * 4 > (64 << 10), WHO ": (k + 1) x C floats of filter exceed 64 KB of LDS");
+    SG_PTR("x", ptrs[0], 4); SG_PTR("W", ptrs[1], 4); SG_OPT("bias", ptrs[2], 4); SG_PTR("z", ptrs[3], 16);
+    SG_LD("ldx", d[4], d[1]); SG_LD("ldw", d[5], d[3]); SG_LD("ldz", d[6], d[3]); SG_MUL4("ldz", d[6]);
+    launch_conv1_fwd(FP(0), (int)d[4], (int)d[0], (int)d[1], (int)d[2], FP(1), (int)d[5], FP(2), (int)d[3], FP(3), (int)d[6], s);
+    SG_LAUNCHED();
+  }
+  if (op == 1) {                                         // ptrs x, dz, dW, scratch;  dims B, L, k, C, ldx, ldz, ldw, scratch_floats
+    SG_DIM("B", d[0], 1); SG_DIM("L", d[1], 1); SG_DIM("k", d[2], 1); SG_DIM("C", d[3], 1);
+    OP_REFUSE(d[0] > 65535, WHO ": B = %lld above the grid's 65535", (long long)d[0]);
+    OP_REFUSE(!conv1_wgrad_shape_ok((int)d[2], (int)d[3]), WHO ": k x C = %lld above 1024 or C = %lld no multiple of 4: launch_conv1_wgrad has no kernel for it",
+              (long long)(d[2] * d[3]), (long long)d[3]);
+    SG_PTR("x", ptrs[0], 4); SG_PTR("dz", ptrs[1], 16); SG_PTR("dW", ptrs[2], 4); SG_PTR("scratch", ptrs[3], 4);
+    SG_LD("ldx", d[4], d[1]); SG_LD("ldz", d[5], d[3]); SG_MUL4("ldz", d[5]); SG_LD("ldw", d[6], d[3]);
+    OP_REFUSE(d[7] < d[0] * d[2] * d[3], WHO ": scratch of %lld floats below B x k x C = %lld (one partial per batch row)", (long long)d[7], (long long)(d[0] * d[2] * d[3]));
+    OP_REFUSE(!conv1_wgrad_supported((int)d[2], (int)d[3]), WHO ": %zu bytes of LDS above the device's %zu", conv1_wgrad_lds_bytes((int)d[2], (int)d[3]), device_lds_limit());
+    launch_conv1_wgrad(FP(0), (int)d[4], (int)d[0], (int)d[1], (int)d[2], FP(1), (int)d[5], (int)d[3], FP(2), (int)d[6], FP(3), (size_t)d[7], s);
+    SG_LAUNCHED();
+  }
+  // 2: ptrs S, W, bias (may be NULL), t;  dims B, Ls, C, Lt, k, lds, ldw, ldt
+  SG_DIM("B", d[0], 1); SG_DIM("Ls", d[1], 1); SG_DIM("C", d[2], 1); SG_DIM("Lt", d[3], 1); SG_DIM("k", d[4], 1);
+  SG_MUL4("C", d[2]);
+  OP_REFUSE(d[1] != (d[3] + 1) / 2, WHO ": Ls = %lld is not ceil(Lt / 2) of Lt = %lld", (long long)d[1], (long long)d[3]);
+  OP_REFUSE(d[4] * d[2] * 4 > (64 << 10), WHO ": k x C floats of filter exceed 64 KB of LDS");
+  SG_PTR("S", ptrs[0], 16); SG_PTR("W", ptrs[1], 4); SG_OPT("bias", ptrs[2], 4); SG_PTR("t", ptrs[3], 4);
+  SG_LD("lds", d[5], d[2]); SG_MUL4("lds", d[5]); SG_LD("ldw", d[6], d[2]); SG_LD("ldt", d[7], d[3]);
+  launch_tconv1(FP(0), (int)d[5], (int)d[0], (int)d[1], (int)d[2], (int)d[3], (int)d[4], FP(1), (int)d[6], FP(2), FP(3), (int)d[7], s);
+  SG_LAUNCHED();
+}
+#undef WHO
+
+#define WHO "op_segan_colred"
+int rsrgan_op_segan_colred(int32_t mode, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream) {
+  // ptrs a, b, coef, out, scratch;  dims lda, coff, ldb, C, rows_per, P, ldcoef, ldo, accumulate, scratch_floats;  fl leak
+  SG_TABLES(1);
+  OP_REFUSE(mode < 0 || mode > 3, WHO ": mode = %d outside 0 .. 3", mode);
+  const int64_t* d = dims;
+  const bool two = mode == 1 || mode == 3;
+  SG_DIM("C", d[3], 1); SG_DIM("rows_per", d[4], 1); SG_DIM("P", d[5], 1); SG_DIM("coff", d[1], 0); SG_FLAG("accumulate", d[8]);
+  OP_REFUSE(d[4] * d[5] > ((int64_t)1 << 30) || d[5] > 64, WHO ": P x rows_per above the entry's 2^30, or P above 64");
+  // 16 bytes wherever the sizes let launch_colred take the 16-byte form (it looks at the sizes, not at the pointers)
+  const int al = (d[3] % 4 == 0 && d[0] % 4 == 0 && d[1] % 4 == 0) ? 16 : 4;
+  SG_PTR("a", ptrs[0], al); SG_PTR("out", ptrs[3], 4); SG_PTR("scratch", ptrs[4], 16);
+  SG_LD("lda", d[0], d[1] + d[3]); SG_LD("ldo", d[7], d[3]);
+  if (two) { SG_PTR("b", ptrs[1], d[2] % 4 == 0 ? al : 4); SG_LD("ldb", d[2], d[3]); }
+  if (mode == 3) { SG_PTR("coef", ptrs[2], d[6] % 4 == 0 ? al : 4); SG_LD("ldcoef", d[6], d[3]); }
+  const size_t need = colred_min_scratch((int)d[3], (int)d[5]);
+  OP_REFUSE(d[9] < 0 || (size_t)d[9] < need, WHO ": scratch of %lld floats below the P x 2 x C = %zu of one chunk per pass", (long long)d[9], need);
+  launch_colred(mode, FP(0), (int)d[0], (int)d[1], FP(1), (int)d[2], (int)d[3], (size_t)d[4], (int)d[5], FP(2), (int)d[6], fl[0], FP(3), (int)d[7], d[8] != 0,
+                FP(4), (size_t)d[9], (hipStream_t)stream);
+  SG_LAUNCHED();
+}
+#undef WHO
+
+#define WHO "op_segan_last_plan"
+int rsrgan_op_segan_last_plan(int32_t out[8]) {
+  OP_REFUSE(!out, WHO ": null pointer");
+  const ColredPlanRecord& p = g_colred_last_plan;
+  const int v[5] = {p.vec, p.mode, p.chunk, p.chunks_per, p.grid};
+  for (int i = 0; i < 8; ++i) out[i] = i < 5 ? v[i] : 0;
+  return RSRGAN_OK;
+}
+#undef WHO
+
+#define WHO "op_segan_vbn"
+int rsrgan_op_segan_vbn(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream) {
+  SG_TABLES(0);
+  OP_REFUSE(op < 0 || op > 3, WHO ": op = %d outside 0 (vbn_coef), 1 (vbn_apply), 2 (vbn_bwd_coef), 3 (vbn_bwd_apply)", op);
+  const int64_t* d = dims;
+  OP_REFUSE(op != 2 && !fl, WHO ": null table (fl: eps or leak)");
+  hipStream_t s = (hipStream_t)stream;
+  // every op: dims C, rows_per, P, ldc, then its own
+  SG_DIM("C", d[0], 1); SG_DIM("rows_per", d[1], 1); SG_DIM("P", d[2], 1); SG_LD("ldc", d[3], d[0]);
+  OP_REFUSE(d[1] * d[2] * d[0] > ((int64_t)1 << 30) || d[2] > 64, WHO ": P x rows_per x C above the entry's 2^30, or P above 64");
+  const int C = (int)d[0], P = (int)d[2], ldc = (int)d[3];
+  const size_t rows_per = (size_t)d[1];
+  if (op == 0) {                                         // ptrs sums, gamma, beta, ref_coef (may be NULL), coef;  dims .., lds, B;  fl eps
+    SG_PTR("sums", ptrs[0], 4); SG_PTR("gamma", ptrs[1], 4); SG_PTR("beta", ptrs[2], 4); SG_OPT("ref_coef", ptrs[3], 4); SG_PTR("coef", ptrs[4], 4);
+    SG_LD("lds", d[4], C); SG_DIM("B", d[5], 1);
+    launch_vbn_coef(FP(0), (int)d[4], P, C, rows_per, (int)d[5], fl[0], FP(1), FP(2), FP(3), FP(4), ldc, s);
+  } else if (op == 1) {                                  // ptrs h, coef, y;  fl leak
+    SG_PTR("h", ptrs[0], 4); SG_PTR("coef", ptrs[1], 4); SG_PTR("y", ptrs[2], 4);
+    launch_vbn_apply(FP(0), C, rows_per, P, FP(1), ldc, fl[0], FP(2), s);
+  } else if (op == 2) {                                  // ptrs sums, gamma, coef, dgamma, dbeta (both may be NULL);  dims .., lds, B, first_live, accumulate
+    SG_PTR("sums", ptrs[0], 4); SG_PTR("gamma", ptrs[1], 4); SG_PTR("coef", ptrs[2], 4); SG_OPT("dgamma", ptrs[3], 4); SG_OPT("dbeta", ptrs[4], 4);
+    OP_REFUSE((ptrs[3] == nullptr) != (ptrs[4] == nullptr), WHO ": dgamma and dbeta must both be given or both be null");
+    SG_LD("lds", d[4], C); SG_DIM("B", d[5], 1);
+    OP_REFUSE(d[6] < 0 || d[6] > 1, WHO ": first_live = %lld outside 0 (all live) .. 1 (pass 0 is the reference)", (long long)d[6]);
+    SG_FLAG("accumulate", d[7]);
+    launch_vbn_bwd_coef(FP(0), (int)d[4], P, (int)d[6], C, rows_per, (int)d[5], FP(1), FP(2), ldc, FP(3), FP(4), d[7] != 0, s);
+  } else {                                               // ptrs h, dy, coef, dh;  fl leak
+    SG_PTR("h", ptrs[0], 4); SG_PTR("dy", ptrs[1], 4); SG_PTR("coef", ptrs[2], 4); SG_PTR("dh", ptrs[3], 4);
+    launch_vbn_bwd_apply(FP(0), FP(1), C, rows_per, P, FP(2), ldc, fl[0], FP(3), s);
+  }
+  SG_LAUNCHED();
+}
+#undef WHO
+
+#define WHO "op_segan_elem"
+int rsrgan_op_segan_elem(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream) {
+  SG_TABLES(0);
+  OP_REFUSE(op < 0 || op > 11, WHO ": op = %d outside 0 .. 11", op);
+  const int64_t* d = dims;
+  OP_REFUSE((op == 4 || op == 5 || op == 11) && !fl, WHO ": null table (fl: leak, or decay and eps)");
+  hipStream_t s = (hipStream_t)stream;
+  switch (op) {
+    case 0: {                                            // pad_rows: ptrs src, dst;  dims B, L, C, pf, pb
+      SG_DIM("B", d[0], 1); SG_DIM("L", d[1], 1); SG_DIM("C", d[2], 1); SG_DIM("pf", d[3], 0); SG_DIM("pb", d[4], 0); SG_MUL4("C", d[2]);
+      OP_REFUSE(d[0] * (d[1] + d[3] + d[4]) * d[2] > ((int64_t)1 << 30), WHO ": B x (pf + L + pb) x C above the entry's 2^30");
+      SG_PTR("src", ptrs[0], 16); SG_PTR("dst", ptrs[1], 16);
+      launch_pad_rows(FP(0), FP(1), (int)d[0], (int)d[1], (int)d[2], (int)d[3], (int)d[4], s);
+      break;
+    }
+    case 1: case 2: {                                    // prep_tconv (one job) / prep_tconv_many: ptrs (W, dst) per job;  dims n, then ldw, nb, na, e, ne, ldd per job
+      SG_DIM("n", d[0], 1);
+      OP_REFUSE(d[0] > 132 || (op == 1 && d[0] != 1), WHO ": n = %lld jobs outside 1 .. 132 (launch_prep_tconv: 1)", (long long)d[0]);
+      const int n = (int)d[0];
+      for (int j = 0; j < n; ++j) {
+        const int64_t* q = d + 1 + 6 * j;
+        SG_PTR("W", ptrs[2 * j], 4); SG_PTR("dst", ptrs[2 * j + 1], 4);
+        SG_DIM("nb", q[1], 1); SG_DIM("na", q[2], 1); SG_DIM("ne", q[4], 1); SG_LD("ldw", q[0], q[2]); SG_LD("ldd", q[5], q[1]);
+        OP_REFUSE(q[3] < 0 || q[3] > 1, WHO ": e = %lld of job %d outside 0 .. 1", (long long)q[3], j);
+        OP_REFUSE(q[4] * q[1] * q[2] > (1 << 28), WHO ": ne x nb x na of job %d above the entry's 2^28", j);
+      }
+      if (op == 1) launch_prep_tconv(FP(0), (int)d[1], (int)d[2], (int)d[3], (int)d[4], (int)d[5], FP(1), (int)d[6], s);
+      else {
+        PrepTconvBatch pb(s);
+        for (int j = 0; j < n; ++j) { const int64_t* q = d + 1 + 6 * j; pb.add(FP(2 * j), (int)q[0], (int)q[1], (int)q[2], (int)q[3], (int)q[4], FP(2 * j + 1), (int)q[5]); }
+        pb.flush();
+      }
+      break;
+    }
+    case 3: {                                            // interleave: ptrs T0, T1, bias (may be NULL), T;  dims Q0, Q1, i00, i01, pl, B, Lt, C
+      SG_DIM("Q0", d[0], 1); SG_DIM("Q1", d[1], 1); SG_DIM("pl", d[4], 0); SG_DIM("B", d[5], 1); SG_DIM("Lt", d[6], 1); SG_DIM("C", d[7], 1); SG_MUL4("C", d[7]);
+      for (int e = 0; e < 2; ++e) {
+        const int64_t i0 = (((e - d[4]) % 2) + 2) % 2, cnt = d[6] > i0 ? (d[6] - i0 + 1) / 2 : 0;
+        OP_REFUSE(d[2 + e] != i0, WHO ": i0%d = %lld is not the first position of parity class %d under pl = %lld", e, (long long)d[2 + e], e, (long long)d[4]);
+        OP_REFUSE(d[e] < cnt, WHO ": Q%d = %lld below the %lld positions of its class", e, (long long)d[e], (long long)cnt);
+      }
+      OP_REFUSE(d[5] * d[6] * d[7] > ((int64_t)1 << 30), WHO ": B x Lt x C above the entry's 2^30");
+      SG_PTR("T0", ptrs[0], 16); SG_PTR("T1", ptrs[1], 16); SG_OPT("bias", ptrs[2], 16); SG_PTR("T", ptrs[3], 16);
+      launch_interleave(FP(0), FP(1), (int)d[0], (int)d[1], (int)d[2], (int)d[3], (int)d[4], FP(2), FP(3), (int)d[5], (int)d[6], (int)d[7], s);
+      break;
+    }
+    case 4: {                                            // act_fwd: ptrs z, alpha (NULL: leaky), out;  dims C, ldo, coff, rows;  fl leak
+      SG_DIM("C", d[0], 1); SG_DIM("coff", d[2], 0); SG_DIM("rows", d[3], 1); SG_LD("ldo", d[1], d[2] + d[0]);
+      OP_REFUSE(d[3] * d[1] > ((int64_t)1 << 30), WHO ": rows x ldo above the entry's 2^30");
+      SG_PTR("z", ptrs[0], 4); SG_OPT("alpha", ptrs[1], 4); SG_PTR("out", ptrs[2], 4);
+      launch_act_fwd(FP(0), (int)d[0], FP(1), fl[0], FP(2), (int)d[1], (int)d[2], (size_t)d[3], s);
+      break;
+    }
+    case 5: {                                            // act_bwd: ptrs dy, z, alpha, extra (may be NULL), dz;  dims ldy, coff, C, rows;  fl leak
+      SG_DIM("C", d[2], 1); SG_DIM("coff", d[1], 0); SG_DIM("rows", d[3], 1); SG_LD("ldy", d[0], d[1] + d[2]);
+      OP_REFUSE(d[3] * d[0] > ((int64_t)1 << 30), WHO ": rows x ldy above the entry's 2^30");
+      SG_PTR("dy", ptrs[0], 4); SG_PTR("z", ptrs[1], 4); SG_OPT("alpha", ptrs[2], 4); SG_OPT("extra", ptrs[3], 4); SG_PTR("dz", ptrs[4], 4);
+      launch_act_bwd(FP(0), (int)d[0], (int)d[1], FP(1), (int)d[2], FP(2), fl[0], FP(3), FP(4), (size_t)d[3], s);
+      break;
+    }
+    case 6: {                                            // copy_cols: ptrs src, dst;  dims lds, soff, ldd, doff, C, rows, accumulate
+      SG_DIM("C", d[4], 1); SG_DIM("rows", d[5], 1); SG_DIM("soff", d[1], 0); SG_DIM("doff", d[3], 0); SG_FLAG("accumulate", d[6]);
+      SG_LD("lds", d[0], d[1] + d[4]); SG_LD("ldd", d[2], d[3] + d[4]);
+      OP_REFUSE(d[5] * std::max(d[0], d[2]) > ((int64_t)1 << 30), WHO ": rows x ld above the entry's 2^30");
+      SG_PTR("src", ptrs[0], 4); SG_PTR("dst", ptrs[1], 4);
+      launch_copy_cols(FP(0), (int)d[0], (int)d[1], FP(1), (int)d[2], (int)d[3], (int)d[4], (size_t)d[5], d[6] != 0, s);
+      break;
+    }
+    case 7: {                                            // build_joint1: ptrs x, tail, noise (may be NULL), joint;  dims Lx, U, B
+      SG_DIM("Lx", d[0], 1); SG_DIM("U", d[1], 1); SG_DIM("B", d[2], 1);
+      OP_REFUSE(d[2] * (d[0] + d[1]) > ((int64_t)1 << 30), WHO ": B x (Lx + U) above the entry's 2^30");
+      SG_PTR("x", ptrs[0], 4); SG_PTR("tail", ptrs[1], 4); SG_OPT("noise", ptrs[2], 4); SG_PTR("joint", ptrs[3], 4);
+      launch_build_joint1(FP(0), (int)d[0], FP(1), (int)d[1], FP(2), FP(3), (int)d[2], s);
+      break;
+    }
+    case 8: {                                            // sum_all: ptrs src, out, scratch (256 floats);  dims rows, cols, ld
+      SG_DIM("rows", d[0], 1); SG_DIM("cols", d[1], 1); SG_LD("ld", d[2], d[1]);
+      OP_REFUSE(d[0] * d[2] > ((int64_t)1 << 30), WHO ": rows x ld above the entry's 2^30");
+      SG_PTR("src", ptrs[0], 4); SG_PTR("out", ptrs[1], 4); SG_PTR("scratch", ptrs[2], 4);
+      launch_sum_all(FP(0), (int)d[0], (int)d[1], (int)d[2], FP(1), FP(2), s);
+      break;
+    }
+    case 9: {                                            // segan_lsgan: ptrs logits, dlogits (may be NULL), loss3;  dims B, mode, fake_pass, P
+      SG_DIM("B", d[0], 1); SG_DIM("P", d[3], 1);
+      OP_REFUSE(d[1] < 0 || d[1] > 1, WHO ": mode = %lld outside 0 (D-run) .. 1 (G-run)", (long long)d[1]);
+      OP_REFUSE(d[2] < 0 || d[2] >= d[3], WHO ": fake_pass = %lld outside [0, P = %lld)", (long long)d[2], (long long)d[3]);
+      OP_REFUSE(d[0] * d[3] > (1 << 24), WHO ": P x B above the entry's 2^24");
+      SG_PTR("logits", ptrs[0], 4); SG_OPT("dlogits", ptrs[1], 4); SG_PTR("loss3", ptrs[2], 4);
+      launch_segan_lsgan(FP(0), (int)d[0], (int)d[1], (int)d[2], (int)d[3], FP(1), FP(2), s);
+      break;
+    }
+    case 10: {                                           // segan_l1: ptrs G, labels, lambda, dG (may be NULL), loss3;  dims n, accumulate
+      SG_DIM("n", d[0], 1); SG_FLAG("accumulate", d[1]);
+      SG_PTR("G", ptrs[0], 4); SG_PTR("labels", ptrs[1], 4); SG_PTR("lambda", ptrs[2], 4); SG_OPT("dG", ptrs[3], 4); SG_PTR("loss3", ptrs[4], 4);
+      launch_segan_l1(FP(0), FP(1), (int)d[0], FP(2), FP(3), d[1] != 0, FP(4), s);
+      break;
+    }
+    default: {                                           // rmsprop: ptrs w, g, ms, lr;  dims n;  fl decay, eps
+      SG_DIM("n", d[0], 1);
+      SG_PTR("w", ptrs[0], 4); SG_PTR("g", ptrs[1], 4); SG_PTR("ms", ptrs[2], 4); SG_PTR("lr", ptrs[3], 4);
+      launch_rmsprop(FP(0), FP(1), FP(2), FP(3), fl[0], fl[1], (size_t)d[0], s);
+      break;
+    }
+  }
+  SG_LAUNCHED();
+}
+#undef WHO
+
+#define WHO "op_segan_dhead"
+int rsrgan_op_segan_dhead(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream) {
+  (void)fl;
+  SG_TABLES(0);
+  OP_REFUSE(op < 0 || op > 1, WHO ": op = %d outside 0 (dhead_fwd), 1 (dhead_bwd)", op);
+  const int64_t* d = dims;                               // dims R, Ld, C, k, ldfc
+  SG_DIM("R", d[0], 1); SG_DIM("Ld", d[1], 1); SG_DIM("C", d[2], 1); SG_DIM("k", d[3], 1); SG_DIM("ldfc", d[4], 1);
+  OP_REFUSE(d[0] * d[1] * d[2] > ((int64_t)1 << 28) || d[3] * d[2] > (1 << 24), WHO ": R x Ld x C above the entry's 2^28");
+  if (op == 0) {                                         // ptrs h, W, wfc, bfc, conv_out, logits
+    const char* names[6] = {"h", "W", "wfc", "bfc", "conv_out", "logits"};
+    for (int i = 0; i < 6; ++i) SG_PTR(names[i], ptrs[i], 4);
+    launch_dhead_fwd(FP(0), (int)d[0], (int)d[1], (int)d[2], (int)d[3], FP(1), FP(2), (int)d[4], FP(3), FP(4), FP(5), (hipStream_t)stream);
+  } else {                                               // ptrs dlogit, h, conv_out, W, wfc, dW, dwfc, dbfc (all three or none), dh
+    const char* names[9] = {"dlogit", "h", "conv_out", "W", "wfc", "dW", "dwfc", "dbfc", "dh"};
+    for (int i = 0; i < 9; ++i) { if (i >= 5 && i <= 7) SG_OPT(names[i], ptrs[i], 4); else SG_PTR(names[i], ptrs[i], 4); }
+    OP_REFUSE((!ptrs[5]) != (!ptrs[6]) || (!ptrs[5]) != (!ptrs[7]), WHO ": dW, dwfc and dbfc must all be given or all be null");
+    launch_dhead_bwd(FP(0), (int)d[0], (int)d[1], (int)d[2], (int)d[3], FP(1), FP(2), FP(3), FP(4), (int)d[4], FP(5), FP(6), FP(7), FP(8), (hipStream_t)stream);
+  }
+  SG_LAUNCHED();
+}
+#undef WHO
 
 }  // extern "C"

@@ -42,24 +42,6 @@ static std::vector<int> lengths(int L, int n) {
   for (int i = 0; i < n; ++i) v.push_back((v.back() + 1) / 2);
   return v;
 }
-struct TGeom { int pl, ne[2], i0[2], q0[2], Q[2], pf, pb; };
-static TGeom tgeom(int Ls, int Lt, int k) {
-  TGeom g{};
-  g.pl = same_pad(Lt, k).pl;
-  g.pf = 0; g.pb = 0;
-  for (int e = 0; e < 2; ++e) {
-    g.ne[e] = (k - e + 1) / 2;
-    g.i0[e] = (((e - g.pl) % 2) + 2) % 2;
-    g.q0[e] = (g.i0[e] + g.pl - e) / 2;
-    g.Q[e] = Lt > g.i0[e] ? (Lt - g.i0[e] + 1) / 2 : 0;
-    if (g.Q[e] > 0 && g.ne[e] > 0) {
-      g.pf = std::max(g.pf, g.ne[e] - 1 - g.q0[e]);
-      g.pb = std::max(g.pb, g.q0[e] + g.Q[e] - 1 - (Ls - 1));
-    }
-  }
-  return g;
-}
-
 int SeganModel::init(const rsrgan_segan_cfg& c, uint64_t seed) {
   cfg = c;
   B = c.batch_size; Lx = c.input_len; U = c.output_dim; n = c.n_layers; Lj = Lx + U;
@@ -68,8 +50,23 @@ int SeganModel::init(const rsrgan_segan_cfg& c, uint64_t seed) {
     if (c.g_depths[i] <= 0 || c.d_depths[i] <= 0 || (c.g_depths[i] & 15) || (c.d_depths[i] & 15)) {
       set_error("conv depths must be positive multiples of 16"); return RSRGAN_ERR_INVALID;
     }
+  for (int i = 0; i < n; ++i)
+    if (c.d_depths[i] > SEGAN_SUMS_COLS) {                 // (the generator's column sums go straight into its gradient buffer)
+      set_error("d_depths above %d (the column-sum buffer of the VBN statistics)", SEGAN_SUMS_COLS); return RSRGAN_ERR_INVALID;
+    }
+  // the direct weight-gradient kernel of the single-channel ends: the last deconv (2 * g_depths[0] channels) and the first D block
+  if (!conv1_wgrad_shape_ok(c.g_kwidth, 2 * c.g_depths[0]) || !conv1_wgrad_shape_ok(c.d_kwidth, c.d_depths[0])) {
+    set_error("g_kwidth * 2 * g_depths[0] = %d or d_kwidth * d_depths[0] = %d above the 1024 filter elements of the single-channel weight gradient",
+              c.g_kwidth * 2 * c.g_depths[0], c.d_kwidth * c.d_depths[0]);
+    return RSRGAN_ERR_INVALID;
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device"); return RSRGAN_ERR_NO_DEVICE; }
+  if (!conv1_wgrad_supported(c.g_kwidth, 2 * c.g_depths[0]) || !conv1_wgrad_supported(c.d_kwidth, c.d_depths[0])) {
+    set_error("the single-channel weight gradient needs %zu bytes of LDS (the device has %zu)",
+              std::max(conv1_wgrad_lds_bytes(c.g_kwidth, 2 * c.g_depths[0]), conv1_wgrad_lds_bytes(c.d_kwidth, c.d_depths[0])), device_lds_limit());
+    return RSRGAN_ERR_INVALID;
+  }
   const std::vector<int> Le = lengths(Lx, n), Dl = lengths(Lj, n);
   Ld = Dl[n];
   const int gk = c.g_kwidth, dk = c.d_kwidth;
@@ -159,21 +156,20 @@ int SeganModel::init(const rsrgan_segan_cfg& c, uint64_t seed) {
   logits = alloc<float>(3 * B + 4); dlogits = alloc<float>(3 * B + 4); djoint = alloc<float>((size_t)B * Lj);
   // ---- scratch: padded copies (window views), parity outputs, gradient ping-pong
   size_t pmax = 0, tmax = 0;
-  auto use_conv = [&](int Bn, int L, int C, int k) { const SameGeom g = same_pad(L, k); pmax = std::max(pmax, (size_t)Bn * (g.pl + L + g.pr) * C); };
+  auto use_conv = [&](int Bn, int L, int C, int k) { pmax = std::max(pmax, conv2_pad_floats(Bn, L, C, k)); };
   auto use_tconv = [&](int Bn, int Ls, int Cs, int Lt, int Ct, int k) {
-    const TGeom g = tgeom(Ls, Lt, k);
-    pmax = std::max(pmax, (size_t)Bn * (g.pf + Ls + g.pb) * Cs);
-    tmax = std::max(tmax, (size_t)Bn * std::max(g.Q[0], g.Q[1]) * Ct);
+    pmax = std::max(pmax, tconv2_pad_floats(Bn, Ls, Cs, Lt, k));
+    tmax = std::max(tmax, tconv2_t_floats(Bn, Ls, Lt, Ct, k));
   };
   for (int i = 1; i < n; ++i) {
     use_conv(B, enc[i].Lin, enc[i].Cin, gk); use_tconv(B, enc[i].Lout, enc[i].Cout, enc[i].Lin, enc[i].Cin, gk);
     use_conv(3 * B, blk[i].Lin, blk[i].Cin, dk); use_tconv(3 * B, blk[i].Lout, blk[i].Cout, blk[i].Lin, blk[i].Cin, dk);
   }
   for (int j = 0; j < n - 1; ++j) { use_tconv(B, dec[j].Lin, dec[j].Cin, dec[j].Lout, dec[j].Cout, gk); use_conv(B, dec[j].Lout, dec[j].Cout, gk); }
-  pad_floats = pmax + 64; t_floats = tmax + 64; g_floats = gmax + 64;
+  pad_floats = pmax + SEGAN_SCRATCH_SLACK; t_floats = tmax + SEGAN_SCRATCH_SLACK; g_floats = gmax + 64;
   pad = alloc<float>(pad_floats); t0 = alloc<float>(t_floats); t1 = alloc<float>(t_floats);
   gA = alloc<float>(g_floats); gB = alloc<float>(g_floats); gC = alloc<float>(g_floats);
-  sums = alloc<float>(3 * 2 * 2048);
+  sums = alloc<float>(3 * 2 * SEGAN_SUMS_COLS);
   red_floats = (size_t)4 << 20; red = alloc<float>(red_floats);
   gemm_ws_floats = (size_t)16 << 20; gemm_ws = alloc<float>(gemm_ws_floats);
   dyn = alloc<float>(8); losses = alloc<float>(8);
@@ -188,11 +184,8 @@ int SeganModel::init(const rsrgan_segan_cfg& c, uint64_t seed) {
 }
 
 void SeganModel::refresh_weights(int net, hipStream_t s) {
-  PrepTconvList pl{};
-  auto add = [&](const float* W, int ldw, int nb, int na, int e, int ne, float* dst, int ldd) {
-    if (pl.n == 44) { launch_prep_tconv_many(pl, s); pl.n = 0; }
-    pl.j[pl.n++] = PrepTconvJob{W, dst, ldw, nb, na, e, ne, ldd};
-  };
+  PrepTconvBatch pb(s);
+  auto add = [&](const float* W, int ldw, int nb, int na, int e, int ne, float* dst, int ldd) { pb.add(W, ldw, nb, na, e, ne, dst, ldd); };
   auto prep_down = [&](const ParamSet& ps, SgLayer& L) {   // data gradient of a downconv: Wt[(rr, co)][ci] = W[dk][ci][co]
     for (int e = 0; e < 2; ++e) add(ps.W(L.tW), ps.t[L.tW].ld, L.Cin, L.Cout, e, L.ne[e], L.Wt[e], pad4(L.Cin));
   };
@@ -203,7 +196,7 @@ void SeganModel::refresh_weights(int net, hipStream_t s) {
   } else {
     for (int i = 1; i < n; ++i) prep_down(D, blk[i]);
   }
-  launch_prep_tconv_many(pl, s);
+  pb.flush();
 }
 
 // ---- primitives

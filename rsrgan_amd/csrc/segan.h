@@ -19,17 +19,36 @@ void launch_conv1_wgrad(const float* x, int ldx, int B, int L, int k, const floa
                         hipStream_t s);
 void launch_tconv1(const float* S, int lds, int B, int Ls, int C, int Lt, int k, const float* W, int ldw, const float* bias, float* t, int ldt,
                    hipStream_t s);
+bool conv1_wgrad_shape_ok(int k, int C);                 // k * C <= 1024 and C % 4 == 0: no device needed
+size_t conv1_wgrad_lds_bytes(int k, int C);
+size_t device_lds_limit();
+bool conv1_wgrad_supported(int k, int C);                // ... and the dynamic LDS within the device's limit (queried once)
 void launch_sum_all(const float* src, int rows, int cols, int ld, float* out, float* scratch, hipStream_t s);
 void launch_prep_tconv(const float* W, int ldw, int nb, int na, int e, int ne, float* dst, int ldd, hipStream_t s);
 struct PrepTconvJob { const float* W; float* dst; int ldw, nb, na, e, ne, ldd; };
 struct PrepTconvList { int n; int first[44]; PrepTconvJob j[44]; };      // <= 2 operands x 22 layers per launch (kernel argument: < 4 KB)
 void launch_prep_tconv_many(PrepTconvList& pl, hipStream_t s);
+struct PrepTconvBatch {                                  // any number of jobs, 44 to a launch (SeganModel::refresh_weights)
+  PrepTconvList pl{};
+  hipStream_t s = nullptr;
+  explicit PrepTconvBatch(hipStream_t s_) : s(s_) {}
+  void add(const float* W, int ldw, int nb, int na, int e, int ne, float* dst, int ldd) {
+    if (pl.n == 44) { launch_prep_tconv_many(pl, s); pl.n = 0; }
+    pl.j[pl.n++] = PrepTconvJob{W, dst, ldw, nb, na, e, ne, ldd};
+  }
+  void flush() { launch_prep_tconv_many(pl, s); pl.n = 0; }
+};
 void launch_interleave(const float* T0, const float* T1, int Q0, int Q1, int i00, int i01, int pl, const float* bias, float* T, int B, int Lt, int C,
                        hipStream_t s);
 void launch_act_fwd(const float* z, int C, const float* alpha, float leak, float* out, int ldo, int coff, size_t rows, hipStream_t s);
 void launch_copy_cols(const float* src, int lds, int soff, float* dst, int ldd, int doff, int C, size_t rows, bool accumulate, hipStream_t s);
 void launch_act_bwd(const float* dy, int ldy, int coff, const float* z, int C, const float* alpha, float leak, const float* extra, float* dz, size_t rows,
                     hipStream_t s);
+// what launch_colred launched last on this host thread: 16-byte form or scalar, mode, rows per chunk, chunks per pass, grid of the partial kernel
+struct ColredPlanRecord { int vec, mode, chunk, chunks_per, grid; };
+extern thread_local ColredPlanRecord g_colred_last_plan;
+inline size_t colred_min_scratch(int C, int P) { return (size_t)P * 2 * C; }      // one chunk per pass
+constexpr int SEGAN_SUMS_COLS = 2048;                    // SeganModel::sums: [3 passes][2][SEGAN_SUMS_COLS]
 void launch_colred(int mode, const float* a, int lda, int coff, const float* b, int ldb, int C, size_t rows_per, int P, const float* coef, int ldcoef,
                    float leak, float* out, int ldo, bool accumulate, float* scratch, size_t scratch_floats, hipStream_t s);
 void launch_vbn_coef(const float* sums, int lds, int P, int C, size_t rows_per, int B, float eps, const float* gamma, const float* beta,
@@ -55,6 +74,31 @@ inline SameGeom same_pad(int L, int k, int stride = 2) {
   g.pl = total / 2; g.pr = total - g.pl;
   return g;
 }
+
+// The parity classes of a transposed stride-2 convolution Ls -> Lt (segan.cpp:tconv2): taps per class, first output position, first
+// source row, outputs per class, zero rows in front of / behind the source
+struct TGeom { int pl, ne[2], i0[2], q0[2], Q[2], pf, pb; };
+inline TGeom tgeom(int Ls, int Lt, int k) {
+  TGeom g{};
+  g.pl = same_pad(Lt, k).pl;
+  g.pf = 0; g.pb = 0;
+  for (int e = 0; e < 2; ++e) {
+    g.ne[e] = (k - e + 1) / 2;
+    g.i0[e] = (((e - g.pl) % 2) + 2) % 2;
+    g.q0[e] = (g.i0[e] + g.pl - e) / 2;
+    g.Q[e] = Lt > g.i0[e] ? (Lt - g.i0[e] + 1) / 2 : 0;
+    if (g.Q[e] > 0 && g.ne[e] > 0) {
+      g.pf = std::max(g.pf, g.ne[e] - 1 - g.q0[e]);
+      g.pb = std::max(g.pb, g.q0[e] + g.Q[e] - 1 - (Ls - 1));
+    }
+  }
+  return g;
+}
+// scratch of one layer (SeganModel::init takes the maximum over its layers and adds SEGAN_SCRATCH_SLACK)
+constexpr size_t SEGAN_SCRATCH_SLACK = 64;
+inline size_t conv2_pad_floats(int Bn, int L, int C, int k) { const SameGeom g = same_pad(L, k); return (size_t)Bn * (g.pl + L + g.pr) * C; }
+inline size_t tconv2_pad_floats(int Bn, int Ls, int Cs, int Lt, int k) { const TGeom g = tgeom(Ls, Lt, k); return (size_t)Bn * (g.pf + Ls + g.pb) * Cs; }
+inline size_t tconv2_t_floats(int Bn, int Ls, int Lt, int Ct, int k) { const TGeom g = tgeom(Ls, Lt, k); return (size_t)Bn * std::max(g.Q[0], g.Q[1]) * Ct; }
 
 // A stride-2 conv layer of either net: filter [k, 1, Cin, Cout] as the GEMM operand [k*Cin][ld(Cout)] (downconv), or a decoder deconv with
 // the filter [k, 1, Cout, Cin] = [k*Cout][ld(Cin)].  Lin/Lout are the lengths on the wide / narrow side.

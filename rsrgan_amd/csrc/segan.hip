@@ -111,14 +111,31 @@ __global__ __launch_bounds__(256) void k_sum_parts(const float* __restrict__ par
   for (int p = 0; p < nparts; ++p) acc += part[(size_t)p * n + e];
   out[(size_t)(e / C) * ldo + (e % C)] = acc;
 }
+// What k_conv1_wgrad_part can run: four filter elements per thread (k * C <= 1024), float4 staging of the gradient rows (C % 4) and its
+// dynamic LDS (69.7 KB at the reference's C = 32) within the device's limit.  The shape half needs no device; SeganModel::init and
+// the test entry ask before the first launch, so the abort below is never reached from either.
+bool conv1_wgrad_shape_ok(int k, int C) { return k >= 1 && C >= 4 && C % 4 == 0 && (long long)k * C <= 1024; }
+size_t conv1_wgrad_lds_bytes(int k, int C) { return ((size_t)C1_SUB * C + 2 * C1_SUB + k) * sizeof(float); }
+size_t device_lds_limit() {                                // queried once (the current device; every card of a node is the same part)
+  static const size_t lim = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0) v = 64 << 10;
+    return (size_t)v;
+  }();
+  return lim;
+}
+bool conv1_wgrad_supported(int k, int C) { return conv1_wgrad_shape_ok(k, C) && conv1_wgrad_lds_bytes(k, C) <= device_lds_limit(); }
 void launch_conv1_wgrad(const float* x, int ldx, int B, int L, int k, const float* dz, int ldz, int C, float* dW, int ldw, float* scratch, size_t scratch_floats,
                         hipStream_t s) {
   const int Lo = (L + 1) / 2, total = std::max((Lo - 1) * 2 + k - L, 0), pl = total / 2;
-  if (k * C > 1024 || C % 4 || ldz % 4) { fprintf(stderr, "rsrgan: conv1 weight gradient needs k * C <= 1024 and C, ldz multiples of 4\n"); abort(); }
+  if (!conv1_wgrad_supported(k, C) || ldz % 4 || (size_t)B * k * C > scratch_floats) {
+    fprintf(stderr, "rsrgan: conv1 weight gradient needs k * C <= 1024, C and ldz multiples of 4, its LDS within the device's and B * k * C floats of scratch\n");
+    abort();
+  }
   int chunk = 1024;                                        // positions per workgroup: ~B * Lo / 1024 workgroups
   while ((size_t)B * ((Lo + chunk - 1) / chunk) * k * C > scratch_floats) chunk *= 2;
   const int nch = (Lo + chunk - 1) / chunk;
-  const size_t lds = ((size_t)C1_SUB * C + 2 * C1_SUB + k) * sizeof(float);
+  const size_t lds = conv1_wgrad_lds_bytes(k, C);
   hipLaunchKernelGGL(k_conv1_wgrad_part, dim3(nch, B), dim3(256), lds, s, x, ldx, L, Lo, k, pl, dz, ldz, C, chunk, scratch);
   hipLaunchKernelGGL(k_sum_parts, dim3((k * C + 255) / 256), dim3(256), 0, s, scratch, B * nch, k * C, C, dW, ldw);
 }
@@ -424,9 +441,16 @@ __global__ __launch_bounds__(256) void k_colred_final(const float* __restrict__ 
     *op = accumulate ? *op + (float)t : (float)t;
   }
 }
+thread_local ColredPlanRecord g_colred_last_plan = {};  // what this host thread launched last (host-only; rsrgan_op_segan_last_plan)
 void launch_colred(int mode, const float* a, int lda, int coff, const float* b, int ldb, int C, size_t rows_per, int P, const float* coef, int ldcoef,
                    float leak, float* out, int ldo, bool accumulate, float* scratch, size_t scratch_floats, hipStream_t s) {
   const bool two = mode == 1 || mode == 3;
+  // one chunk per pass is the least the partials take: with less scratch the doubling below would never end
+  if (rows_per == 0) return;                               // nothing to sum (no caller gets here)
+  if (colred_min_scratch(C, P) > scratch_floats) {
+    fprintf(stderr, "rsrgan: column reduction of %d passes x %d columns needs %zu floats of scratch (got %zu)\n", P, C, colred_min_scratch(C, P), scratch_floats);
+    abort();
+  }
   // RSRGAN_COLRED_VEC: bit m = the 16-byte form for mode m.  Mode 2 (the VBN statistics) stays on the scalar form by default: the
   // reference's E[h^2] - E[h]^2 (bnorm.py:40-41) is ill-conditioned in fp32 where |mean| >> sigma (the first two blocks on waveform
   // input), and the 16384-sample parity case holds its 2e-3 against the fp64 oracle only with sums that differ from the 16-byte
@@ -441,6 +465,7 @@ void launch_colred(int mode, const float* a, int lda, int coff, const float* b, 
     chunk *= 2;
   const int chunks_per = (int)((rows_per + chunk - 1) / chunk);
   dim3 grid(P * chunks_per), block(256);
+  g_colred_last_plan = ColredPlanRecord{vec ? 1 : 0, mode, chunk, chunks_per, P * chunks_per};
 #define RSR_COLRED(K, M) hipLaunchKernelGGL(K<M>, grid, block, 0, s, a, lda, coff, b, ldb, C, rows_per, chunk, chunks_per, coef, ldcoef, leak, scratch)
   if (vec) {
     if (mode == 0) RSR_COLRED(k_colred_part4, 0);
@@ -535,8 +560,11 @@ __global__ __launch_bounds__(256) void k_vbn_bwd_apply(const float* __restrict__
     const int c = (int)(i - r * C);
     const float* o = coef + (size_t)(r / rows_per) * 8 * ldc + c;
     const float hv = h[i], sc = o[3 * ldc];
-    const float g = dy[i] * (fmaf(hv, sc, o[4 * ldc]) >= 0.f ? 1.f : leak);
-    dh[i] = g * sc + o[5 * ldc] + o[6 * ldc] * hv;
+    const float f = fmaf(hv, sc, o[4 * ldc]) >= 0.f ? 1.f : leak;         // the side of the kink: k_vbn_apply's own rounding
+    // one rounding: g = dy f and k2 h are exact in double.  (In fp32, g, g sc + k1 and the sum were rounded one after another: 2 ulp of
+    // the largest term against the fp64 value, tests/test_gpu_segan_ops.py; the kernel is bandwidth-bound either way)
+    const double g = (double)dy[i] * (double)f;
+    dh[i] = (float)(fma(g, (double)sc, (double)o[5 * ldc]) + (double)o[6 * ldc] * (double)hv);
   }
 }
 void launch_vbn_bwd_apply(const float* h, const float* dy, int C, size_t rows_per, int P, const float* coef, int ldc, float leak, float* dh, hipStream_t s) {
@@ -589,9 +617,10 @@ void launch_dhead_fwd(const float* h, int R, int Ld, int C, int k, const float* 
 // dW[dk][c] = sum_{r,p} dconv[r][p] h[r, p+dk-pl, c] ; dh[r,l,c] = sum_p dconv[r][p] W[l - p + pl][c]
 __global__ __launch_bounds__(256) void k_dhead_bwd_small(const float* __restrict__ dlogit, int R, int Ld, const float* __restrict__ conv_out,
                                                          float* __restrict__ dwfc, int ldfc, float* __restrict__ dbfc) {
-  const int p = threadIdx.x;
-  if (p < Ld) { float a = 0.f; for (int r = 0; r < R; ++r) a += dlogit[r] * conv_out[(size_t)r * Ld + p]; dwfc[(size_t)p * ldfc] = a; }
-  if (p == 255) { float a = 0.f; for (int r = 0; r < R; ++r) a += dlogit[r]; dbfc[0] = a; }
+  for (int p = threadIdx.x; p < Ld; p += 256) {            // (Ld > 256: five layers on 16384-sample chunks)
+    float a = 0.f; for (int r = 0; r < R; ++r) a += dlogit[r] * conv_out[(size_t)r * Ld + p]; dwfc[(size_t)p * ldfc] = a;
+  }
+  if (threadIdx.x == 255) { float a = 0.f; for (int r = 0; r < R; ++r) a += dlogit[r]; dbfc[0] = a; }
 }
 __global__ __launch_bounds__(256) void k_dhead_bwd_w(const float* __restrict__ dlogit, const float* __restrict__ wfc, int ldfc, const float* __restrict__ h,
                                                      int R, int Ld, int C, int k, float* __restrict__ dW) {

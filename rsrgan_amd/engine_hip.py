@@ -587,6 +587,25 @@ class HipEngine:
         d["route"] = BN_ROUTES[d["route"]]
         return d
 
+    def op_segan(self, family, op, ptrs, dims, fl=()):
+        """rsrgan_op_segan_<family>, op by name (_lib.SEGAN_OPS); ptrs: tensors or None, dims: ints, fl: floats (include/rsrgan.h)"""
+        from ._lib import SEGAN_OPS
+        pt = (C.c_void_p * max(len(ptrs), 1))(*[None if t is None else t.data_ptr() for t in ptrs])
+        dm = (C.c_int64 * max(len(dims), 1))(*[int(v) for v in dims])
+        ff = (C.c_float * max(len(fl), 1))(*[float(v) for v in fl])
+        check(getattr(self.lib, "rsrgan_op_segan_" + family)(SEGAN_OPS[family].index(op), pt, dm, ff, self._stream()))
+
+    def op_segan_sizes(self, kind, dims) -> list:
+        out = (C.c_int64 * 12)()
+        check(self.lib.rsrgan_op_segan_sizes(kind, (C.c_int64 * len(dims))(*[int(v) for v in dims]), out))
+        return list(out)
+
+    def op_segan_last_plan(self) -> dict:
+        from ._lib import SEGAN_PLAN_FIELDS
+        out = (C.c_int32 * 8)()
+        check(self.lib.rsrgan_op_segan_last_plan(out))
+        return dict(zip(SEGAN_PLAN_FIELDS, list(out)))
+
     def op_lstm_colsums(self, dz, cprev, ccur, db, dwi, dwf, dwo, rows, H):
         """lists of nb tensors each: dz [rows][4H], cprev / ccur [rows][H], db [>= 4H], dwi / dwf / dwo [>= H]"""
         check(self.lib.rsrgan_op_lstm_colsums(len(dz), self._table(dz), self._table(cprev), self._table(ccur), self._table(db),

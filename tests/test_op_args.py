@@ -1,4 +1,4 @@
-"""The operator test entries (rsrgan_op_gemm2, _gemm_batch, _gemm16_batch, _lstm_colsums, _colsum, _gemm_last_plan, _conv_*, _bn_*) refuse every
+"""The operator test entries (rsrgan_op_gemm2, _gemm_batch, _gemm16_batch, _lstm_colsums, _colsum, _gemm_last_plan, _conv_*, _bn_*, _segan_*) refuse every
 argument error BEFORE their first HIP call, naming it in rsrgan_last_error(): so the refusals run here, without a device.  The
 pointers are made-up addresses: a refused call never reads them."""
 import ctypes as C
@@ -342,3 +342,218 @@ def test_bn_last_plan_null_and_initial_record(lib):
     refused(lib, bn_fwd(lib, rows=0), "positive")
     again = (C.c_int32 * 16)(*([-7] * 16))
     assert lib.rsrgan_op_bn_last_plan(again) == 0 and list(again) == list(out)   # a refused call launches nothing and records nothing
+
+
+# ---- rsrgan_op_segan_*: (family, op) -> (number of pointers, optional pointer slots, a valid dims table, floats)
+SEGAN_VALID = {
+    ("conv2", 0): (5, {2}, [2, 9, 16, 5, 48, 48, None], []),                     # pad_floats filled from rsrgan_op_segan_sizes
+    ("conv2", 1): (4, set(), [2, 9, 16, 5, 48, 48, 48, None], []),
+    ("conv2", 2): (9, {2}, [2, 5, 16, 9, 5, 48, 16, None, None, None, None], []),
+    ("conv1", 0): (4, {2}, [2, 37, 31, 16, 40, 16, 16], []),
+    ("conv1", 1): (4, set(), [2, 37, 31, 16, 40, 16, 16, 2 * 31 * 16], []),
+    ("conv1", 2): (4, {2}, [2, 19, 16, 37, 31, 16, 16, 40], []),
+    ("colred", 3): (5, set(), [16, 0, 16, 16, 100, 2, 16, 16, 0, 64], [0.3]),
+    ("vbn", 0): (5, {3}, [16, 9, 3, 16, 16, 2], [1e-5]),
+    ("vbn", 1): (3, set(), [16, 9, 3, 16], [0.3]),
+    ("vbn", 2): (5, {3, 4}, [16, 9, 3, 16, 16, 2, 1, 0], [0.0]),
+    ("vbn", 3): (4, set(), [16, 9, 3, 16], [0.3]),
+    ("elem", 0): (2, set(), [2, 9, 16, 3, 4], [0.0]),
+    ("elem", 1): (2, set(), [1, 16, 16, 16, 0, 3, 16], [0.0]),
+    ("elem", 2): (4, set(), [2, 16, 16, 16, 0, 3, 16, 16, 16, 16, 1, 2, 16], [0.0]),
+    ("elem", 3): (4, {2}, [5, 4, 0, 1, 2, 2, 9, 16], [0.0]),
+    ("elem", 4): (3, {1}, [16, 40, 8, 9], [0.3]),
+    ("elem", 5): (5, {2, 3}, [40, 8, 16, 9], [0.3]),
+    ("elem", 6): (2, set(), [40, 8, 32, 4, 16, 9, 0], [0.0]),
+    ("elem", 7): (4, {2}, [37, 5, 2], [0.0]),
+    ("elem", 8): (3, set(), [9, 37, 40], [0.0]),
+    ("elem", 9): (3, {1}, [4, 0, 2, 3], [0.0]),
+    ("elem", 10): (5, {3}, [300, 1], [0.0]),
+    ("elem", 11): (4, set(), [300], [0.9, 1e-10]),
+    ("dhead", 0): (6, set(), [3, 9, 16, 5, 1], []),
+    ("dhead", 1): (9, {5, 6, 7}, [3, 9, 16, 5, 1], []),
+}
+
+
+def segan_sizes(lib, kind, dims):
+    out = (C.c_int64 * 12)()
+    rc = lib.rsrgan_op_segan_sizes(kind, (C.c_int64 * len(dims))(*dims), out)
+    return rc, list(out)
+
+
+def segan_call(lib, family, op, null_at=None, misalign_at=None, dims=None, **patch):
+    n, _, valid, fl = SEGAN_VALID[(family, op)]
+    d = list(valid if dims is None else dims)
+    if family == "conv2":                                       # the model's sizes for the valid layer
+        if op == 2:
+            s = segan_sizes(lib, 1, [2, 5, 16, 9, 48, 5])[1]
+            for i, v in zip((7, 8, 9, 10), s[:4]):
+                d[i] = v if d[i] is None else d[i]
+        else:
+            i = 6 if op == 0 else 7
+            d[i] = segan_sizes(lib, 0, [2, 9, 16, 5])[1][0] if d[i] is None else d[i]
+    for i, v in patch.get("set", {}).items():
+        d[i] = v
+    ptrs = [None if i == null_at else P + 4096 * i + (4 if i == misalign_at else 0) for i in range(n)]
+    return getattr(lib, "rsrgan_op_segan_" + family)(op, (C.c_void_p * n)(*ptrs), (C.c_int64 * len(d))(*d), (C.c_float * max(len(fl), 1))(*fl), None)
+
+
+@pytest.mark.parametrize("family,op", sorted(SEGAN_VALID))
+def test_segan_null_pointers_and_tables(lib, family, op):
+    n, optional, valid, fl = SEGAN_VALID[(family, op)]
+    fn = getattr(lib, "rsrgan_op_segan_" + family)
+    refused(lib, fn(op, None, (C.c_int64 * 16)(), (C.c_float * 2)(), None), "op_segan_" + family, "null table")
+    refused(lib, fn(99, (C.c_void_p * 16)(), (C.c_int64 * 16)(), (C.c_float * 2)(), None), "op_segan_" + family, "outside")
+    for i in range(n):
+        if i not in optional:
+            refused(lib, segan_call(lib, family, op, null_at=i), "op_segan_" + family, "null pointer")
+    if optional & {5, 6, 7} and family == "dhead":
+        refused(lib, segan_call(lib, family, op, null_at=6), "all be given or all be null")
+    if family == "vbn" and op == 2:
+        refused(lib, segan_call(lib, family, op, null_at=3), "both be given or both be null")
+
+
+@pytest.mark.parametrize("family,op", sorted(SEGAN_VALID))
+def test_segan_sizes_below_one(lib, family, op):
+    """every slot of every dims table at -1 (sizes, offsets, flags and scratch sizes alike), and a size beyond the entry's limit"""
+    valid = SEGAN_VALID[(family, op)][2]
+    for i in range(len(valid)):
+        refused(lib, segan_call(lib, family, op, set={i: -1}), "op_segan_" + family)
+    refused(lib, segan_call(lib, family, op, set={0: 1 << 40}), "op_segan_" + family)
+
+
+def test_segan_conv2_refusals(lib):
+    refused(lib, segan_call(lib, "conv2", 0, set={2: 18}), "Cin", "multiple of 4")
+    refused(lib, segan_call(lib, "conv2", 0, set={4: 50, 5: 52}), "Cout", "multiple of 4")
+    refused(lib, segan_call(lib, "conv2", 0, set={5: 44}), "leading dimension ldw")
+    refused(lib, segan_call(lib, "conv2", 0, set={5: 50}), "ldw", "multiple of 4")
+    refused(lib, segan_call(lib, "conv2", 0, misalign_at=4), "pad not 16-byte aligned")
+    need = segan_sizes(lib, 0, [2, 9, 16, 5])[1][0]
+    assert need == 2 * (9 + 4) * 16 + 64                        # same_pad(9, 5): out 5, total (5 - 1) * 2 + 5 - 9 = 4
+    refused(lib, segan_call(lib, "conv2", 0, set={6: need - 1}), "pad of", "the model gives")
+    refused(lib, segan_call(lib, "conv2", 1, set={7: need - 1}), "pad of", "the model gives")
+    refused(lib, segan_call(lib, "conv2", 1, set={5: 44}), "leading dimension ldz")
+    s = segan_sizes(lib, 1, [2, 5, 16, 9, 48, 5])[1]
+    # tgeom(5, 9, 5): pl = 2, ne = {3, 2}, i0 = {0, 1}, Q = {5, 4}, q0 = {1, 1}: pf = 1, pb = 1
+    assert s[:11] == [2 * 7 * 16 + 64, 2 * 5 * 48 + 64, 3 * 16 * 48, 2 * 16 * 48, 2, 0, 1, 5, 4, 1, 1], s
+    for i, word in ((7, "pad of"), (8, "t0 / t1 of"), (9, "Wt0 of"), (10, "Wt1 of")):
+        refused(lib, segan_call(lib, "conv2", 2, set={i: s[i - 7] - 1}), word)
+    refused(lib, segan_call(lib, "conv2", 2, set={3: 8, 1: 5}), "not ceil(Lt / 2)")
+    refused(lib, segan_call(lib, "conv2", 2, set={4: 1}), "k = 1")
+    refused(lib, segan_call(lib, "conv2", 2, misalign_at=7), "Wt0 not 16-byte aligned")
+    assert segan_sizes(lib, 1, [2, 1, 16, 1, 48, 5])[1][7:9] == [1, 0]            # Ls = Lt = 1: one empty parity class
+    refused(lib, segan_sizes(lib, 1, [2, 5, 16, 8, 48, 5])[0], "op_segan_sizes", "not ceil(Lt / 2)")
+    refused(lib, segan_sizes(lib, 7, [1])[0], "kind = 7")
+    refused(lib, lib.rsrgan_op_segan_sizes(0, None, None), "null pointer")
+
+
+def test_segan_conv1_refusals(lib):
+    refused(lib, segan_call(lib, "conv1", 0, set={3: 20, 5: 20, 6: 20}), "C = 20", "multiple of 16")
+    refused(lib, segan_call(lib, "conv1", 0, set={4: 36}), "leading dimension ldx")
+    refused(lib, segan_call(lib, "conv1", 0, set={6: 18}), "ldz")
+    refused(lib, segan_call(lib, "conv1", 0, misalign_at=3), "z not 16-byte aligned")
+    # launch_conv1_wgrad would abort() on these: refused, never launched
+    refused(lib, segan_call(lib, "conv1", 1, set={2: 33, 3: 32, 5: 32, 6: 32, 7: 1 << 20}), "k x C = 1056 above 1024")
+    refused(lib, segan_call(lib, "conv1", 1, set={2: 17, 3: 64, 5: 64, 6: 64, 7: 1 << 20}), "k x C = 1088 above 1024")
+    refused(lib, segan_call(lib, "conv1", 1, set={3: 18, 5: 20, 6: 20}), "no multiple of 4")
+    refused(lib, segan_call(lib, "conv1", 1, set={5: 18}), "ldz", "multiple of 4")
+    refused(lib, segan_call(lib, "conv1", 1, set={7: 2 * 31 * 16 - 1}), "scratch of", "B x k x C")
+    refused(lib, segan_call(lib, "conv1", 1, set={0: 70000, 7: 1 << 30}), "65535")
+    assert segan_sizes(lib, 2, [32, 32])[1][:2] == [1, (512 * 32 + 1024 + 32) * 4]
+    assert segan_sizes(lib, 2, [31, 32])[1][1] == 69756                          # the reference's first D block: 69.7 KB
+    assert segan_sizes(lib, 2, [33, 32])[1][0] == 0 and segan_sizes(lib, 2, [21, 48])[1][0] == 1 and segan_sizes(lib, 2, [8, 6])[1][0] == 0
+    refused(lib, segan_call(lib, "conv1", 2, set={2: 18, 5: 20, 6: 20}), "C = 18", "multiple of 4")
+    refused(lib, segan_call(lib, "conv1", 2, set={1: 18}), "not ceil(Lt / 2)")
+    refused(lib, segan_call(lib, "conv1", 2, set={7: 36}), "leading dimension ldt")
+
+
+def test_segan_colred_refusals(lib):
+    before = (C.c_int32 * 8)()
+    assert lib.rsrgan_op_segan_last_plan(before) == 0
+    for mode in (-1, 4):
+        refused(lib, lib.rsrgan_op_segan_colred(mode, (C.c_void_p * 5)(), (C.c_int64 * 10)(), (C.c_float * 1)(), None), "mode = %d" % mode)
+    n, _, valid, fl = SEGAN_VALID[("colred", 3)]
+
+    def colred(mode, null_at=None, **set_):
+        d = list(valid)
+        for i, v in set_.items():
+            d[int(i[1:])] = v
+        ptrs = [None if i == null_at else P + 4096 * i for i in range(5)]
+        return lib.rsrgan_op_segan_colred(mode, (C.c_void_p * 5)(*ptrs), (C.c_int64 * 10)(*d), (C.c_float * 1)(0.3), None)
+    assert segan_sizes(lib, 3, [16, 2])[1][0] == 64
+    for mode in range(4):
+        refused(lib, colred(mode, d9=63), "scratch of 63 floats below the P x 2 x C = 64")     # one float short: refused, the doubling never starts
+        refused(lib, colred(mode, d0=12), "leading dimension lda")
+        refused(lib, colred(mode, d1=4), "leading dimension lda")                # coff + C beyond the row
+        refused(lib, colred(mode, d7=12), "leading dimension ldo")
+        refused(lib, colred(mode, null_at=0), "null pointer (a)")
+    for mode in (1, 3):
+        refused(lib, colred(mode, null_at=1), "null pointer (b)")
+        refused(lib, colred(mode, d2=12), "leading dimension ldb")
+    refused(lib, colred(3, null_at=2), "null pointer (coef)")
+    refused(lib, colred(3, d6=12), "leading dimension ldcoef")
+    refused(lib, colred(0, d5=65), "P above 64")
+    refused(lib, lib.rsrgan_op_segan_last_plan(None), "op_segan_last_plan", "null pointer")
+    out = (C.c_int32 * 8)()
+    assert lib.rsrgan_op_segan_last_plan(out) == 0 and list(out) == list(before)      # a refused call launches nothing and records nothing
+
+
+def test_segan_elem_vbn_dhead_refusals(lib):
+    refused(lib, segan_call(lib, "elem", 0, set={2: 18}), "C = 18", "multiple of 4")
+    refused(lib, segan_call(lib, "elem", 0, misalign_at=1), "dst not 16-byte aligned")
+    refused(lib, segan_call(lib, "elem", 1, set={0: 2}), "launch_prep_tconv: 1")
+    refused(lib, segan_call(lib, "elem", 2, set={0: 133}), "1 .. 132")
+    refused(lib, segan_call(lib, "elem", 2, set={10: 2}), "e = 2 of job 1")
+    refused(lib, segan_call(lib, "elem", 2, set={12: 12}), "leading dimension ldd")
+    refused(lib, segan_call(lib, "elem", 3, set={2: 1}), "i00 = 1 is not the first position of parity class 0 under pl = 2")
+    refused(lib, segan_call(lib, "elem", 3, set={1: 3}), "Q1 = 3 below the 4 positions")
+    refused(lib, segan_call(lib, "elem", 3, set={7: 18}), "multiple of 4")
+    refused(lib, segan_call(lib, "elem", 4, set={1: 20}), "leading dimension ldo")
+    refused(lib, segan_call(lib, "elem", 5, set={0: 20}), "leading dimension ldy")
+    refused(lib, segan_call(lib, "elem", 6, set={0: 20}), "leading dimension lds")
+    refused(lib, segan_call(lib, "elem", 6, set={2: 16}), "leading dimension ldd")
+    refused(lib, segan_call(lib, "elem", 8, set={2: 36}), "leading dimension ld")
+    refused(lib, segan_call(lib, "elem", 9, set={1: 2}), "mode = 2")
+    refused(lib, segan_call(lib, "elem", 9, set={1: 1, 2: 3}), "fake_pass")
+    refused(lib, segan_call(lib, "elem", 6, set={6: 2}), "accumulate = 2 is neither 0 nor 1")
+    refused(lib, segan_call(lib, "vbn", 0, set={3: 12}), "leading dimension ldc")
+    refused(lib, segan_call(lib, "vbn", 0, set={4: 12}), "leading dimension lds")
+    refused(lib, segan_call(lib, "vbn", 2, set={6: 2}), "first_live = 2")
+    refused(lib, segan_call(lib, "vbn", 1, set={2: 65}), "P above 64")
+    refused(lib, segan_call(lib, "dhead", 1, set={0: 1 << 20, 1: 1 << 10}), "2^28")
+
+
+def test_segan_null_float_table(lib):
+    """fl may be NULL exactly where include/rsrgan.h lists no float: ops that take one refuse NULL; the others get past it to their own checks"""
+    def call(family, op, **kw):
+        n, _, valid, _ = SEGAN_VALID[(family, op)]
+        d = list(valid)
+        for i, v in kw.items():
+            d[int(i[1:])] = v
+        ptrs = [P + 4096 * i for i in range(n)]
+        return getattr(lib, "rsrgan_op_segan_" + family)(op, (C.c_void_p * n)(*ptrs), (C.c_int64 * len(d))(*d), None, None)
+    for family, op in (("vbn", 0), ("vbn", 1), ("vbn", 3), ("elem", 4), ("elem", 5), ("elem", 11), ("colred", 3)):
+        refused(lib, call(family, op), "null table", "fl")
+    refused(lib, call("elem", 0, d2=18), "C = 18")                 # pad_rows, copy_cols, bwd_coef: NULL fl is fine, the next check speaks
+    refused(lib, call("elem", 6, d6=2), "accumulate = 2")
+    refused(lib, call("vbn", 2, d6=2), "first_live = 2")
+
+
+def test_segan_create_refuses_what_would_abort_in_a_step(lib):
+    """configs whose single-channel weight gradient has no kernel (k * C > 1024) or whose depths exceed the column-sum buffer are refused
+    at create time, before the device is asked for"""
+    def create(**kw):
+        cfg = _lib.SeganCfg()
+        assert lib.rsrgan_segan_default_cfg(C.byref(cfg)) == 0
+        cfg.n_layers, cfg.input_len, cfg.batch_size = 2, 64, 2
+        for k, v in kw.items():
+            if k.endswith("depths"):
+                for i, x in enumerate(v):
+                    getattr(cfg, k)[i] = x
+            else:
+                setattr(cfg, k, v)
+        h = C.c_void_p()
+        return lib.rsrgan_segan_create(C.byref(cfg), 1, C.byref(h))
+    refused(lib, create(g_depths=[32, 32], g_kwidth=31), "g_kwidth * 2 * g_depths[0] = 1984", "1024")
+    refused(lib, create(d_depths=[48, 48], d_kwidth=31), "d_kwidth * d_depths[0] = 1488", "1024")
+    refused(lib, create(d_depths=[16, 2064], d_kwidth=5), "d_depths above 2048")
+    assert segan_sizes(lib, 2, [20, 2 * 16])[1][0] == 1 and segan_sizes(lib, 2, [31, 16])[1][0] == 1      # the reference's own shapes pass
