@@ -49,7 +49,8 @@ enum { RSRGAN_G_LSTM = 0, RSRGAN_G_RES_LSTM_L = 1, RSRGAN_G_RES_LSTM_BASE = 2,
        RSRGAN_G_RCED = 4, /* models/rced.py: frame-level 9 x conv2d + FC generator (dnn_trainer.py:98-99), batch_norm=False */
        RSRGAN_G_BNLSTM = 5 /* models/bnlstm.py: input FC + ReLU, BNLSTMCell(g_cells, num_proj=g_proj, peepholes) x g_layers with batch
                               normalisation inside the recurrence, output FC; RSRGAN_FLAG_SUPERVISED only (models/rnn_trainer.py),
-                              batch_size <= 64, no RSRGAN_FLAG_BATCH_NORM, no dropout */,
+                              batch_size <= 64 (training handles; an inference handle pads to the persistent launch's row groups), no
+                              RSRGAN_FLAG_BATCH_NORM, no dropout */,
        RSRGAN_G_RES_LSTM_I = 6 /* models/res_lstm_i.py: res_lstm_l's cells and variable table, but the residual is always the stack's
                                   input: inputs_{l+1} = outputs_l + x, the output FC reads outputs_L + x (never a running sum);
                                   needs g_proj == input_dim; RSRGAN_FLAG_SUPERVISED only (models/rnn_trainer.py:97-108: the
@@ -126,8 +127,14 @@ enum {
                                   launches run without their stash stores (csrc/gpersist.hip LEAN), a batch longer than one launch as
                                   consecutive launches that carry the state.  RSRGAN_NET_G's tensor table is the training handle's (names,
                                   order, offsets), so a checkpoint loads.  For the sequence generators lstm, res_lstm_l, res_lstm_base,
-                                  res_lstm_i (with RSRGAN_FLAG_SUPERVISED, as always) and the unprojected stack; dnn, rced and bnlstm:
-                                  RSRGAN_ERR_INVALID ("not built").  Work: rsrgan_forward_g, rsrgan_forward_g_stream, rsrgan_g_state_*,
+                                  res_lstm_i (with RSRGAN_FLAG_SUPERVISED, as always), the unprojected stack and bnlstm; dnn and rced:
+                                  RSRGAN_ERR_INVALID ("not built").  bnlstm (with RSRGAN_FLAG_SUPERVISED | RSRGAN_FLAG_WAVEFRONT):
+                                  the three batch-norm sites are folded into the kernels, the bias and a per-unit affine pair with the moving
+                                  statistics at create and at every rsrgan_set_params(what = 0); the persistent launch is the only forward
+                                  it has, so create returns RSRGAN_ERR_INVALID without RSRGAN_FLAG_WAVEFRONT ("not built"), for a shape
+                                  without a persistent plan and under RSRGAN_GP_TAGS=0, and after a reported device failure
+                                  (rsrgan_device_status) the forward calls return RSRGAN_ERR_HIP.  batch_size is padded to 1, 2, 4 or 8
+                                  groups of 32 rows (at most 256).  Work: rsrgan_forward_g, rsrgan_forward_g_stream, rsrgan_g_state_*,
                                   rsrgan_set_params / rsrgan_get_params with what = 0 on RSRGAN_NET_G, the tensor-table calls,
                                   rsrgan_device_status, rsrgan_device_bytes, the profile counters, rsrgan_destroy.  Refused before the first
                                   HIP call, rsrgan_last_error() naming the inference-only handle: rsrgan_d_step, rsrgan_g_step,
@@ -183,7 +190,8 @@ int rsrgan_forward_g(rsrgan_handle h, const float* x, const int32_t* lengths, in
  * The handle keeps a CARRIED generator state: per layer l the cell state c_l [batch_size, H] and the projected state m_l
  * [batch_size, P] (P = H without num_proj: the state is h), fp32, zero after rsrgan_create.  Only the five calls below read or
  * write it; rsrgan_forward_g and every training call start from cell.zero_state as before.  Sequence generators only:
- * RSRGAN_ERR_INVALID for the frame-level ones (dnn, rced: no state) and for bnlstm (not built).
+ * RSRGAN_ERR_INVALID for the frame-level ones (dnn, rced: no state) and for a bnlstm training handle (not built; a bnlstm
+ * inference handle, RSRGAN_FLAG_INFER, carries (c, m) per layer like the others: c is the raw cell state, before the cell site's norm).
  *
  * floats of one row's state blob: sum over layers of (H + P); a row is layer 0's c, layer 0's m, layer 1's c, ... unpadded. */
 int rsrgan_g_state_floats(rsrgan_handle h, int32_t* n);
@@ -347,6 +355,12 @@ int rsrgan_op_lstm_colsums(int32_t nb, const float* const* dz, const float* cons
 /* out[c] = sum_r a[r * lda + c] * (b ? b[r * ldb + c] : 1); tall != 0: the tall-and-narrow form (b must be NULL) */
 int rsrgan_op_colsum(const float* a, int32_t lda, const float* b, int32_t ldb, float* out, int32_t rows, int32_t cols, int32_t tall,
                      void* stream);
+/* the decode-time fold of one BNLSTMCell (csrc/bnlstm.hip k_bnl_fold).  Wx = input_kernel, Wh = state_kernel [P][4H];
+ * bn = {scale, offset, moving_mean, moving_var} x {input [4H], state [4H], cell [H]}; bias [4H].  With g = scale / sqrt(moving_var + 1e-3):
+ * KxT [4H][ldI] row col = g_in[col] * Wx[:, col] and KhT [4H][ldP] likewise with g_st (columns [P, ld) zero), bias_f [4H] = bias +
+ * (offset_in - g_in mean_in) + (offset_st - g_st mean_st), ca [H] = g_cell, cb [H] = offset_cell - g_cell mean_cell.  DEVICE pointers. */
+int rsrgan_op_bnl_fold(const float* Wx, const float* Wh, const float* const bn[12], const float* bias, int32_t P, int32_t H, float* KxT,
+                       int32_t ldI, float* KhT, int32_t ldP, float* bias_f, float* ca, float* cb, void* stream);
 
 /* ---- the implicit-GEMM convolution of the R-CED generator (csrc/conv.hip).  Unit parity tests only (tests/test_gpu_conv_ops.py,
  * tests/test_op_args.py); no trainer calls them.  Each goes through the host launch function Model::rced_forward / rced_backward

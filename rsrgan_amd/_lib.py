@@ -26,7 +26,7 @@ SYMBOLS = ["rsrgan_default_cfg", "rsrgan_create", "rsrgan_destroy", "rsrgan_last
            "rsrgan_grad_bucket_count", "rsrgan_grad_bucket_info", "rsrgan_grad_bucket_wait",
            "rsrgan_profile_begin", "rsrgan_profile_read", "rsrgan_profile_read_kind", "rsrgan_profile_launches", "rsrgan_op_launch_floor", "rsrgan_device_status", "rsrgan_device_bytes", "rsrgan_set_dropout",
            "rsrgan_op_gemm", "rsrgan_op_gemm2", "rsrgan_op_gemm_batch", "rsrgan_op_gemm16_batch", "rsrgan_op_gemm_last_plan",
-           "rsrgan_op_lstm_colsums", "rsrgan_op_colsum", "rsrgan_version",
+           "rsrgan_op_lstm_colsums", "rsrgan_op_colsum", "rsrgan_op_bnl_fold", "rsrgan_version",
            "rsrgan_op_conv_fwd", "rsrgan_op_conv_wgrad", "rsrgan_op_conv_ws_floats", "rsrgan_op_conv_supported", "rsrgan_op_conv_last_plan",
            "rsrgan_op_bn_forward", "rsrgan_op_bn_backward", "rsrgan_op_bn_commit", "rsrgan_op_bn_last_plan",
            "rsrgan_op_segan_sizes", "rsrgan_op_segan_conv2", "rsrgan_op_segan_conv1", "rsrgan_op_segan_colred", "rsrgan_op_segan_last_plan",
@@ -116,6 +116,7 @@ def load():
     lib.rsrgan_op_gemm_last_plan.argtypes = [C.POINTER(i32)]
     lib.rsrgan_op_lstm_colsums.argtypes = [i32, pp, pp, pp, pp, pp, pp, pp, i32, i32, vp]
     lib.rsrgan_op_colsum.argtypes = [p, i32, p, i32, p, i32, i32, i32, vp]
+    lib.rsrgan_op_bnl_fold.argtypes = [p, p, pp, p, i32, i32, p, i32, p, i32, p, p, p, vp]
     lib.rsrgan_op_conv_fwd.argtypes = [p, i32, i32, p, i32, i32, p, i32, p, p, i32, i32, i32, i32, i32, i32, vp]
     lib.rsrgan_op_conv_wgrad.argtypes = [p, i32, i32, p, i32, i32, p, i32, p, p, i64, i32, i32, i32, i32, i32, vp]
     lib.rsrgan_op_conv_ws_floats.argtypes = [i32, i32, i32, i32, i32]

@@ -23,7 +23,18 @@ int Model::bnl_check(const rsrgan_cfg& c) const {
     return RSRGAN_ERR_INVALID;
   }
   if (c.flags & RSRGAN_FLAG_BATCH_NORM) { set_error("g_type bnlstm: the input FC's batch_norm (RSRGAN_FLAG_BATCH_NORM) is not built"); return RSRGAN_ERR_INVALID; }
-  if (!bnl_supported(c.batch_size)) {
+  if (c.flags & RSRGAN_FLAG_INFER) {
+    // decode normalises with the moving statistics, so rows do not interact (no 64-row limit: the batch is padded to the
+    // persistent launch's row groups) -- and the persistent launch is the only forward such a handle has
+    if (!(c.flags & RSRGAN_FLAG_WAVEFRONT)) {
+      set_error("g_type bnlstm with RSRGAN_FLAG_INFER needs RSRGAN_FLAG_WAVEFRONT: its forward is the persistent launch, a launch-per-phase forward of the folded cell is not built");
+      return RSRGAN_ERR_INVALID;
+    }
+    if (!switches().gp_tags) {
+      set_error("g_type bnlstm with RSRGAN_FLAG_INFER: RSRGAN_GP_TAGS=0 is set, and the folded cell's persistent forward is built for tagged rings only");
+      return RSRGAN_ERR_INVALID;
+    }
+  } else if (!bnl_supported(c.batch_size)) {
     set_error("g_type bnlstm: batch_size=%d, at most 64 rows per GPU are supported (one workgroup holds a step's batch statistics)", c.batch_size);
     return RSRGAN_ERR_INVALID;
   }
@@ -60,6 +71,32 @@ void Model::bnl_params() {
   }
   g_fc_out_w = G.add("g_model/fully_connected_1/weights", P, Dout, false);
   g_fc_out_b = G.add("g_model/fully_connected_1/biases", 1, Dout, true);
+}
+
+// An inference handle's layers (RSRGAN_FLAG_INFER): one LstmLayer view per BNLSTMCell for the persistent forward -- input and
+// recurrent width P, the cell's own bias / peephole / projection tensors, no stacked kernel (tK = -1: input_kernel and state_kernel stay two
+// tensors; KxT / KhT receive their folded, transposed copies from bnl_refresh_fold)
+int Model::bnl_infer_layers() {
+  for (const BnlCell& C : bnl) {
+    LstmLayer L;
+    L.has_proj = true;
+    L.I = L.P = cfg.g_proj; L.H = cfg.g_cells; L.ldI = L.ldP = pad4(L.P); L.ldH = pad4(L.H);
+    L.tK = -1; L.tb = C.tb; L.twf = C.twf; L.twi = C.twi; L.two = C.two; L.tWp = C.tWp;
+    gl.push_back(L);
+  }
+  return RSRGAN_OK;
+}
+
+void Model::bnl_refresh_fold(hipStream_t s) {
+  for (size_t l = 0; l < bnl.size(); ++l) {
+    const BnlCell& C = bnl[l]; const LstmLayer& L = gl[l];
+    BnlFold f{};
+    f.Wx = G.W(C.tWx); f.Wh = G.W(C.tWh); f.bias = G.W(C.tb);
+    for (int k = 0; k < 4; ++k) { f.bn[k] = G.W(C.tin[k]); f.bn[4 + k] = G.W(C.tst[k]); f.bn[8 + k] = G.W(C.tce[k]); }
+    f.P = L.P; f.H = L.H; f.ldI = L.ldI; f.ldP = L.ldP; f.eps = kBnlEps;
+    f.KxT = L.KxT; f.KhT = L.KhT; f.bias_f = L.bias_f; f.ca = L.ca; f.cb = L.cb;
+    launch_bnl_fold(f, s);
+  }
 }
 
 int Model::bnl_alloc() {

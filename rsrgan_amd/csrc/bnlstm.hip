@@ -333,6 +333,48 @@ __global__ __launch_bounds__(64) void k_bnl_bn_in_bwd(BnlLayer a, float* __restr
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------ decode
+// Outside training every batch-norm site normalises with the moving statistics (BNLSTMCell.py:43-49): constants of the handle, so each
+// site is a per-column affine map and the cell a peephole LSTMP with scaled kernels.  With g = scale / sqrt(moving_var + eps)
+// -- computed as scale * (1.0f / sqrtf(moving_var + eps)), the expression of the step kernels above --:
+//   KxT[col][k] = g_in[col] W_xh[k][col],  KhT[col][k] = g_st[col] W_hh[k][col]        (k-contiguous, rows zero-padded to their ld)
+//   bias_f[col] = (bias + (offset_in - g_in mean_in)) + (offset_st - g_st mean_st)
+//   ca[u] = g_cell[u],  cb[u] = offset_cell - g_cell mean_cell
+// grid (ceil(4H / 32), ceil(max(ldI, ldP) / 32), 2 = input | state), 256 threads: a 32 x 32 tile through LDS, coalesced on both sides;
+// the first tile row of the input half also writes the bias, that of the state half the cell pair.
+__global__ __launch_bounds__(256) void k_bnl_fold(BnlFold a) {
+  __shared__ float tile[32][33];
+  const int H4 = 4 * a.H, P = a.P, st = blockIdx.z;
+  const float* W = st ? a.Wh : a.Wx;
+  float* out = st ? a.KhT : a.KxT;
+  const int ld = st ? a.ldP : a.ldI;
+  const float *sc = a.bn[4 * st], *mv = a.bn[4 * st + 3];
+  const int c0 = blockIdx.x * 32, k0 = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int i = ty; i < 32; i += 8) {
+    const int k = k0 + i, c = c0 + tx;
+    tile[i][tx] = (k < P && c < H4) ? W[(size_t)k * H4 + c] : 0.f;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, k = k0 + tx;
+    if (c < H4 && k < ld) {
+      const float g = sc[c] * (1.0f / sqrtf(mv[c] + a.eps));
+      out[(size_t)c * ld + k] = k < P ? tile[tx][i] * g : 0.f;
+    }
+  }
+  if (blockIdx.y != 0 || ty != 0) return;
+  const int c = c0 + tx;
+  if (st == 0 && c < H4) {
+    const float gi = a.bn[0][c] * (1.0f / sqrtf(a.bn[3][c] + a.eps)), gs = a.bn[4][c] * (1.0f / sqrtf(a.bn[7][c] + a.eps));
+    a.bias_f[c] = (a.bias[c] + fmaf(-gi, a.bn[2][c], a.bn[1][c])) + fmaf(-gs, a.bn[6][c], a.bn[5][c]);
+  }
+  if (st == 1 && c < a.H) {
+    const float gc = a.bn[8][c] * (1.0f / sqrtf(a.bn[11][c] + a.eps));
+    a.ca[c] = gc;
+    a.cb[c] = fmaf(-gc, a.bn[10][c], a.bn[9][c]);
+  }
+}
+
 }  // namespace
 
 bool bnl_supported(int B) { return B >= 1 && B <= BNL_MAXB; }
@@ -354,6 +396,10 @@ void launch_bnl_cell_bwd(const BnlLayer& a, int t, hipStream_t s) {
 }
 void launch_bnl_dm(const BnlLayer& a, int t, hipStream_t s) {
   hipLaunchKernelGGL(k_bnl_dm, dim3((a.P + BNL_PC - 1) / BNL_PC), dim3(1024), 0, s, a, t);
+}
+void launch_bnl_fold(const BnlFold& a, hipStream_t s) {
+  const int ld = a.ldI > a.ldP ? a.ldI : a.ldP;
+  hipLaunchKernelGGL(k_bnl_fold, dim3((4 * a.H + 31) / 32, (ld + 31) / 32, 2), dim3(256), 0, s, a);
 }
 void launch_bnl_bn_in_bwd(const BnlLayer& a, float* dzx, int T, hipStream_t s) {
   hipLaunchKernelGGL(k_bnl_bn_in_bwd, dim3((4 * a.H + 63) / 64, T), dim3(64), 0, s, a, dzx, T);

@@ -241,7 +241,7 @@ int rsrgan_forward_g(rsrgan_handle h, const float* x, const int32_t* lengths, in
 // ---- the stateful generator forward ----
 static int gstate_check(Model& m, const char* what) {
   if (m.g_dnn()) { set_error("%s: frame-level generators (dnn, rced) carry no recurrent state", what); return RSRGAN_ERR_INVALID; }
-  if (m.g_bnl()) { set_error("%s: g_type bnlstm: the stateful forward is not built", what); return RSRGAN_ERR_INVALID; }
+  if (m.g_bnl() && !m.infer()) { set_error("%s: g_type bnlstm: the stateful forward is not built for a training handle (an inference handle, RSRGAN_FLAG_INFER, has it)", what); return RSRGAN_ERR_INVALID; }
   if (!m.g_state) { set_error("%s: this generator has no carried state", what); return RSRGAN_ERR_INVALID; }
   return RSRGAN_OK;
 }
@@ -685,6 +685,22 @@ int rsrgan_op_colsum(const float* a, int32_t lda, const float* b, int32_t ldb, f
   return RSRGAN_OK;
 }
 
+int rsrgan_op_bnl_fold(const float* Wx, const float* Wh, const float* const bn[12], const float* bias, int32_t P, int32_t H, float* KxT,
+                       int32_t ldI, float* KhT, int32_t ldP, float* bias_f, float* ca, float* cb, void* stream) {
+  OP_REFUSE(!Wx || !Wh || !bn || !bias || !KxT || !KhT || !bias_f || !ca || !cb, "op_bnl_fold: null pointer");
+  for (int k = 0; k < 12; ++k) OP_REFUSE(!bn[k], "op_bnl_fold: null pointer in bn[%d]", k);
+  OP_REFUSE(P <= 0 || H <= 0, "op_bnl_fold: P and H must be positive (got %d, %d)", P, H);
+  OP_REFUSE(ldI < P || ldP < P, "op_bnl_fold: leading dimension below P = %d (ldI %d, ldP %d)", P, ldI, ldP);
+  OP_REFUSE((long long)H * 4 * (long long)(ldI > ldP ? ldI : ldP) > (1ll << 28), "op_bnl_fold: 4H x ld exceeds the entry's 2^28 floats");
+  BnlFold f{};
+  f.Wx = Wx; f.Wh = Wh; f.bias = bias;
+  for (int k = 0; k < 12; ++k) f.bn[k] = bn[k];
+  f.P = P; f.H = H; f.ldI = ldI; f.ldP = ldP; f.eps = 1e-3f;          // (BNLSTMCell.py:20 batch_norm(epsilon=1e-3))
+  f.KxT = KxT; f.KhT = KhT; f.bias_f = bias_f; f.ca = ca; f.cb = cb;
+  launch_bnl_fold(f, (hipStream_t)stream);
+  if (hipGetLastError() != hipSuccess) { set_error("op_bnl_fold launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
 
 // ---- the implicit-GEMM convolution (conv.hip) through the launch functions Model::rced_forward / rced_backward call
 // the prepared filter Ft of one call: grow-only and kept for the life of the thread like op_ws() for the process (a test entry has no

@@ -233,12 +233,15 @@ __device__ __forceinline__ bool gp_sweep(const GpBuf& b, const unsigned (&lo)[NL
 }
 
 // LDS of a workgroup (NT = 5: 129 KB)
-template <int NT>
-struct GpLds {
+// (CN, gp_fwd_body: the cell norm's offsets b_c of the slice; an empty base elsewhere, so that sizeof(GpLds<NT>) and every member's offset stay)
+template <int NT, bool CN> struct GpLdsCn {};
+template <int NT> struct GpLdsCn<NT, true> { float cnb[4 * NT]; };
+template <int NT, bool CN = false>
+struct GpLds : GpLdsCn<NT, CN> {
   // (small, hot arrays first: a DS immediate offset reaches 64 KB; see DpTrailLds)
   unsigned cnt_x[GP_NR][4], cnt_p[GP_NR], cnt_h[GP_NR], cnt_m[GP_NR], cnt_g[GP_NR], cnt_s[GP_NR], dead, cnt_j[GP_NR], pad_[11];
   int len[GP_ROWS];                         // the rows' lengths: read per step (a register that holds one for the whole launch was spilled, and a scratch reload sat in the cell phase and in front of the publication)
-  float peep[4 * NT][4];                    // {w_i, w_f, w_o, -} per cell of this slice (one 16-byte read per cell)
+  float peep[4 * NT][4];                    // {w_i, w_f, w_o, - (CN: a_c)} per cell of this slice (one 16-byte read per cell)
   float bias[4 * NT][4];                    // {b_i, b_j, b_f, b_o} per cell: the accumulator registers of a lane
   float gs[2][GP_NR][2][64][4];             // the two reducing G waves' partial sums of this workgroup's half chunk [step parity][tile][wave][half wave = even / odd producers, fragment lane]
   float st[6][GP_ROWS][4 * NT];             // the step's stash: gates i, j, f, o | c | h   (h also feeds the projection)
@@ -262,9 +265,14 @@ struct GpLds {
 // the same arithmetic in the same order, the R waves leave c after the last step in slot 1 of the c stash, the reducers the carried m in
 // slot 1 of mst, and out / res_out are written where the pointer is not null (the top layer: the layers below publish through gran2 alone).
 // Slot 0 is read under CARRY and never written.  A variant of its own, as CARRY is.
-template <int NT, bool RES, bool TAG, bool CARRY = false, bool RESX = false, bool LEAN = false>
-__device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S, const unsigned c1, const unsigned bid) {
+// CN: the decode-time BNLSTMCell (models/BNLSTMCell.py:169-205 with the moving statistics; bnlstm.hip k_bnl_fold): the input and state
+// sites are folded into K_x, K_h and the bias on the host side of the launch, the cell site is one fused multiply-add per cell in front
+// of the output tanh, h = sigmoid(o + w_o c) tanh(a_c c + b_c); the peepholes and the carried state keep the raw c.  a_c rides the free
+// fourth word of S.peep, b_c sits in S.cnb.  A variant of its own (an inference handle's: LEAN and TAG), as CARRY and LEAN are.
+template <int NT, bool RES, bool TAG, bool CARRY = false, bool RESX = false, bool LEAN = false, bool CN = false>
+__device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT, CN>& S, const unsigned c1, const unsigned bid) {
   static_assert(RES || !RESX, "RESX is a form of RES");
+  static_assert(!CN || (LEAN && TAG && !RES), "CN is built for the lean, tagged forward of a plain stack");
   constexpr int NR = GP_NR, NU = NT * NR, CW = 4 * NT;
   GPT_DECL
   const int tid = threadIdx.x, lane = tid & 63, lr = lane & 15, q = lane >> 4;
@@ -312,6 +320,13 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
     const int k = e / CW, cl = e - k * CW, cell = min(cell0 + cl, H - 1);
     if (k < 3) S.peep[cl][k] = (k == 0 ? L.wi : k == 1 ? L.wf : L.wo)[cell];
     else S.bias[cl][k - 3] = L.bias[(k - 3) * H + cell];
+  }
+  if constexpr (CN) {
+    for (int e = tid; e < CW; e += GP_WAVES * 64) {
+      const int cell = min(cell0 + e, H - 1);
+      S.peep[e][3] = L.ca[cell];
+      S.cnb[e] = L.cb[cell];
+    }
   }
   if (CARRY) {
     // the carried state m(-1) = slot 0 of mst, as B fragments: lane (q, lr) of (tile r, k-block jb) = row 16 r + lr, columns 16 jb + 4 q ..
@@ -429,7 +444,9 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
             const float gj = gp_tanh(z[1]);
             const float cn = gf * cpv + gi * gj;
             const float go = gp_sigmoid(z[3] + pw[2] * cn);
-            const float hh = go * gp_tanh(cn);
+            float hh;
+            if constexpr (CN) hh = go * gp_tanh(fmaf(pw[3], cn, S.cnb[4 * w + q + 16 * s]));
+            else hh = go * gp_tanh(cn);
             cprev[r][s] = live ? cn : cpv;
             float* const d = stc + r * 16 * CW + s * 16;
             d[0 * GP_ROWS * CW] = live ? gi : 0.f; d[1 * GP_ROWS * CW] = live ? gj : 0.f;
@@ -728,14 +745,14 @@ __device__ __forceinline__ void gp_fwd_body(const GPersistArgs& a, GpLds<NT>& S,
 }
 
 constexpr unsigned GP_GEN_WRAP = 1u << 21;      // the generator's control block: generation 2^21 - 1 is followed by 1
-template <int NT, bool RES, bool TAG, bool CARRY = false, bool RESX = false, bool LEAN = false>
+template <int NT, bool RES, bool TAG, bool CARRY = false, bool RESX = false, bool LEAN = false, bool CN = false>
 __global__ __launch_bounds__(GP_WAVES * 64, 3) void k_glstm_fwd(const GPersistArgs a) {
-  __shared__ __attribute__((aligned(16))) GpLds<NT> S;
+  __shared__ __attribute__((aligned(16))) GpLds<NT, CN> S;
   gu32* ctl = (gu32*)a.ctl;
   const unsigned gen = __hip_atomic_load(ctl + DP_CTL_GEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (counts launches; nothing depends on it)
   // (TAG) steps written to the hop-1 ring by the launches so far, mod 2 GP_R1: every workgroup reads it here, the last one to finish moves it on
   const unsigned c1 = TAG ? __hip_atomic_load(ctl + GP_CTL_C1 + GP_CIDX(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-  gp_fwd_body<NT, RES, TAG, CARRY, RESX, LEAN>(a, S, c1, blockIdx.x);
+  gp_fwd_body<NT, RES, TAG, CARRY, RESX, LEAN, CN>(a, S, c1, blockIdx.x);
   __syncthreads();                                                 // (every wave leaves the body on every path)
   if (threadIdx.x == 0)
     persist_last_out(ctl, gen, [&] { return gridDim.x; }, [&] { return LEAN && !a.L[a.nl - 1].out ? a.L[a.nl - 1].res_out : a.L[a.nl - 1].out; }, GP_GEN_WRAP, [&] {
@@ -2291,10 +2308,13 @@ static void gp_static(F&& f, bool v, B... more) {
 void launch_glstm_fwd(const GPersistArgs& a, hipStream_t s) {
   gp_arm_gran2(a, s);
   const dim3 g(gp_grid(a)), b(GP_WAVES * 64);
-  // (a.res == 2, res_lstm_i: out_l + x at every layer, gp_fwd_body RESX; a.carry: the stateful forward; a.lean: an inference handle's)
-  gp_static([&](auto res, auto tag, auto carry, auto resx, auto lean) {
-    if constexpr (res.value || !resx.value) hipLaunchKernelGGL((k_glstm_fwd<5, res.value, tag.value, carry.value, resx.value, lean.value>), g, b, 0, s, a);
-  }, a.res != 0, a.tags != 0, a.carry != 0, a.res == 2, a.lean != 0);
+  // (a.res == 2, res_lstm_i: out_l + x at every layer, gp_fwd_body RESX; a.carry: the stateful forward; a.lean: an inference handle's;
+  // a.cnorm: a bnlstm inference handle's -- the callers pair it with lean and tags and no residual sums, the only forms instantiated)
+  gp_static([&](auto res, auto tag, auto carry, auto resx, auto lean, auto cn) {
+    if constexpr (cn.value) {
+      if constexpr (!res.value && tag.value && lean.value) hipLaunchKernelGGL((k_glstm_fwd<5, false, true, carry.value, false, true, true>), g, b, 0, s, a);
+    } else if constexpr (res.value || !resx.value) hipLaunchKernelGGL((k_glstm_fwd<5, res.value, tag.value, carry.value, resx.value, lean.value>), g, b, 0, s, a);
+  }, a.res != 0, a.tags != 0, a.carry != 0, a.res == 2, a.lean != 0, a.cnorm != 0);
   ++g_chain_launches;
 }
 // ---- the unprojected form: plan, sizes, launch ----

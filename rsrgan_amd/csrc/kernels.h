@@ -213,6 +213,7 @@ struct GPersistLayer {
   float* dmt;                                     // backward: [T][N][ldP] total dm per step (the projection's weight gradient reads it)
   int I, P, ldI, ldP, ldH;
   float* res_out;                                 // residual stacks (GPersistArgs::res): [T][N][ldP] s_l = out_l + s_{l-1}: the next layer's input, the output FC's for the top layer
+  const float *ca, *cb;                           // GPersistArgs::cnorm: the folded cell-site batch norm [H], h = sigmoid(o + w_o c) tanh(ca c + cb); null elsewhere
 };
 struct GPersistArgs {
   GPersistLayer L[GP_MAXL];
@@ -255,6 +256,9 @@ struct GPersistArgs {
   // an inference handle's forward (RSRGAN_FLAG_INFER; gpersist.hip LEAN): no per-step stash stores -- the final c / m go to slot 1 of the
   // c / mst buffers (two slots are all they have), out / res_out are written where the pointer is not null; the forward launches only
   int lean;
+  // a bnlstm inference handle's forward (gpersist.hip CN; bnlstm.hip k_bnl_fold): the cell in front of the output tanh goes through the
+  // per-unit affine map L[l].ca, L[l].cb; with lean and tags only (the forward launch k_glstm_fwd)
+  int cnorm;
 };
 constexpr int GP_TMAX = 2046;                     // longest launch (slot offsets are 32-bit; a longer batch takes the launch-per-phase path)
 bool gpersist_plan(GPersistArgs& a);              // fills NT / NC; false: shape not supported

@@ -180,8 +180,8 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     set_error("invalid sizes in rsrgan_cfg");
     return RSRGAN_ERR_INVALID;
   }
-  if (infer() && (g_dnn() || g_bnl())) {
-    set_error("RSRGAN_FLAG_INFER: an inference-only handle for g_type %d is not built (the sequence generators lstm, res_lstm_l, res_lstm_base, res_lstm_i only)", c.g_type);
+  if (infer() && g_dnn()) {
+    set_error("RSRGAN_FLAG_INFER: an inference-only handle for g_type %d is not built (the sequence generators lstm, res_lstm_l, res_lstm_base, res_lstm_i, bnlstm only)", c.g_type);
     return RSRGAN_ERR_INVALID;
   }
   if (c.d_type != RSRGAN_D_LSTM && c.d_type != RSRGAN_D_DNN) { set_error("Unrecognized D type %d", c.d_type); return RSRGAN_ERR_INVALID; }
@@ -287,6 +287,7 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     g_fc_out_b = G.add("g_model/forward_out/fully_connected/biases", 1, Dout, true);
   } else if (g_bnl()) {                                                  // models/bnlstm.py:101-123
     bnl_params();
+    if (infer()) bnl_infer_layers();                                     // (the same table; gl = the folded views)
   } else {
     set_error("Unrecognized G type %d", c.g_type);                       // gan_rnn_placeholder.py:131-132
     return RSRGAN_ERR_INVALID;
@@ -308,8 +309,10 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   }
   // ---- row padding for the persistent generator recurrences (model.h Bt) ----
   {
-    const int Bp = (Bt + GP_ROWS - 1) / GP_ROWS * GP_ROWS;
-    if (switches().pad_rows && gp_live && Bp != Bt && !g_dnn() && !g_bnl() && !d_dnn() && wavefront()) {
+    int Bp = (Bt + GP_ROWS - 1) / GP_ROWS * GP_ROWS;
+    // (a bnlstm inference handle has no other forward than the persistent one: up to the next count of row groups its plans take -- 1, 2, 4, 8)
+    if (bnl_infer()) for (int g : {1, 2, 4, 8}) if (Bp <= g * GP_ROWS) { Bp = g * GP_ROWS; break; }
+    if (switches().pad_rows && gp_live && Bp != Bt && !g_dnn() && (!g_bnl() || infer()) && !d_dnn() && wavefront()) {
       B = Bp;
       GPersistArgs ga{};
       if (!gpersist_shape(ga, std::min(Tmax, (int)GP_TMAX))) B = Bt;     // (only where the padded batch does take the persistent path)
@@ -332,6 +335,11 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     for (auto& L : *layers) {
       L.KxT = alloc<float>((size_t)4 * L.H * L.ldI);
       L.KhT = alloc<float>((size_t)4 * L.H * L.ldP);
+      if (bnl_infer()) {                                    // (the folded bias and cell pair; no launch-per-phase path, so none of its copies)
+        L.bias_f = alloc<float>((size_t)4 * L.H); L.ca = alloc<float>(L.H); L.cb = alloc<float>(L.H);
+        if (!L.KxT || !L.KhT || !L.bias_f || !L.ca || !L.cb) { set_error("hipMalloc failed (bnlstm folded copies)"); return RSRGAN_ERR_HIP; }
+        continue;
+      }
       L.WpT = L.has_proj ? alloc<float>((size_t)L.P * L.ldH) : nullptr;
       const int ncb = (L.H + 15) / 16, kbI = (L.ldI + L.ldP + 15) / 16, kbP = (L.ldP + 15) / 16, kbH = (L.ldH + 15) / 16, kb4 = (4 * L.H + 15) / 16;
       L.Wg_full = alloc<float>(swizzle_floats(4 * ncb, kbI));
@@ -349,10 +357,11 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   const bool res_sums = c.g_type == RSRGAN_G_RES_LSTM_L || c.g_type == RSRGAN_G_RES_LSTM_I;      // (the output FC reads g_res, not the top layer's out)
   inf_W = std::min(Tmax, (int)INFER_WINDOW);
   for (size_t l = 0; l < gl.size(); ++l) {
-    if (inf) alloc_stash_infer(*this, g_st[l], gl[l], B, inf_W, l + 1 == gl.size() && !res_sums ? Tmax : inf_W);
+    if (bnl_infer()) alloc_stash_infer(*this, g_st[l], gl[l], B, 1, l + 1 == gl.size() ? Tmax : 0);      // (slots 0 and 1; the top layer's outputs)
+    else if (inf) alloc_stash_infer(*this, g_st[l], gl[l], B, inf_W, l + 1 == gl.size() && !res_sums ? Tmax : inf_W);
     else alloc_stash(*this, g_st[l], gl[l], B, Tmax);
   }
-  if (!g_dnn() && !g_bnl() && !gl.empty() && gl.size() <= (size_t)GP_MAXL) {      // the carried state of the stateful forward
+  if (!g_dnn() && (!g_bnl() || inf) && !gl.empty() && gl.size() <= (size_t)GP_MAXL) {      // the carried state of the stateful forward
     for (auto& L : gl) g_state_sf += L.H + L.P;
     g_state = alloc<float>((size_t)B * g_state_sf);
     if (!g_state) { set_error("hipMalloc failed (carried generator state)"); return RSRGAN_ERR_HIP; }
@@ -408,10 +417,10 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     g_act.push_back(x_tm);
     for (size_t l = 0; l + 1 < gfc.size(); ++l) g_act.push_back(alloc<float>(TB * gfc[l].ld_out));
     g_act.push_back(y_tm);
-  } else if (g_bnl()) {
+  } else if (g_bnl() && !inf) {
     const int rc = bnl_alloc();
     if (rc) return rc;
-  } else if (c.g_type == RSRGAN_G_LSTM) {
+  } else if (c.g_type == RSRGAN_G_LSTM || g_bnl()) {
     g_h0 = alloc<float>(TB * ldP);
     g_ins[0] = g_h0;
     for (size_t l = 0; l < gl.size(); ++l) g_ins[l + 1] = g_st[l].out;
@@ -515,7 +524,7 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
       else dw_ws = nullptr;
     }
   }
-  if (gp_live && !g_dnn() && !g_bnl()) {
+  if (gp_live && !g_dnn() && (!g_bnl() || inf)) {
     GPersistArgs ga{};
     gp_Tcap = std::min(Tmax, (int)GP_TMAX);
     gp_noproj = !gl.empty() && !gl[0].has_proj;
@@ -559,6 +568,13 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
         gpersist_rearm();
       } else { gp_gran1 = gp_gran2 = nullptr; gp_ctl = nullptr; }
     }
+  }
+  if (bnl_infer() && !gp_fwd_on()) {
+    // the persistent forward is the only one this handle has (no launch-per-phase path knows the fold): no plan, no handle
+    set_error("g_type bnlstm with RSRGAN_FLAG_INFER: no persistent forward plan for this configuration (batch_size=%d padded to %d rows, %d x %d / p%d; "
+              "gpersist_plan's shapes, every workgroup of a row group resident at once, RSRGAN_GPERSIST / RSRGAN_PAD_ROWS not switched off), "
+              "and a launch-per-phase forward of the folded cell is not built", Bt, B, c.g_layers, c.g_cells, c.g_proj);
+    return RSRGAN_ERR_INVALID;
   }
   {
     // the trailing discriminator BPTT beside k_glstm_bwd (the G-run): both launches' workgroups resident at once -- ask the device
@@ -746,6 +762,7 @@ void Model::refresh_transposes(int net, hipStream_t s) {
     if (tl.n == 16) { launch_transpose_many(tl, s); tl.n = 0; }
     tl.j[tl.n++] = TransposeJob{src, dst, lds_, ldd, R, C, 0};
   };
+  if (net == RSRGAN_NET_G && bnl_infer()) { bnl_refresh_fold(s); return; }      // (its forward copies are the folded ones, nothing else)
   for (auto& L : layers) {
     const float* K = ps.W(L.tK);
     const int H4 = 4 * L.H;
@@ -772,6 +789,7 @@ void Model::refresh_transposes(int net, hipStream_t s) {
 // then rebuilt at the top of rnn_forward / rnn_backward -- the only readers -- instead of after every optimizer step (46 us for the
 // generator's 23 MB, 11 us for the discriminator).
 void Model::refresh_swizzles(int net, hipStream_t s) {
+  if (net == RSRGAN_NET_G && bnl_infer()) return;          // (no launch-per-phase path, none of its copies)
   const ParamSet& ps = net == RSRGAN_NET_G ? G : D;
   auto& layers = net == RSRGAN_NET_G ? gl : dl;
   {
@@ -1096,12 +1114,13 @@ int Model::trail_nrt() const {
 bool Model::gpersist_shape(GPersistArgs& a, int T) const {              // (sizes only: usable before any buffer exists)
   const bool res = (cfg.g_type == RSRGAN_G_RES_LSTM_L || g_resi()) && switches().gp_res;      // the running residual sum rides the hand-offs (gpersist.hip RES)
   // (res_lstm_base, models/res_lstm_base.py:101-139: the same stack of projected cells fed the input frames directly, no sums)
-  if (!gp_live || gl.empty() || gl.size() > (size_t)GP_MAXL || (cfg.g_type != RSRGAN_G_LSTM && cfg.g_type != RSRGAN_G_RES_LSTM_BASE && !res)) return false;
+  if (!gp_live || gl.empty() || gl.size() > (size_t)GP_MAXL || (cfg.g_type != RSRGAN_G_LSTM && cfg.g_type != RSRGAN_G_RES_LSTM_BASE && !res && !bnl_infer())) return false;
   a = GPersistArgs{};
   a.nl = (int)gl.size(); a.N = B; a.T = T; a.H = gl[0].H; a.res = res ? (g_resi() ? 2 : 1) : 0;      // (2: res_lstm_i, the sums are out_l + x -- gpersist.hip RESX, the forward launch only)
   bool noproj = !gl[0].has_proj;
   // ring slots tagged with the parity of the ring pass instead of re-armed with sentinels (gpersist.hip gp_store_t); RSRGAN_GP_TAGS=0: the sentinel form
   a.tags = switches().gp_tags && !noproj ? 1 : 0;
+  if (bnl_infer()) { if (!a.tags) return false; a.cnorm = 1; }      // (gpersist.hip CN: instantiated for tagged rings only; bnl_check refuses the handle)
   for (size_t l = 0; l < gl.size(); ++l) {
     const LstmLayer& L = gl[l];
     if (L.has_proj == noproj || L.H != a.H) return false;
@@ -1130,7 +1149,7 @@ bool Model::gpersist_args(GPersistArgs& a, int T) const {
   for (size_t l = 0; l < gl.size(); ++l) {
     const LstmLayer& L = gl[l]; const LstmStash& S = g_st[l];
     GPersistLayer& G_ = a.L[l];
-    G_.KxT = L.KxT; G_.KhT = L.KhT; G_.bias = G.W(L.tb); G_.wi = G.W(L.twi); G_.wf = G.W(L.twf); G_.wo = G.W(L.two); G_.Wp = L.has_proj ? G.W(L.tWp) : nullptr;
+    G_.KxT = L.KxT; G_.KhT = L.KhT; G_.bias = L.bias_f ? L.bias_f : G.W(L.tb); G_.ca = L.ca; G_.cb = L.cb; G_.wi = G.W(L.twi); G_.wf = G.W(L.twf); G_.wo = G.W(L.two); G_.Wp = L.has_proj ? G.W(L.tWp) : nullptr;
     G_.gates = S.gates; G_.c = S.c; G_.h = S.h; G_.mst = S.mst; G_.out = S.out; G_.dmt = S.dmt;
     G_.res_out = a.res ? g_res[l] : nullptr;
   }
@@ -1815,9 +1834,9 @@ void Model::gstate_xfer(int dir, int T, int rows, const int* mask, hipStream_t s
 }
 
 void Model::g_forward_head(int T, hipStream_t s) {
-  if (cfg.g_type == RSRGAN_G_LSTM) {   // h = leakyrelu(x.W + b)  (models/lstm.py:82-87)
+  if (cfg.g_type == RSRGAN_G_LSTM || g_bnl()) {   // h = leakyrelu(x.W + b)  (models/lstm.py:82-87; bnlstm.py:103-108: relu, as bnl_forward)
     const int P = gR, ldP = pad4(P);
-    gemm(x_tm, ldDin, true, G.W(g_fc_in_w), ldP, false, g_h0, ldP, T * B, P, Din, G.W(g_fc_in_b), 1, cfg.lrelu_alpha, false, s);
+    gemm(x_tm, ldDin, true, G.W(g_fc_in_w), ldP, false, g_h0, ldP, T * B, P, Din, G.W(g_fc_in_b), 1, g_bnl() ? 0.f : cfg.lrelu_alpha, false, s);
   }
 }
 void Model::g_forward_tail(int T, hipStream_t s) {   // y = outputs.W + b (models/lstm.py:121-124)
@@ -1827,7 +1846,7 @@ void Model::g_forward_tail(int T, hipStream_t s) {   // y = outputs.W + b (model
 }
 void Model::g_forward(int T, hipStream_t s, Chain* extra) {
   if (g_dnn()) { bn_eval_call = false; g_frame_forward(T * B, s); g_fwd_valid = true; return; }
-  if (g_bnl()) { bnl_forward(T, false, s); return; }      // (rsrgan_forward_g: decode normalises with the moving statistics)
+  if (g_bnl() && !infer()) { bnl_forward(T, false, s); return; }      // (rsrgan_forward_g: decode normalises with the moving statistics)
   g_forward_head(T, s);
   if (infer()) { infer_forward(T, s); g_forward_tail(T, s); return; }
   if (!extra && persist_forward_g(T, s)) { g_forward_tail(T, s); return; }
@@ -1887,6 +1906,11 @@ void Model::infer_forward(int T, hipStream_t s) {
     launch_window_len(len_dev, len_win, B, t0, Tw, s);
     if (persist && persist_forward_g(Tw, s)) {
       inf_slot = 1;
+    } else if (bnl_infer()) {
+      // (a bnlstm handle: the launch path does not know the fold.  Reached only after persist_disable, whose failure the caller has already
+      // been told by rsrgan_device_status: every later forward reports it again)
+      set_error("g_type bnlstm inference handle: the persistent forward is off after a reported device failure, and no other forward is built");
+      inf_failed = true; break;
     } else if (persist) {
       persist = false;                                   // (no persistent plan takes this shape: the same frames again, in the launch path's windows)
       continue;

@@ -48,6 +48,9 @@ struct LstmLayer {               // one tf.contrib.rnn.LSTMCell(H, use_peepholes
   float *Wg_full = nullptr, *Wg_h = nullptr;              // gates: [x | m] . K and m . K[I:] alone (x-part batched)
   float *WpT_sw = nullptr, *Wp_sw = nullptr;              // projection forward / backward phase A
   float *Kb_full = nullptr, *Kb_rec = nullptr;            // backward phase B: rows [0, I+P) and rows [I, I+P) of K
+  // a bnlstm inference handle's view of a BNLSTMCell (bnlstm.cpp bnl_infer_layers): KxT / KhT hold the folded kernels, bias_f the folded
+  // bias [4H], ca / cb the cell site's affine pair [H]; tK = -1 (input_kernel and state_kernel are two tensors).  Null on every other layer.
+  float *bias_f = nullptr, *ca = nullptr, *cb = nullptr;
 };
 
 struct ConvLayer {               // tf.contrib.layers.conv2d([S, fw], SAME) of models/rced.py: weights [S*fw*Cin][Cout] (= [S, fw, Cin, Cout])
@@ -147,6 +150,16 @@ void launch_bnl_ema(const BnlLayer& a, int T, float decay, hipStream_t s);
 void launch_bnl_cell_bwd(const BnlLayer& a, int t, hipStream_t s);
 void launch_bnl_dm(const BnlLayer& a, int t, hipStream_t s);
 void launch_bnl_bn_in_bwd(const BnlLayer& a, float* dzx, int T, hipStream_t s);
+// the decode-time fold of one layer's three batch-norm sites into its kernels, bias and a per-unit affine pair (bnlstm.hip k_bnl_fold)
+struct BnlFold {
+  const float *Wx, *Wh;                       // input_kernel, state_kernel [P][4H]
+  const float* bn[12];                        // {scale, offset, moving_mean, moving_var} x {input, state, cell}
+  const float* bias;                          // [4H]
+  int P, H, ldI, ldP;
+  float eps;
+  float *KxT, *KhT, *bias_f, *ca, *cb;        // [4H][ldI], [4H][ldP], [4H], [H], [H]
+};
+void launch_bnl_fold(const BnlFold& a, hipStream_t s);
 
 struct Model {
   rsrgan_cfg cfg{};
@@ -260,6 +273,11 @@ struct Model {
   void bnl_forward(int T, bool train, hipStream_t s);
   void bnl_backward(int T, float* dy, hipStream_t s);
   int bnl_step(const float* x, const float* labels, const int32_t* lengths, int T, float* out_losses, bool want_grads, hipStream_t s);
+  // RSRGAN_FLAG_INFER with g_type bnlstm: gl holds one folded LstmLayer view per BNLSTMCell, the forward is
+  // infer_forward's persistent branch with GPersistArgs::cnorm, and nothing of bnl_alloc exists
+  bool bnl_infer() const { return g_bnl() && infer(); }
+  int bnl_infer_layers();                                                  // gl + the folded copies' buffers
+  void bnl_refresh_fold(hipStream_t s);                                    // with every refresh of the generator's forward copies
   // R-CED generator (dnn.cpp): rc_act[l] = input of conv layer l as [M][ldCin] positions x channels, rc_act[L] = its output
   std::vector<ConvLayer> gconv;
   FcLayer rc_fc{};

@@ -53,7 +53,7 @@ def build_parser():
     p.add_argument("--decode_chunk", type=int, default=0, help="decode: frames per forward call (run_gan_rnn --decode_chunk)")
     p.add_argument("--decode_streams", type=int, default=1, help="decode with --decode_chunk: utterances decoded side by side")
     p.add_argument("--decode_lean", default=False, action="store_true", help="decode on an inference-only model (inference_only=True: "
-                   "the generator alone, no BPTT stash)")
+                   "the generator alone, no BPTT stash; --g_type bnlstm with --decode_chunk always decodes on it)")
     return p
 
 
@@ -165,12 +165,24 @@ def train(FLAGS, model_factory=None, log=print, net_overrides=None):
     return history
 
 
+def decode_lean(FLAGS, log=print):
+    """whether decode builds the inference-only model: --decode_lean, and -- with one logged line -- a chunked bnlstm decode without it: the
+    stateful forward of a bnlstm model exists on the inference handle only (a training handle answers 'not built')"""
+    if getattr(FLAGS, "decode_lean", False):
+        return True
+    if int(getattr(FLAGS, "decode_chunk", 0) or 0) > 0 and getattr(FLAGS, "g_type", None) == "bnlstm":
+        log("--decode_chunk with --g_type bnlstm: decoding on the inference-only model (as --decode_lean), the only stateful forward bnlstm has")
+        return True
+    return False
+
+
 def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
     """decode (:89-176) = run_gan_rnn.decode on an RNNTrainer: batch 1 (or --decode_streams rows of --decode_chunk frames)"""
     chunk, streams = int(getattr(FLAGS, "decode_chunk", 0) or 0), max(1, int(getattr(FLAGS, "decode_streams", 1) or 1))
+    lean = decode_lean(FLAGS, log) if model_factory is None else False
     mk = model_factory or (lambda: _model(argparse.Namespace(**dict(vars(FLAGS), batch_size=streams if chunk > 0 else 1)), True, None,
                                           net_overrides, max_frames=chunk if chunk > 0 else FLAGS.max_frames,
-                                          **({"inference_only": True} if getattr(FLAGS, "decode_lean", False) else {})))
+                                          **({"inference_only": True} if lean else {})))
     return gan_loop.decode(FLAGS, model_factory=mk, log=log)
 
 

@@ -2,7 +2,7 @@
 """Decode throughput and streaming latency of the sequence generators, one JSON line per configuration.
 
     python tools/decode_bench.py [--g_type res_lstm_l] [--utts 256] [--min_frames 200] [--max_frames 1500] [--repeats 3]
-                                 [--configs a,b,c,d,live] [--lib path/to/librsrgan_hip.so] [--lean]
+                                 [--configs a,b,c,d,live,bnlstm] [--lib path/to/librsrgan_hip.so] [--lean]
 
 A seeded synthetic test set (utterance lengths uniform in [min_frames, max_frames], N(0,1) features, the handle's initial
 variables) goes through
@@ -13,6 +13,11 @@ variables) goes through
     d     --decode_chunk 200 --decode_streams 64
     live  one stream on a batch_size-1 handle: ms per StreamEnhancer.push of 10 / 50 / 100 frames (median and p90 of the pushes
           of one long utterance; the host waits for every push's output, as a recogniser behind it would)
+
+    bnlstm  (not in the default list) 3 x BNLSTMCell(760, num_proj=280), Din 257, Dout 40, the initial variables, one utterance
+          of --bn_frames (1000) frames: whole, in --chunk-frame chunks and as 32 streams on the inference-only model
+          (RNNTrainer(inference_only=True): the persistent forward on the folded variables), and whole on the full model's forward
+          (two launches per step and layer) -- --repeats alternating passes over the four, median us per frame of each
 
 and reports utterances/s and frames/s of every repeat (host wall clock around the whole set, device drained at the end: the
 copies of the inputs and outputs are part of decoding).  `--lib`: time another build of the library (configuration a only
@@ -41,6 +46,49 @@ def build(g_type, batch, frames, din, dout, lean=False):
     return GAN_RNN(None, args, ["gpu:0"], cross_validation=True, infer=True, max_frames=frames, **({"inference_only": True} if lean else {}))
 
 
+def bnlstm_config(a, base):
+    """one utterance through the bnlstm inference model (whole, chunked, 32 streams) and through the full model's forward"""
+    import torch
+    from rsrgan_amd.stream import decode_streams
+    from rsrgan_amd.trainer import RNNTrainer
+    T, chunk = a.bn_frames, a.chunk
+    args = SimpleNamespace(batch_size=1, input_dim=a.input_dim, output_dim=a.output_dim, left_context=0, right_context=0, g_type="bnlstm",
+                           keep_prob=1.0, batch_norm=False, num_gpu=1, save_dir=None, l2_scale=0.0)
+
+    def mk(batch, frames, lean):
+        return RNNTrainer(None, SimpleNamespace(**dict(vars(args), batch_size=batch)), ["gpu:0"], cross_validation=True, max_frames=frames,
+                          inference_only=lean)
+    utt = np.random.default_rng(a.seed).standard_normal((T, a.input_dim)).astype(np.float32)
+    ln = np.array([T], np.int32)
+    whole, chunked, many, full = mk(1, T, True), mk(1, chunk, True), mk(32, chunk, True), mk(1, T, False)
+    g = whole.get_vars()[0]
+    for m in (chunked, many):
+        m.set_vars(g)
+    full.set_vars(g, None)
+    runs = {
+        "whole": (T, lambda: whole.forward(utt[None], ln)),
+        "chunked": (T, lambda: sum(1 for _ in decode_streams(chunked, iter([utt]), chunk, 1))),
+        "streams32": (32 * T, lambda: sum(1 for _ in decode_streams(many, iter([utt] * 32), chunk, 32))),
+        "full_forward": (T, lambda: full.forward(utt[None], ln)),
+    }
+    y_lean, y_full = np.asarray(whole.forward(utt[None], ln), np.float64), np.asarray(full.forward(utt[None], ln), np.float64)
+    secs = {k: [] for k in runs}
+    for rep_ in range(a.repeats + 1):                     # (pass 0 warms every shape up)
+        for k, (_, fn) in runs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if rep_:
+                secs[k].append(time.perf_counter() - t0)
+    rec = dict(base, config="bnlstm", g_type="bnlstm", utterances=1, frames=T, chunk=chunk,
+               lean_vs_full_rel=float(np.linalg.norm(y_lean - y_full) / np.linalg.norm(y_full)),
+               device_bytes=dict(inference=whole.engine.device_bytes(), full=full.engine.device_bytes()))
+    for k, (frames, _) in runs.items():
+        rec[k] = dict(seconds=[round(s, 5) for s in secs[k]], us_per_frame_median=round(1e6 * float(np.median(secs[k])) / frames, 3))
+    print(json.dumps(rec), flush=True)
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--g_type", default="res_lstm_l")
@@ -55,6 +103,7 @@ def main(argv=None):
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--lib", default=None)
     p.add_argument("--lean", default=False, action="store_true", help="run the configurations on an inference-only model")
+    p.add_argument("--bn_frames", type=int, default=1000, help="configuration bnlstm: frames of its utterance")
     a = p.parse_args(argv)
     if a.lib:
         from rsrgan_amd import _lib
@@ -134,6 +183,9 @@ def main(argv=None):
                 out["push_%d" % n] = dict(pushes=len(ms), ms_median=round(float(np.median(ms)), 4), ms_p90=round(float(np.percentile(ms, 90)), 4),
                                           ms_per_frame=round(float(np.median(ms)) / n, 5))
             print(json.dumps(dict(base, config="live", batch_size=1, **out)), flush=True)
+        elif name == "bnlstm":
+            bnlstm_config(a, base)
+            continue
         else:
             raise SystemExit("unknown configuration %r" % name)
         del model
