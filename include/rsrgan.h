@@ -414,6 +414,19 @@ int rsrgan_op_bn_forward(const float* z, int32_t ldz, float* y, int32_t ldy, int
 int rsrgan_op_bn_backward(float* dy, int32_t ldd, const float* y, int32_t ldy, const float* z, int32_t ldz, int32_t rows, int32_t cols,
                           int32_t calls, const float* stat, int32_t ldc, float* dbeta, float* dgamma, int32_t accumulate, int32_t relu,
                           float* sums, float* scratch, int64_t scratch_floats, void* stream);
+/* The sequence form (csrc/bn_seq.hip; tests/test_gpu_bn_seq_ops.py): one call of the same layer followed by a leaky-ReLU of slope
+ * alpha (relu = 0: no activation, y is not read by the backward pass), under the row rule of a padded time-major batch: row r counts
+ * iff Bp == 0 || r % Bp < Bt.  The moments and the backward sums run over the counted rows (n of them); y and dz are written as exact
+ * zeros on the other rows whatever z and dy hold there.  Arguments, layouts, padding-column contract and refusals are those of
+ * rsrgan_op_bn_forward / _backward (y and dz come out 0 in the padding columns); refused in addition: alpha outside [0, 1], a row
+ * rule other than Bp = Bt = 0 or 1 <= Bt <= Bp, rows no multiple of Bp.  The backward pass also writes sums = [s1 / n, s2 / n]. */
+int rsrgan_op_bn_seq_forward(const float* z, int32_t ldz, float* y, int32_t ldy, int32_t rows, int32_t cols, float* const* vars,
+                             float* stat, int32_t ldc, int32_t training, int32_t relu, float alpha, int32_t Bp, int32_t Bt,
+                             float* scratch, int64_t scratch_floats, void* stream);
+int rsrgan_op_bn_seq_backward(float* dy, int32_t ldd, const float* y, int32_t ldy, const float* z, int32_t ldz, int32_t rows,
+                              int32_t cols, const float* stat, int32_t ldc, float* dbeta, float* dgamma, int32_t accumulate,
+                              int32_t relu, float alpha, int32_t Bp, int32_t Bt, float* sums, float* scratch, int64_t scratch_floats,
+                              void* stream);
 /* the update ops of n = 1..24 layers in one launch (launch_bn_commit_many): entry i has vars[8 * i .. 8 * i + 7], stat[i] and
  * dims[4 * i ..] = cols, ldc, times0, times1 (statistics slot 0 applied times0 times, then slot 1 times1 times).  single != 0: n = 1
  * and times1 = 0 through launch_bn_commit.  Refused: n outside 1..24, a null pointer, negative times, cols < 1, ldc % 4 or

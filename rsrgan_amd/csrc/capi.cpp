@@ -198,8 +198,23 @@ static int copy_params(rsrgan_handle h, int net, int what, float* dense, bool to
   if (!buf) { set_error("buffer %d not present for net %d", what, net); return RSRGAN_ERR_INVALID; }
   StreamScope sc(h->m, stream);
   hipStream_t s = sc.work;
-  for (const TensorDesc& t : p->t) launch_pad_copy(dense + t.dense_off, buf + t.off, t.rows, t.cols, t.ld, to_padded, s);
+  // (an inference handle under RSRGAN_FLAG_BATCH_NORM: the device copy of the input FC is the folded one, the variable as it was set
+  //  comes from the host)
+  const bool folded = !to_padded && what == 0 && net == RSRGAN_NET_G && h->m.seq_bn_infer() && !h->m.g_w0_host.empty();
+  for (size_t i = 0; i < p->t.size(); ++i) {
+    const TensorDesc& t = p->t[i];
+    if (folded && (int)i == h->m.g_fc_in_w) {
+      if (hipMemcpy2DAsync(dense + t.dense_off, (size_t)t.cols * sizeof(float), h->m.g_w0_host.data(), (size_t)t.ld * sizeof(float),
+                           (size_t)t.cols * sizeof(float), t.rows, hipMemcpyHostToDevice, s) != hipSuccess) {
+        set_error("rsrgan_get_params: copying the input FC's weights from the host failed");
+        return RSRGAN_ERR_HIP;
+      }
+      continue;
+    }
+    launch_pad_copy(dense + t.dense_off, buf + t.off, t.rows, t.cols, t.ld, to_padded, s);
+  }
   if (to_padded && what == 0) {
+    if (net == RSRGAN_NET_G) h->m.g_fc_in_unfolded = true;
     h->m.refresh_transposes(net, s);
     if (net == RSRGAN_NET_G) h->m.g_fwd_valid = false;
   }
@@ -285,6 +300,11 @@ int rsrgan_forward_g_stream(rsrgan_handle h, const float* x, const int32_t* leng
   return guard("rsrgan_forward_g_stream", [&]() -> int {
     Model& m = h->m;
     if (int rc = gstate_check(m, "rsrgan_forward_g_stream")) return rc;
+    if (m.seq_bn() && !m.infer() && !m.cfg.cross_validation) {
+      set_error("rsrgan_forward_g_stream: RSRGAN_FLAG_BATCH_NORM on a training handle normalises with each call's batch moments, so a chunked "
+                "forward would differ from the whole utterance; stream on a cross_validation or an inference handle (the moving statistics)");
+      return RSRGAN_ERR_INVALID;
+    }
     if (!y) { set_error("null output"); return RSRGAN_ERR_INVALID; }
     StreamScope sc(m, stream);
     hipStream_t s = sc.work;
@@ -823,6 +843,47 @@ int rsrgan_op_bn_backward(float* dy, int32_t ldd, const float* y, int32_t ldy, c
   launch_bn_backward(dy, ldd, y, ldy, z, ldz, rows, cols, stat, ldc, dbeta, dgamma, accumulate != 0, relu != 0, sums, scratch,
                      (size_t)scratch_floats, (hipStream_t)stream, calls);
   if (hipGetLastError() != hipSuccess) { set_error("op_bn_backward launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
+
+// the sequence form (bn_seq.hip): one call, a leaky-ReLU of slope alpha and the row rule (Bp, Bt) of a padded batch
+#define OP_BN_SEQ_RULE(who) \
+  OP_REFUSE(!(alpha >= 0.f && alpha <= 1.f), who ": alpha = %g outside [0, 1]", (double)alpha); \
+  OP_REFUSE(Bp < 0 || Bt < 0 || (Bp == 0 && Bt != 0) || (Bp > 0 && (Bt < 1 || Bt > Bp)), \
+            who ": row rule (Bp %d, Bt %d): Bp = Bt = 0 counts every row, else 1 <= Bt <= Bp", Bp, Bt); \
+  OP_REFUSE(Bp > 0 && rows % Bp, who ": rows = %d is no multiple of Bp = %d", rows, Bp)
+
+int rsrgan_op_bn_seq_forward(const float* z, int32_t ldz, float* y, int32_t ldy, int32_t rows, int32_t cols, float* const* vars, float* stat,
+                             int32_t ldc, int32_t training, int32_t relu, float alpha, int32_t Bp, int32_t Bt, float* scratch,
+                             int64_t scratch_floats, void* stream) {
+  const int calls = 1;
+  OP_REFUSE(!z || !y || !vars || !stat || !scratch, "op_bn_seq_forward: null pointer (z, y, vars, stat or scratch)");
+  OP_BN_SHAPE("op_bn_seq_forward", ldz, ldy, ldz);
+  OP_BN_SEQ_RULE("op_bn_seq_forward");
+  OP_REFUSE(((size_t)z & 15) || ((size_t)y & 15) || ((size_t)stat & 15), "op_bn_seq_forward: z, y or stat not 16-byte aligned");
+  OP_REFUSE((size_t)scratch & 3, "op_bn_seq_forward: scratch not 4-byte aligned");
+  BnVars v;
+  OP_REFUSE(!op_bn_vars(vars, v), "op_bn_seq_forward: a null or misaligned pointer among the eight variables");
+  launch_bn_seq_forward(z, ldz, y, ldy, rows, cols, v, stat, ldc, training != 0, relu != 0, alpha, Bp, Bt, scratch, (size_t)scratch_floats,
+                        (hipStream_t)stream);
+  if (hipGetLastError() != hipSuccess) { set_error("op_bn_seq_forward launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
+
+int rsrgan_op_bn_seq_backward(float* dy, int32_t ldd, const float* y, int32_t ldy, const float* z, int32_t ldz, int32_t rows, int32_t cols,
+                              const float* stat, int32_t ldc, float* dbeta, float* dgamma, int32_t accumulate, int32_t relu, float alpha,
+                              int32_t Bp, int32_t Bt, float* sums, float* scratch, int64_t scratch_floats, void* stream) {
+  const int calls = 1;
+  OP_REFUSE(!dy || !y || !z || !stat || !sums || !scratch, "op_bn_seq_backward: null pointer (dy, y, z, stat, sums or scratch)");
+  OP_REFUSE((dbeta == nullptr) != (dgamma == nullptr), "op_bn_seq_backward: dbeta and dgamma must both be given or both be null");
+  OP_BN_SHAPE("op_bn_seq_backward", ldd, ldy, ldz);
+  OP_BN_SEQ_RULE("op_bn_seq_backward");
+  OP_REFUSE(((size_t)dy & 15) || ((size_t)y & 15) || ((size_t)z & 15) || ((size_t)stat & 15) || ((size_t)sums & 15),
+            "op_bn_seq_backward: dy, y, z, stat or sums not 16-byte aligned");
+  OP_REFUSE(((size_t)scratch & 3) || ((size_t)dbeta & 3) || ((size_t)dgamma & 3), "op_bn_seq_backward: scratch, dbeta or dgamma not 4-byte aligned");
+  launch_bn_seq_backward(dy, ldd, y, ldy, z, ldz, rows, cols, stat, ldc, dbeta, dgamma, accumulate != 0, relu != 0, alpha, Bp, Bt, sums, scratch,
+                         (size_t)scratch_floats, (hipStream_t)stream);
+  if (hipGetLastError() != hipSuccess) { set_error("op_bn_seq_backward launch failed"); return RSRGAN_ERR_HIP; }
   return RSRGAN_OK;
 }
 

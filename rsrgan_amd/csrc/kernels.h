@@ -441,6 +441,17 @@ void launch_bn_commit_many(const BnCommitList& cl, hipStream_t s);
 enum { BN_ROUTE_NONE = 0, BN_ROUTE_SMALL = 1, BN_ROUTE_SLICED = 2, BN_ROUTE_NARROW = 3 };
 struct BnPlanRecord { int route, backward, calls, launches, slices, per, pgx, pgy, egrid, q, R; };
 extern thread_local BnPlanRecord g_bn_last_plan;
+// ---- the same layer on the sequence path (bn_seq.hip): leaky-ReLU of slope alpha (act) and the row rule (Bp, Bt) of a padded
+// batch -- row r counts iff Bp == 0 || r % Bp < Bt; the statistics run over the counted rows, y / dz are exact zeros on the others.
+// Two launches per direction (one with training = false); scratch: 2 x slices x cols floats of partials, slices <= 32.
+int bn_seq_count(int rows, int Bp, int Bt);              // n, the number of counted rows
+void launch_bn_seq_forward(const float* z, int ldz, float* y, int ldy, int rows, int cols, const BnVars& v, float* stat, int ldc, bool training,
+                           bool act, float alpha, int Bp, int Bt, float* scratch, size_t scratch_floats, hipStream_t s);
+void launch_bn_seq_backward(float* dy, int ldd, const float* y, int ldy, const float* z, int ldz, int rows, int cols, const float* stat, int ldc,
+                            float* dbeta, float* dgamma, bool accumulate, bool act, float alpha, int Bp, int Bt, float* sums, float* scratch,
+                            size_t scratch_floats, hipStream_t s);
+// inference handle: W[k][c] *= a[c] in place, bias[c] = b[c], from the moving statistics
+void launch_bn_seq_fold(float* W, int ldw, int K, int cols, const BnVars& v, float* bias, hipStream_t s);
 void launch_colsum(const float* a, int lda, const float* b, int ldb, float* out, int rows, int cols,
                    float* scratch /* >= 64*cols floats */, hipStream_t s);
 

@@ -221,10 +221,18 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   };
   if (g_bnl()) { const int rc = bnl_check(c); if (rc) return rc; }
   if (bn_on() && !g_dnn()) {
-    set_error("RSRGAN_FLAG_BATCH_NORM is built for the frame-level generators (dnn, rced) + discriminator_dnn only");
-    return RSRGAN_ERR_INVALID;
+    // the sequence path: the flag acts in models/lstm.py:61-87 alone (res_lstm_*'s input FC is commented out, discriminator_lstm's too)
+    if (c.g_type != RSRGAN_G_LSTM) {
+      set_error("RSRGAN_FLAG_BATCH_NORM on the sequence path is built for g_type lstm only (the reference's res_lstm_* generators ignore "
+                "batch_norm: build them without the flag; bnlstm's input-FC batch norm is not built), got g_type %d", c.g_type);
+      return RSRGAN_ERR_INVALID;
+    }
+    if (c.d_type != RSRGAN_D_LSTM) {
+      set_error("RSRGAN_FLAG_BATCH_NORM with a sequence generator needs discriminator_lstm (discriminator_dnn's batch norm is built for the frame-level generators only)");
+      return RSRGAN_ERR_INVALID;
+    }
   }
-  if (bn_on()) {      // the update ops of a run are ONE launch over a fixed table (kernels.h BnCommitList): refuse what it cannot hold
+  if (bn_on() && g_dnn()) {      // the update ops of a run are ONE launch over a fixed table (kernels.h BnCommitList): refuse what it cannot hold
     const int nbn = (c.g_type == RSRGAN_G_RCED ? 9 : c.g_layers) + (c.d_type == RSRGAN_D_DNN ? c.d_layers : 0);
     if (nbn > 24) { set_error("batch norm: %d normalised layers, at most 24 are supported", nbn); return RSRGAN_ERR_INVALID; }
   }
@@ -259,7 +267,14 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     add_fc(G, gfc, fc_name("g_model", c.g_layers), in, Dout);
   } else if (c.g_type == RSRGAN_G_LSTM) {                                // models/lstm.py:82-124
     g_fc_in_w = G.add("g_model/fully_connected/weights", Din, P, false);
-    g_fc_in_b = G.add("g_model/fully_connected/biases", 1, P, true);
+    if (bn_on()) {
+      // normalizer_fn=batch_norm: no biases.  gan_rnn_placeholder.py:254 / rnn_trainer.py:164 sum l2_loss over every trainable g_ variable
+      // without "bias" in its name: beta and gamma TAKE the L2 term here (the frame-level nets regularise weights only)
+      add_bn(G, "g_model/fully_connected", P, g_bn_t);
+      for (int k = 0; k < 2; ++k) { G.t[g_bn_t[k]].l2 = true; G.t[g_bn_t[k]].const_init = true; }
+    } else {
+      g_fc_in_b = G.add("g_model/fully_connected/biases", 1, P, true);
+    }
     for (int l = 0; l < c.g_layers; ++l)
       add_lstm(G, gl, "g_model/rnn/multi_rnn_cell/cell_" + std::to_string(l) + "/lstm_cell", P, H, c.g_proj);
     g_fc_out_w = G.add("g_model/fully_connected_1/weights", P, Dout, false);
@@ -424,6 +439,14 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     g_h0 = alloc<float>(TB * ldP);
     g_ins[0] = g_h0;
     for (size_t l = 0; l < gl.size(); ++l) g_ins[l + 1] = g_st[l].out;
+    if (seq_bn_infer()) {
+      g_bn_fold_b = alloc<float>(ldP);
+      if (!g_bn_fold_b) { set_error("hipMalloc failed (sequence batch norm)"); return RSRGAN_ERR_HIP; }
+    } else if (seq_bn()) {
+      g_z0 = alloc<float>(TB * ldP); g_bn_stat = alloc<float>((size_t)BN_STAT_ROWS * ldP); g_bn_sums = alloc<float>((size_t)2 * ldP);
+      g_bn_scr = alloc<float>((size_t)64 * ldP);
+      if (!g_z0 || !g_bn_stat || !g_bn_sums || !g_bn_scr) { set_error("hipMalloc failed (sequence batch norm)"); return RSRGAN_ERR_HIP; }
+    }
   } else {
     g_ins[0] = x_tm;
     for (size_t l = 0; l < gl.size(); ++l) {
@@ -651,7 +674,7 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
     std::vector<float> host((size_t)ps->padded, 0.f);
     if (ps == &G && g_bnl()) bnl_init(host, seed);
     else for (auto& t : ps->t) {
-      if (!t.l2) {                                           // biases: zero, except R-CED's output FC (rced.py:116: 0.1)
+      if (!t.l2 || t.const_init) {                           // biases: zero, except R-CED's output FC (rced.py:116: 0.1)
         if (t.bias_init != 0.f)
           for (int cc = 0; cc < t.cols; ++cc) host[(size_t)t.off + cc] = t.bias_init;
         continue;
@@ -673,6 +696,7 @@ int Model::init(const rsrgan_cfg& c, uint64_t seed) {
   hdyn[DYN_L2] = c.l2_scale; hdyn[DYN_CLIP] = c.clip_norm; hdyn[DYN_B1] = c.adam_beta1; hdyn[DYN_B2] = c.adam_beta2;
   hdyn[DYN_EPS] = c.adam_eps; hdyn[DYN_EMA] = c.ema_decay;
   HIPC(hipMemcpy(dyn, hdyn, sizeof(hdyn), hipMemcpyHostToDevice));
+  g_fc_in_unfolded = true;                         // (the initial values were just uploaded)
   refresh_transposes(RSRGAN_NET_G, nullptr);
   if (!inf) {
     refresh_transposes(RSRGAN_NET_D, nullptr);
@@ -727,7 +751,10 @@ int Model::build_buckets() {
     bool ok = true;
     GradBucket b;
     range(G, g_fc_out_w, g_fc_out_b, b); ok = ok && g_fc_out_b == g_fc_out_w + 1; v.push_back(b);
-    if (cfg.g_type == RSRGAN_G_LSTM) { range(G, g_fc_in_w, g_fc_in_b, b); ok = ok && g_fc_in_b == g_fc_in_w + 1; v.push_back(b); }
+    if (cfg.g_type == RSRGAN_G_LSTM) {
+      const int hi = seq_bn() ? g_bn_t[7] : g_fc_in_b;                 // (batch norm: weights, then the eight BatchNorm variables)
+      range(G, g_fc_in_w, hi, b); ok = ok && hi == g_fc_in_w + (seq_bn() ? 8 : 1); v.push_back(b);
+    }
     for (auto& L : gl) {
       const int lo = L.tK, hi = L.has_proj ? L.tWp : L.two;
       ok = ok && L.tb > lo && L.tb < hi && L.twf > lo && L.twi > lo && L.two <= hi && hi - lo == (L.has_proj ? 5 : 4);
@@ -763,6 +790,7 @@ void Model::refresh_transposes(int net, hipStream_t s) {
     tl.j[tl.n++] = TransposeJob{src, dst, lds_, ldd, R, C, 0};
   };
   if (net == RSRGAN_NET_G && bnl_infer()) { bnl_refresh_fold(s); return; }      // (its forward copies are the folded ones, nothing else)
+  if (net == RSRGAN_NET_G && seq_bn_infer()) seq_bn_fold(s);                     // (folds only behind a writer of the variables: g_fc_in_unfolded)
   for (auto& L : layers) {
     const float* K = ps.W(L.tK);
     const int H4 = 4 * L.H;
@@ -1836,8 +1864,54 @@ void Model::gstate_xfer(int dir, int T, int rows, const int* mask, hipStream_t s
 void Model::g_forward_head(int T, hipStream_t s) {
   if (cfg.g_type == RSRGAN_G_LSTM || g_bnl()) {   // h = leakyrelu(x.W + b)  (models/lstm.py:82-87; bnlstm.py:103-108: relu, as bnl_forward)
     const int P = gR, ldP = pad4(P);
+    if (seq_bn_infer()) {      // the folded layer: h = leakyrelu(x.W' + b)
+      gemm(x_tm, ldDin, true, G.W(g_fc_in_w), ldP, false, g_h0, ldP, T * B, P, Din, g_bn_fold_b, 1, cfg.lrelu_alpha, false, s);
+      return;
+    }
+    if (seq_bn()) {      // h = leakyrelu(batch_norm(x.W)): batch moments over the caller's rows in a training fetch, else the moving statistics
+      gemm(x_tm, ldDin, true, G.W(g_fc_in_w), ldP, false, g_z0, ldP, T * B, P, Din, nullptr, 0, 0.f, false, s);
+      g_fwd_bn_train = bn_training();
+      launch_bn_seq_forward(g_z0, ldP, g_h0, ldP, T * B, P, bn_vars(G, g_bn_t), g_bn_stat, ldP, g_fwd_bn_train, true, cfg.lrelu_alpha, pad_Bp(), Bt,
+                            g_bn_scr, (size_t)64 * ldP, s);
+      return;
+    }
     gemm(x_tm, ldDin, true, G.W(g_fc_in_w), ldP, false, g_h0, ldP, T * B, P, Din, G.W(g_fc_in_b), 1, g_bnl() ? 0.f : cfg.lrelu_alpha, false, s);
   }
+}
+// d = d(h0) [R][ldP] -> the input layer's parameter gradients (models/lstm.py:82-87).  Without batch norm: through the leaky-ReLU, dW and
+// the bias column sum.  With it: the normaliser's backward (dbeta, dgamma, dz in place, exact zeros on the padding rows), then dW = x^T.dz.
+void Model::g_fc_in_backward(float* d, int R, float* colsum_scratch, hipStream_t q) {
+  const int P = gR, ldP = pad4(P);
+  if (seq_bn()) {
+    launch_bn_seq_backward(d, ldP, g_h0, ldP, g_z0, ldP, R, P, g_bn_stat, ldP, G.Gd(g_bn_t[0]), G.Gd(g_bn_t[1]), false, true, cfg.lrelu_alpha,
+                           pad_Bp(), Bt, g_bn_sums, g_bn_scr, (size_t)64 * ldP, q);
+    gemm(x_tm, ldDin, false, d, ldP, false, G.Gd(g_fc_in_w), ldP, Din, P, R, nullptr, 0, 0.f, false, q);
+    return;
+  }
+  launch_lrelu_bwd(g_h0, d, (size_t)R, P, ldP, cfg.lrelu_alpha, q);
+  gemm(x_tm, ldDin, false, d, ldP, false, G.Gd(g_fc_in_w), ldP, Din, P, R, nullptr, 0, 0.f, false, q);
+  launch_colsum(d, ldP, nullptr, 0, G.Gd(g_fc_in_b), R, P, colsum_scratch, q);
+}
+// An inference handle's input FC: keep the weights as they were set on the host, then fold the moving statistics into the device copy
+// in place.  Only a writer of the variables (Model::init, rsrgan_set_params) raises g_fc_in_unfolded; without it the device copy is
+// already the folded one and a second fold would scale it again and lose the host copy, so the call does nothing.
+void Model::seq_bn_fold(hipStream_t s) {
+  if (!g_fc_in_unfolded) return;
+  const TensorDesc& t = G.t[g_fc_in_w];
+  g_w0_host.resize((size_t)t.rows * t.ld);
+  if (hipMemcpyAsync(g_w0_host.data(), G.W(g_fc_in_w), g_w0_host.size() * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess) {
+    set_error("RSRGAN_FLAG_BATCH_NORM | RSRGAN_FLAG_INFER: copying the input FC's weights to the host failed");
+    inf_failed = true;
+    return;
+  }
+  launch_bn_seq_fold(G.W(g_fc_in_w), t.ld, t.rows, gR, bn_vars(G, g_bn_t), g_bn_fold_b, s);
+  g_fc_in_unfolded = false;
+}
+// the generator's UPDATE_OPS of one run (gan_rnn_placeholder.py:164-175 filters them by scope; tower 0 builds G twice, :196,204): the
+// statistics of the run's forward, `times` times.  The discriminator has no batch norm: a D-run commits nothing.
+void Model::seq_bn_commit(int times, hipStream_t s) {
+  launch_bn_commit(gR, bn_vars(G, g_bn_t), g_bn_stat, pad4(gR), times, s);
 }
 void Model::g_forward_tail(int T, hipStream_t s) {   // y = outputs.W + b (models/lstm.py:121-124)
   const int P = gR, ldP = pad4(P);
@@ -2003,9 +2077,7 @@ void Model::g_backward_pass(int T, float* dy, hipStream_t s) {
     }
     if (!persist_backward_g(ch, T, s)) rnn_backward(chains, T, s);
     // through leakyrelu and the input FC (models/lstm.py:82-87)
-    launch_lrelu_bwd(g_h0, cur, (size_t)R, P, ldP, cfg.lrelu_alpha, s);
-    gemm(x_tm, ldDin, false, cur, ldP, false, G.Gd(g_fc_in_w), ldP, Din, P, R, nullptr, 0, 0.f, false, s);
-    launch_colsum(cur, ldP, nullptr, 0, G.Gd(g_fc_in_b), R, P, scratch, s);
+    g_fc_in_backward(cur, R, scratch, s);
   } else if (cfg.g_type == RSRGAN_G_RES_LSTM_L) {
     // d(inputs_l) = dx_l + d(inputs_{l+1}): accumulate in place in one buffer
     for (int l = (int)Lg - 1; l >= 0; --l) {
@@ -2028,6 +2100,7 @@ int Model::d_backward(const float* x, const float* labels, const int32_t* length
   if (g_dnn()) return dnn_d_backward(x, labels, T, out_losses, want_grads, s);
   if (d_dnn()) { nr = nullptr; nf = nullptr; }    // discriminator_dnn.py:58: the noise layer is commented out
   bn_eval_call = !want_grads;                      // (is_training of this fetch: the DropoutWrapper masks; read by seq_drop_on() below)
+  if (seq_bn()) g_fwd_bn_train = bn_training();    // (on the host: a replayed segment does not run g_forward_head's body)
   dfree_current = false;                           // this run writes the discriminator's stash and input rows
   // RSRGAN_DPIPE: D(real) on the side stream, ahead of this call's place in the stream; the run itself is k_glstm_fwd_dt (D(G(x)) trailing)
   bool dsplit = false;
@@ -2127,6 +2200,12 @@ int Model::g_backward(const float* x, const float* labels, const int32_t* length
   if (g_dnn()) return dnn_g_backward(x, labels, T, out_losses, want_grads, reuse, s);
   if (g_bnl()) return bnl_step(x, labels, lengths, T, out_losses, want_grads, s);
   bn_eval_call = !want_grads;                      // (is_training of this fetch)
+  if (seq_bn() && want_grads && cfg.cross_validation) {
+    set_error("RSRGAN_FLAG_BATCH_NORM: gradients of the cross_validation model (moving-statistics batch norm) are not built");
+    return RSRGAN_ERR_INVALID;
+  }
+  if (seq_bn() && reuse && g_fwd_bn_train != bn_training()) reuse = false;      // the forward at hand normalised the other way
+  if (seq_bn() && !reuse) g_fwd_bn_train = bn_training();
   dfree_current = false;                           // this run reads and writes the discriminator's stash
   if (seq_drop_on()) { reuse = false; launch_drop_tick(drop_ctr, s); }     // a new sess.run: new DropoutWrapper masks, a new forward
   if (supervised()) {
@@ -2144,6 +2223,7 @@ int Model::g_backward(const float* x, const float* labels, const int32_t* length
         launch_l2(G.w, G.g, G.ct, dyn + DYN_L2, G.partial, s);
         launch_l2_total(G.partial, G.ct.n_chunks, dyn + DYN_L2, losses + 5, s);
       }
+      if (seq_bn() && bn_training()) seq_bn_commit(2, s);      // rnn_trainer.py:131-132,148-150: the generator is built twice
       { finish_buckets(RSRGAN_NET_G, s); g_grads_ready = true; }
     } else {
       launch_mse(y_tm, lab_tm, ldDout, nullptr, T * B, Dout, dyn + DYN_LAMBDA, false, losses + 4, scratch, s, pad_Bp(), Bt);
@@ -2215,6 +2295,8 @@ int Model::g_backward(const float* x, const float* labels, const int32_t* length
       (void)hipMemsetAsync(losses + 5, 0, sizeof(float), s);
     }
     launch_g_total(losses + 3, dyn + DYN_LAMBDA, s);
+    // the G-run's update ops, at the end of the run and inside its captured segment: the generator's, twice with the same batch
+    if (seq_bn() && want_grads && bn_training()) seq_bn_commit(2, s);
   };
 
   // the discriminator's BPTT in its trailing form beside the generator's (persist_backward_trail): decided here, on the host
@@ -2236,9 +2318,7 @@ int Model::g_backward(const float* x, const float* labels, const int32_t* length
         launch_colsum(dy, ldDout, nullptr, 0, G.Gd(g_fc_out_b), R, Dout, (side && q == side) ? scratch2 : scratch, q);
       };
       post = [&](hipStream_t q) {
-        launch_lrelu_bwd(g_h0, bufA, (size_t)R, gR, ldP_, cfg.lrelu_alpha, q);
-        gemm(x_tm, ldDin, false, bufA, ldP_, false, G.Gd(g_fc_in_w), ldP_, Din, gR, R, nullptr, 0, 0.f, false, q);
-        launch_colsum(bufA, ldP_, nullptr, 0, G.Gd(g_fc_in_b), R, gR, (side && q == side) ? scratch2 : scratch, q);
+        g_fc_in_backward(bufA, R, (side && q == side) ? scratch2 : scratch, q);
       };
     }
     // the next D-run's D(real) (32 workgroups that own their CUs) runs beside these launches when the host is ahead: the chip-filling
@@ -2348,9 +2428,7 @@ int Model::g_backward(const float* x, const float* labels, const int32_t* length
           launch_colsum(dy, ldDout, nullptr, 0, G.Gd(g_fc_out_b), R, Dout, (side && q == side) ? scratch2 : scratch, q);
         };
         post = [&](hipStream_t q) {        // through leakyrelu and the input FC (models/lstm.py:82-87); bufA holds d(h0)
-          launch_lrelu_bwd(g_h0, bufA, (size_t)R, P, ldP, cfg.lrelu_alpha, q);
-          gemm(x_tm, ldDin, false, bufA, ldP, false, G.Gd(g_fc_in_w), ldP, Din, P, R, nullptr, 0, 0.f, false, q);
-          launch_colsum(bufA, ldP, nullptr, 0, G.Gd(g_fc_in_b), R, P, (side && q == side) ? scratch2 : scratch, q);
+          g_fc_in_backward(bufA, R, (side && q == side) ? scratch2 : scratch, q);
         };
       }
       if (gsplit) {      // (RSRGAN_DPIPE) the launch only: ev_dfree is recorded behind it, what follows is a segment of its own (bwd_rest)
@@ -2393,9 +2471,7 @@ int Model::g_backward(const float* x, const float* labels, const int32_t* length
     if (cfg.g_type == RSRGAN_G_LSTM && !fcs_inside) {
       run_seg(seg_key(SEG_G_FCIN, T, kbits), s, [&]() {
         // through leakyrelu and the input FC (models/lstm.py:82-87); bufA holds d(h0)
-        launch_lrelu_bwd(g_h0, bufA, (size_t)R, P, ldP, cfg.lrelu_alpha, s);
-        gemm(x_tm, ldDin, false, bufA, ldP, false, G.Gd(g_fc_in_w), ldP, Din, P, R, nullptr, 0, 0.f, false, s);
-        launch_colsum(bufA, ldP, nullptr, 0, G.Gd(g_fc_in_b), R, P, scratch, s);
+        g_fc_in_backward(bufA, R, scratch, s);
       });
       if (bucketed) mark_bucket(RSRGAN_NET_G, bi++, s);
     }

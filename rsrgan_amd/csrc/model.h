@@ -26,6 +26,7 @@ struct TensorDesc {
   bool is_vector;
   int xavier_fan_out = 0;   // > 0: fan_out of the xavier limit (conv: receptive field x Cout) instead of cols
   float bias_init = 0.f;    // constant initial value of a bias vector
+  bool const_init = false;  // initialised to bias_init although it takes the L2 term (beta / gamma of the sequence generator's batch norm)
 };
 
 struct ParamSet {
@@ -326,6 +327,25 @@ struct Model {
   BnVars bn_vars(const ParamSet& ps, const int (&tbn)[8]) const;
   void bn_commit_stack(const ParamSet& ps, const std::vector<FcLayer>& L, int times0, int times1, BnCommitList& cl);
   float* bn_sums = nullptr;      // [2][max ld_out] work space of launch_bn_backward
+  // batch norm on the sequence path: g_type lstm's input layer is leakyrelu(batch_norm(x.W)), no bias (models/lstm.py:61-87).
+  // The rows of a padded batch that are the library's own count in no statistic (pad_Bp() / Bt; bn_seq.hip).
+  bool seq_bn() const { return bn_on() && cfg.g_type == RSRGAN_G_LSTM; }
+  int g_bn_t[8] = {-1, -1, -1, -1, -1, -1, -1, -1};     // g_model/fully_connected/BatchNorm/* in the ParamSet
+  float* g_z0 = nullptr;         // [T*B][ldP] x.W before the normaliser (kept for the backward pass)
+  float* g_bn_stat = nullptr;    // [BN_STAT_ROWS][ldP] of the run's forward
+  float* g_bn_sums = nullptr;    // [2][ldP]
+  float* g_bn_scr = nullptr;     // [64][ldP] slice partials (its own: the backward pass may run on the side stream)
+  bool g_fwd_bn_train = false;   // is_training of the forward that filled g_h0 (reuse_g_forward needs the same)
+  void g_fc_in_backward(float* d, int R, float* colsum_scratch, hipStream_t q);      // d(h0) -> the input layer's parameter gradients
+  void seq_bn_commit(int times, hipStream_t s);
+  // RSRGAN_FLAG_INFER with the flag: the moving statistics are folded into the input FC IN PLACE once per rsrgan_set_params (W' = W.a,
+  // bias b: the forward keeps its bias + leaky GEMM epilogue, no launch and no device buffer beyond the folded bias).  The variable as
+  // it was set stays on the host for rsrgan_get_params.
+  bool seq_bn_infer() const { return seq_bn() && infer(); }
+  float* g_bn_fold_b = nullptr;          // [ldP]
+  std::vector<float> g_w0_host;          // g_model/fully_connected/weights [Din][ldP] as set
+  bool g_fc_in_unfolded = false;         // the device copy holds the weights as set (raised by init and rsrgan_set_params, cleared by the fold)
+  void seq_bn_fold(hipStream_t s);
   void d_dnn_forward_loss(int T, int Nd, int n_real, bool want_grads, float* loss3, hipStream_t s, int calls = 1, int call0 = 0);
   void bn_commit_run(bool with_d, hipStream_t s);
   int dnn_d_backward(const float* x, const float* labels, int T, float* out_losses, bool want_grads, hipStream_t s);

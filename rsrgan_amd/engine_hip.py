@@ -571,6 +571,20 @@ class HipEngine:
                                              stat.stride(0), _ptr(dbeta), _ptr(dgamma), 1 if accumulate else 0, 1 if relu else 0, _ptr(sums),
                                              _ptr(scratch), scratch.numel() if scratch_floats is None else scratch_floats, self._stream()))
 
+    def op_bn_seq_forward(self, z, y, rows, cols, bn_vars, stat, scratch, alpha=0.3, Bp=0, Bt=0, training=True, relu=True, scratch_floats=None):
+        """the sequence form: leaky-ReLU of slope alpha; row r counts iff Bp == 0 or r % Bp < Bt (include/rsrgan.h)"""
+        check(self.lib.rsrgan_op_bn_seq_forward(_ptr(z), z.stride(0), _ptr(y), y.stride(0), rows, cols, self._table(bn_vars), _ptr(stat),
+                                                stat.stride(0), 1 if training else 0, 1 if relu else 0, alpha, Bp, Bt, _ptr(scratch),
+                                                scratch.numel() if scratch_floats is None else scratch_floats, self._stream()))
+
+    def op_bn_seq_backward(self, dy, y, z, rows, cols, stat, sums, scratch, alpha=0.3, Bp=0, Bt=0, dbeta=None, dgamma=None, accumulate=False,
+                           relu=True, scratch_floats=None):
+        """dy [rows][ldd] is overwritten by dz (exact zeros on the rows that do not count); sums [2][ldc]"""
+        check(self.lib.rsrgan_op_bn_seq_backward(_ptr(dy), dy.stride(0), _ptr(y), y.stride(0), _ptr(z), z.stride(0), rows, cols, _ptr(stat),
+                                                 stat.stride(0), _ptr(dbeta), _ptr(dgamma), 1 if accumulate else 0, 1 if relu else 0, alpha,
+                                                 Bp, Bt, _ptr(sums), _ptr(scratch),
+                                                 scratch.numel() if scratch_floats is None else scratch_floats, self._stream()))
+
     def op_bn_commit(self, entries, single=False):
         """entries: (bn_vars, stat, cols, times0, times1) per layer; single: k_bn_commit instead of k_bn_commit_many"""
         dims = []

@@ -222,10 +222,16 @@ class GAN_RNN(Model):
         self.MOVING_AVERAGE_DECAY = 0.9999
         self.max_grad_norm = 15
         self.keep_prob = 1.0 if cross_validation else getattr(args, "keep_prob", 1.0)
-        self.batch_norm = getattr(args, "batch_norm", False)
-        if self.batch_norm:
-            raise NotImplementedError("batch_norm is off on this path "
-                                      "(run_gan_rnn_placeholder.sh:131; train_gan_rnn_placeholder.py:723-728)")
+        # args.batch_norm acts in models/lstm.py:61-87 alone: the input layer becomes leakyrelu(batch_norm(x.W, renorm=True)), no bias.
+        # res_lstm_l / res_lstm_base / res_lstm_i build normalizer_params but their input FC is commented out: the flag is a no-op
+        # there and the handle is the one without it.  bnlstm's input-FC batch norm is not built.
+        self.batch_norm = bool(getattr(args, "batch_norm", False))
+        g_type = getattr(args, "g_type", None)
+        if self.batch_norm and g_type == "bnlstm":
+            raise NotImplementedError("bnlstm: the input FC's batch_norm (renorm) is not built")
+        self.engine_batch_norm = self.batch_norm and g_type == "lstm"
+        if self.batch_norm and not self.engine_batch_norm:
+            print("batch_norm=True with g_type {}: the reference ignores it there (the input FC is commented out)".format(g_type))
         self.batch_size = args.batch_size
         self.devices = devices
         self.num_gpu = getattr(args, "num_gpu", 1)
@@ -254,7 +260,8 @@ class GAN_RNN(Model):
             self.engine = HipEngine(batch_size=self.batch_size, max_frames=max_frames or 1000, input_dim=din,
                                     output_dim=self.output_dim, g_type=self.g_type, l2_scale=self.l2_scale,
                                     cross_validation=cross_validation, seed=seed,
-                                    **dict(net_overrides or {}, **({"inference": True} if self.inference_only else {})))
+                                    **dict(net_overrides or {}, **({"inference": True} if self.inference_only else {}),
+                                           **({"batch_norm": True} if self.engine_batch_norm else {})))
         self.ema_enabled = getattr(self.engine, "ema_enabled", True)
         self._scalars = {}
         if share_engine_from is None:
@@ -373,6 +380,29 @@ class GAN_RNN(Model):
             return tw
         tw = tw.cpu().numpy()
         return list(tw[:, 0]), list(tw[:, 1]), list(tw[:, 2]), list(tw[:, 3])
+
+    BN_STATE = ("moving_mean", "moving_variance", "renorm_mean", "renorm_mean_weight", "renorm_stddev", "renorm_stddev_weight")
+
+    def sync_batch_norm_state(self):
+        """GAN.sync_batch_norm_state on the sequence path: every rank commits the statistics of its own batches (the generator's
+        input-FC batch norm; the discriminator has none), the reference's towers update ONE copy.  Puts the mean over ranks of the six
+        statistics -- nothing else -- into every rank's copy; the outer loops call it after each training epoch, before the
+        cross-validation pass and the checkpoint.  Returns the number of floats exchanged."""
+        if not getattr(self, "engine_batch_norm", False) or rdist.world_size(self.process_group) <= 1:
+            return 0
+        ranges = [(off, int(np.prod(shape))) for name, shape, off in self.engine.tensor_table(NET_G)
+                  if "/BatchNorm/" in name and name.rsplit("/", 1)[1] in self.BN_STATE]
+        if not ranges:
+            return 0
+        flat = self.engine.get_params(NET_G, "variables")
+        packed = torch.cat([flat[o:o + c] for o, c in ranges])
+        rdist.all_reduce_mean_(packed, self.process_group)
+        at = 0
+        for o, c in ranges:
+            flat[o:o + c] = packed[at:at + c]
+            at += c
+        self.engine.set_params(NET_G, flat, "variables")
+        return at
 
     def _summary_fetch(self, inputs, labels, lengths):
         """the 3 + 4 losses and G(x) of THIS rank's rows, without the *_opt ops and without any collective"""

@@ -119,6 +119,8 @@ def train(FLAGS, model_factory=None, log=print, net_overrides=None):
         start = datetime.datetime.now()
         # reader thread + Queue(32) as :463-478: reading, CMVN, splicing and padding overlap the GPU steps
         tr = train_one_iteration(None, tr_model, train_batch_per_iter * FLAGS.num_gpu, iteration + 1, prefetch(tr_reader), FLAGS.num_gpu)
+        if hasattr(tr_model, "sync_batch_norm_state"):
+            tr_model.sync_batch_norm_state()           # one copy of the batch-norm statistics over the ranks, before cross-validation and the checkpoint
         cv = eval_one_iteration(None, cv_model, valdi_batch_per_iter * FLAGS.num_gpu, iteration + 1,
                                 prefetch(b for b in cv_reader if len(b[0]) == full), FLAGS.num_gpu)
         end = datetime.datetime.now()
