@@ -439,6 +439,26 @@ int rsrgan_op_bn_commit(int32_t n, float* const* vars, const float* const* stat,
  * after calls 1 .. n-1; backward: call n-1) */
 int rsrgan_op_bn_last_plan(int32_t out[16]);
 
+/* ---- the feature front end of the sequence recipes on the device (csrc/feat.hip): global CMVN (io_funcs/make_tfrecords.py:84-87),
+ * Kaldi-style splicing (io_funcs/tfrecords_io.py:177-203), zero padding to T (io_funcs/tfrecords_dataset.py:139-175).  One launch; no
+ * handle.  raw [raw_rows][D]: the utterances' raw frames, packed; offsets [B + 1]: utterance b is rows offsets[b] .. offsets[b + 1] - 1,
+ * n_b = offsets[b + 1] - offsets[b].  With Dout = D * (left + 1 + right):
+ *   out[b, t, c * D + d] = norm(raw[offsets[b] + clamp(t + c - left, 0, n_b - 1), d])   for t < min(n_b, T), c = 0 .. left + right
+ *   out[b, t, :]         = 0                                                            for t >= min(n_b, T), every t when n_b <= 0
+ *   lengths[b]           = min(max(n_b, 0), T)
+ *   norm(v)              = mean ? (float)(((double)v - mean[d]) / stddev[d]) : v
+ * Columns: left contexts far to near, the centre, right contexts near to far (io.features.splice_feats).  The context is clamped at the
+ * utterance's own first and last frame, not at T: truncation never invents a repeated frame.  The arithmetic is IEEE double
+ * subtraction and division and one rounding to float, which is what the host path computes (io.features.apply_cmvn): the results are
+ * equal bit for bit.  Source rows are additionally clamped into [0, raw_rows): the kernel is memory-safe whatever the device-resident
+ * offset table holds.  All pointers are DEVICE pointers; mean and stddev ([D] double) are both given or both NULL; lengths may be NULL.
+ * RSRGAN_ERR_INVALID before the first HIP call, rsrgan_last_error() naming the argument, for: a null raw, offsets or out; only one of
+ * mean / stddev; raw or out not 16-byte aligned; offsets or lengths not 4-byte, mean or stddev not 8-byte aligned; B, T, D or raw_rows
+ * below 1; left or right negative.  Limits, refused alike: left or right above 1024; B * T * D * (left + 1 + right) above 2^32 - 1
+ * elements (a 16 GiB batch: the kernel divides flat indices in 32 bits); raw_rows * D above 2^40. */
+int rsrgan_feat_batch(const float* raw, int64_t raw_rows, const int32_t* offsets, int32_t B, int32_t T, int32_t D, int32_t left,
+                      int32_t right, const double* mean, const double* stddev, float* out, int32_t* lengths, void* stream);
+
 /* ---- the SEGAN operators (csrc/segan.hip and the window-GEMM primitives of csrc/segan.cpp).  Unit parity tests only
  * (tests/test_gpu_segan_ops.py, tests/test_op_args.py); no trainer calls them.  Each goes through the host function SeganModel calls
  * and never launches a kernel directly.  One entry per family: op selects the launcher; ptrs is a HOST table of device pointers,

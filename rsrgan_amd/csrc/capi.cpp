@@ -917,6 +917,29 @@ int rsrgan_op_bn_last_plan(int32_t out[16]) {
   return RSRGAN_OK;
 }
 
+// ---- the feature front end (feat.hip): no handle, one launch on the caller's stream
+int rsrgan_feat_batch(const float* raw, int64_t raw_rows, const int32_t* offsets, int32_t B, int32_t T, int32_t D, int32_t left, int32_t right,
+                      const double* mean, const double* stddev, float* out, int32_t* lengths, void* stream) {
+  OP_REFUSE(!raw || !offsets || !out, "feat_batch: null pointer (raw, offsets or out)");
+  OP_REFUSE((mean == nullptr) != (stddev == nullptr), "feat_batch: mean and stddev must both be given or both be null");
+  OP_REFUSE(((size_t)raw & 15) || ((size_t)out & 15), "feat_batch: raw or out not 16-byte aligned");
+  OP_REFUSE(((size_t)offsets & 3) || ((size_t)lengths & 3), "feat_batch: offsets or lengths not 4-byte aligned");
+  OP_REFUSE(((size_t)mean & 7) || ((size_t)stddev & 7), "feat_batch: mean or stddev not 8-byte aligned");
+  OP_REFUSE(B < 1 || T < 1 || D < 1 || raw_rows < 1, "feat_batch: B, T, D, raw_rows must be positive (got %d, %d, %d, %lld)", B, T, D,
+            (long long)raw_rows);
+  OP_REFUSE(left < 0 || right < 0, "feat_batch: negative context (left %d, right %d)", left, right);
+  OP_REFUSE(left > 1024 || right > 1024, "feat_batch: context above the entry's 1024 (left %d, right %d)", left, right);
+  const unsigned long long lim = 0xFFFFFFFFull;            // flat indices are divided in 32 bits (feat.hip)
+  unsigned long long total = (unsigned long long)B * (unsigned long long)T;          // (< 2^62: no overflow before the checks)
+  OP_REFUSE(total > lim || total * (unsigned long long)D > lim || total * (unsigned long long)D * (unsigned long long)(left + 1 + right) > lim,
+            "feat_batch: B x T x D x (left + 1 + right) = %d x %d x %d x %d above the entry's 2^32 - 1 elements", B, T, D, left + 1 + right);
+  OP_REFUSE((unsigned long long)raw_rows > ((1ull << 40) / (unsigned long long)D), "feat_batch: raw_rows x D = %lld x %d above the entry's 2^40",
+            (long long)raw_rows, D);
+  launch_feat_batch(raw, (long long)raw_rows, offsets, B, T, D, left, right, mean, stddev, out, lengths, (hipStream_t)stream);
+  if (hipGetLastError() != hipSuccess) { set_error("feat_batch launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
+
 // ---- the SEGAN operators (segan.hip, and the window-GEMM primitives of segan.cpp) through the host functions SeganModel calls, on
 // caller-owned buffers (tests/test_gpu_segan_ops.py).  One entry per family: op selects the launcher, ptrs is a HOST table of device
 // pointers, dims a host table of sizes, fl of float parameters, each in the order include/rsrgan.h lists.

@@ -452,6 +452,10 @@ void launch_bn_seq_backward(float* dy, int ldd, const float* y, int ldy, const f
                             size_t scratch_floats, hipStream_t s);
 // inference handle: W[k][c] *= a[c] in place, bias[c] = b[c], from the moving statistics
 void launch_bn_seq_fold(float* W, int ldw, int K, int cols, const BnVars& v, float* bias, hipStream_t s);
+// ---- the feature front end (feat.hip): CMVN in double, context splice and zero padding of packed raw utterances in one launch.
+// out [B][T][D * (left + 1 + right)] (16-byte aligned, B * T * Dout < 2^32), lengths [B] or null, mean / stddev [D] double or both null.
+void launch_feat_batch(const float* raw, long long raw_rows, const int* offsets, int B, int T, int D, int left, int right, const double* mean,
+                       const double* stddev, float* out, int* lengths, hipStream_t s);
 void launch_colsum(const float* a, int lda, const float* b, int ldb, float* out, int rows, int cols,
                    float* scratch /* >= 64*cols floats */, hipStream_t s);
 

@@ -214,6 +214,79 @@ class HipEngine:
         t.record_stream(cur)
         return t
 
+    # -- the feature front end on the device (include/rsrgan.h rsrgan_feat_batch, csrc/feat.hip) ---------------------------
+    def op_feat_batch(self, raw, offsets, B, T, D, left, right, mean, stddev, out, lengths=None, raw_rows=None, stream=None):
+        """rsrgan_feat_batch on caller-owned device tensors (raw [rows, D] f32, offsets [B + 1] i32, mean / stddev [D] f64 or None,
+        out B * T * D * (left + 1 + right) f32, lengths [B] i32 or None), on `stream` (default: the current one)"""
+        check(self.lib.rsrgan_feat_batch(_ptr(raw), raw.shape[0] if raw_rows is None else raw_rows, _ptr(offsets), B, T, D, left, right,
+                                         _ptr(mean), _ptr(stddev), _ptr(out), _ptr(lengths),
+                                         self._stream() if stream is None else C.c_void_p(stream.cuda_stream)))
+
+    def _cmvn_device(self, mean, stddev, us):
+        """the two CMVN vectors as fp64 device tensors, uploaded once per pair of host arrays (the cache holds the host arrays, so
+        their ids stay theirs)"""
+        cache = self.__dict__.setdefault("_cmvn_cache", {})
+        ent = cache.get((id(mean), id(stddev)))
+        if ent is None:
+            host = [np.ascontiguousarray(v, np.float64).reshape(-1) for v in (mean, stddev)]
+            with torch.cuda.stream(us):
+                dev = [torch.from_numpy(h).to(self.device) for h in host]
+            if len(cache) > 16:
+                cache.clear()
+            ent = cache[(id(mean), id(stddev))] = (mean, stddev, dev[0], dev[1])
+        return ent[2], ent[3]
+
+    def featurize(self, packed, left=None, right=None, mean=None, stddev=None, ready=False, limit=True):
+        """io.PackedBatch (raw frames + offsets) -> (x [B, T, D * (left + 1 + right)] f32, lengths [B] i32) on the device: CMVN, splice
+        and padding in one kernel (csrc/feat.hip), bit for bit what io.features computes on the host.  left / right / mean / stddev
+        default to what the batch carries.  The packed frames and the offset table travel on the engine's upload stream and the kernel
+        runs there: ready=True waits for THAT stream only and vouches for the results (what upload_ready gives the labels and lengths of
+        a D-run under RSRGAN_DPIPE=1); ready=False hands them over by event, as upload_async does.  ValueError before any device work
+        if an utterance is longer than max_frames (limit=False: the caller cuts the result into chunks itself, as the chunked decode
+        does)."""
+        left = packed.left if left is None else int(left)
+        right = packed.right if right is None else int(right)
+        if mean is None and stddev is None:
+            mean, stddev = packed.mean, packed.stddev
+        if (mean is None) != (stddev is None):
+            raise ValueError("featurize: mean and stddev must both be given or both be None")
+        data, offsets = packed.data, packed.offsets
+        if not isinstance(data, np.ndarray) or data.dtype != np.float32 or data.ndim != 2:
+            raise ValueError("featurize: packed.data must be a float32 [rows, D] array")
+        B, T = int(packed.shape[0]), int(packed.shape[1])
+        D = data.shape[1]
+        offsets = np.ascontiguousarray(offsets, np.int32)
+        if offsets.shape != (B + 1,) or B < 1 or T < 1 or data.shape[0] < 1:
+            raise ValueError("featurize: B = %d, T = %d, %d rows, %d offsets" % (B, T, data.shape[0], offsets.shape[0]))
+        n = np.diff(offsets.astype(np.int64))
+        if n.min() < 0 or offsets[0] < 0 or offsets[-1] > data.shape[0]:
+            raise ValueError("featurize: the offset table does not describe utterances inside the %d packed rows" % data.shape[0])
+        if limit and max(int(n.max()), T) > self.max_frames:
+            raise ValueError("featurize: an utterance of %d frames (T = %d) is longer than max_frames = %d" % (int(n.max()), T, self.max_frames))
+        if mean is not None and (np.size(mean) != D or np.size(stddev) != D):
+            raise ValueError("featurize: mean / stddev must hold D = %d entries, got %d / %d" % (D, np.size(mean), np.size(stddev)))
+        us = getattr(self, "_upload_stream", None)
+        if us is None:
+            us = self._upload_stream = torch.cuda.Stream(self.device)
+        dm, ds = self._cmvn_device(mean, stddev, us) if mean is not None else (None, None)
+        with torch.cuda.stream(us):
+            raw = torch.from_numpy(np.ascontiguousarray(data)).to(self.device, non_blocking=True)
+            off = torch.from_numpy(offsets).to(self.device, non_blocking=True)
+            out = torch.empty(B, T, D * (left + 1 + right), dtype=torch.float32, device=self.device)
+            ln = torch.empty(B, dtype=torch.int32, device=self.device)
+            self.op_feat_batch(raw, off, B, T, D, left, right, dm, ds, out, ln, stream=us)
+            if not ready:
+                ev = torch.cuda.Event()
+                ev.record(us)
+        cur = torch.cuda.current_stream(self.device)
+        if ready:
+            us.synchronize()
+            self._vouch(out); self._vouch(ln)
+        else:
+            cur.wait_event(ev)
+        out.record_stream(cur); ln.record_stream(cur)
+        return out, ln
+
     def _i32(self, a) -> torch.Tensor:
         t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
         return t.to(self.device).to(torch.int32).contiguous()       # placeholder is float32, cast like dynamic_rnn

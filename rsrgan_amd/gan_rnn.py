@@ -306,7 +306,8 @@ class GAN_RNN(Model):
         return torch.randn(self.batch_size, 1, self.output_dim, generator=self._noise_gen, device=dev) * self.disc_noise_std
 
     def _shard(self, a):
-        """per-GPU batch slicing (:157-159): a fed [B*num_gpu, ...] batch -> this rank's rows."""
+        """per-GPU batch slicing (:157-159): a fed [B*num_gpu, ...] batch -> this rank's rows.  An io.PackedBatch (raw frames for
+        the device-side front end) is sliced by utterance (PackedBatch.rows)."""
         if a is None:
             return None
         n = a.shape[0]
@@ -315,6 +316,8 @@ class GAN_RNN(Model):
         ws, r = rdist.world_size(self.process_group), rdist.rank(self.process_group)
         if n != self.batch_size * ws:
             raise ValueError("batch has %d rows, expected %d or %d" % (n, self.batch_size, self.batch_size * ws))
+        if hasattr(a, "rows") and hasattr(a, "offsets"):
+            return a.rows(self.batch_size * r, self.batch_size * (r + 1))
         return a[self.batch_size * r:self.batch_size * (r + 1)]
 
     def on_stream(self):

@@ -35,6 +35,55 @@ def splice_feats(feats, left, right):
     return np.concatenate(parts, 1)
 
 
+class PackedBatch(object):
+    """A batch as the device-side front end takes it (HipEngine.featurize, csrc/feat.hip): the utterances' RAW frames one after the
+    other and where each begins -- no CMVN, no splice, no padding.  `data` float32 [rows, D]; `offsets` int32 [B + 1] (utterance b
+    is data[offsets[b]:offsets[b + 1]]); `shape` = the (B, T, D * (left + 1 + right)) the expanded batch has, so that what reads
+    `.shape[0]` of a fed batch (train_one_iteration's row check, GAN_RNN._shard) works on either kind.  `left`, `right`, `mean`,
+    `stddev` say how the reader that made the batch would have expanded it (mean / stddev: float64 [D], or None for no CMVN)."""
+
+    def __init__(self, data, offsets, shape, left=0, right=0, mean=None, stddev=None):
+        self.data, self.offsets, self.shape = data, offsets, tuple(int(v) for v in shape)
+        self.left, self.right, self.mean, self.stddev = int(left), int(right), mean, stddev
+        if self.offsets.shape[0] != self.shape[0] + 1:
+            raise ValueError("offsets must hold B + 1 = %d entries, got %d" % (self.shape[0] + 1, self.offsets.shape[0]))
+
+    def __len__(self):
+        return self.shape[0]
+
+    def lengths(self):
+        """frames of every utterance after truncation at T (int32 [B]): what the kernel writes as `lengths`"""
+        return np.minimum(np.diff(self.offsets), self.shape[1]).astype(np.int32)
+
+    def rows(self, lo, hi):
+        """utterances [lo, hi) as a batch of their own -- this rank's shard of a fed batch (GAN_RNN._shard): only their frames, offsets
+        rebased to 0, the same T"""
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo <= hi <= self.shape[0]:
+            raise ValueError("rows [%d, %d) outside the batch of %d" % (lo, hi, self.shape[0]))
+        a, b = int(self.offsets[lo]), int(self.offsets[hi])
+        return PackedBatch(self.data[a:b], (self.offsets[lo:hi + 1] - self.offsets[lo]).astype(np.int32), (hi - lo,) + self.shape[1:],
+                           self.left, self.right, self.mean, self.stddev)
+
+
+def pack_utterances(mats, left=0, right=0, mean=None, stddev=None, T=None, names=None):
+    """float32 [n_i, D] matrices -> PackedBatch padded to T (default: the longest).  A matrix that is not float32 raises ValueError
+    naming it: the device entry takes fp32 raw frames only."""
+    for i, m in enumerate(mats):
+        if not isinstance(m, np.ndarray) or m.dtype != np.float32 or m.ndim != 2:
+            raise ValueError("utterance %s: the device-side front end takes float32 [frames, dim] matrices only, got %s %s" % (
+                names[i] if names is not None else i, getattr(m, "dtype", type(m).__name__), getattr(m, "shape", "")))
+    n = [m.shape[0] for m in mats]
+    offsets = np.zeros(len(mats) + 1, np.int64)
+    np.cumsum(n, out=offsets[1:])
+    if offsets[-1] >= 2 ** 31:
+        raise ValueError("a packed batch of %d frames does not fit the int32 offset table" % offsets[-1])
+    D = mats[0].shape[1]
+    data = np.concatenate(mats, 0)                           # (a private, writable copy also of a single read-only matrix)
+    return PackedBatch(data, offsets.astype(np.int32), (len(mats), max(n) if T is None else int(T), D * (left + 1 + right)), left, right,
+                       mean, stddev)
+
+
 class PaddedBatchReader(object):
     """get_padded_batch (tfrecords_dataset.py:53-180) without TFRecords: reads (inputs, labels)
     utterance pairs from two scp files, applies CMVN and splicing, groups utterances into windows of
@@ -42,10 +91,19 @@ class PaddedBatchReader(object):
     pads each batch with zeros to its longest utterance and yields
     [utt_ids, inputs [B,T,D*(L+1+R)] f32, labels [B,T,Dout] f32, lengths [B] i32] -- the items
     train_one_iteration pops from its queue (train_gan_rnn_placeholder.py:67).  Partial windows are
-    emitted at the end of the data, like tf.contrib.data.group_by_window; the training loop skips them."""
+    emitted at the end of the data, like tf.contrib.data.group_by_window; the training loop skips them.
+
+    device_features=True: CMVN, splicing and padding are left to the device (HipEngine.featurize).  materialize only reads and
+    concatenates the raw utterances and yields [utt_ids, PackedBatch(inputs), PackedBatch(labels), lengths]; plan() is the same, so
+    the same seed draws the same batches in the same order, and the expanded items are bit for bit the default reader's."""
 
     def __init__(self, inputs_scp, labels_scp, batch_size, left_context=0, right_context=0, cmvn=None,
-                 num_buckets=20, shuffle=True, seed=None):
+                 num_buckets=20, shuffle=True, seed=None, device_features=False):
+        self.device_features = bool(device_features)
+        self._stats = None
+        if self.device_features and cmvn is not None:
+            self._stats = tuple(np.ascontiguousarray(cmvn[k], np.float64).reshape(-1)
+                                for k in ("mean_inputs", "stddev_inputs", "mean_labels", "stddev_labels"))
         self.inputs, self.labels = ArkReader(), ArkReader()
         self.inputs(inputs_scp)
         self.labels(labels_scp)
@@ -101,7 +159,21 @@ class PaddedBatchReader(object):
             if windows[key]:
                 yield windows[key]
 
+    def _packed(self, indices):
+        ids = [self.inputs.utt_ids[i] for i in indices]
+        xs = [self.inputs.read_utt_data_from_index(i) for i in indices]
+        ys = [self.labels.read_utt_data_from_index(i) for i in indices]
+        for u, x, y in zip(ids, xs, ys):
+            if x.shape[0] != y.shape[0]:
+                raise ValueError("utterance %s: %d input frames, %d label frames" % (u, x.shape[0], y.shape[0]))
+        mi, si, ml, sl = self._stats if self._stats is not None else (None,) * 4
+        X = pack_utterances(xs, self.left, self.right, mi, si, names=ids)
+        Y = pack_utterances(ys, 0, 0, ml, sl, names=ids)
+        return [ids, X, Y, X.lengths()]
+
     def materialize(self, indices: List[int]) -> List:
+        if self.device_features:
+            return self._packed(indices)
         return self._pad([self._utt(i) for i in indices])
 
     def __iter__(self) -> Iterator[List]:

@@ -21,7 +21,7 @@ import numpy as np
 
 from . import dist as rdist
 from .gan_rnn import GAN_RNN
-from .io import ArkReader, ArkWriter, PaddedBatchReader, prefetch, splice_feats
+from .io import ArkReader, ArkWriter, PaddedBatchReader, pack_utterances, prefetch, splice_feats
 from .train import eval_one_iteration, exponential_decay, train_one_iteration
 
 
@@ -65,6 +65,9 @@ def build_parser():
                    "batch row")
     p.add_argument("--decode_lean", default=False, action="store_true", help="decode on an inference-only model (inference_only=True: "
                    "the generator alone, no BPTT stash)")
+    p.add_argument("--device_features", type=str2bool, nargs="?", const=True, default=False, help="CMVN, context splice and padding on the "
+                   "device (csrc/feat.hip): the reader ships packed raw frames and an offset table instead of the expanded batch; "
+                   "training, cross-validation and --decode; the same numbers bit for bit")
     return p
 
 
@@ -79,7 +82,7 @@ def _cmvn(FLAGS):
 
 def _reader(FLAGS, inputs_scp, labels_scp, cmvn, shuffle, seed):
     return PaddedBatchReader(inputs_scp, labels_scp, FLAGS.batch_size * FLAGS.num_gpu, FLAGS.left_context, FLAGS.right_context,
-                             cmvn=cmvn, shuffle=shuffle, seed=seed)
+                             cmvn=cmvn, shuffle=shuffle, seed=seed, device_features=bool(getattr(FLAGS, "device_features", False)))
 
 
 def get_num_batch(reader, full):
@@ -193,6 +196,21 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
             x = (x - cmvn["mean_inputs"]) / cmvn["stddev_inputs"]
         return splice_feats(x, FLAGS.left_context, FLAGS.right_context).astype(np.float32)
 
+    host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    if getattr(FLAGS, "device_features", False):
+        # --device_features: the raw utterance travels, CMVN and the splice run on the device (HipEngine.featurize) and the generator reads
+        # the device tensor; the same bits as features() above.  De-normalising the output_dim-wide result stays on the host.
+        featurize = getattr(getattr(model, "engine", None), "featurize", None)
+        if featurize is None:
+            raise SystemExit("--device_features needs an engine with a device-side front end (HipEngine.featurize)")
+        stats = (None, None) if cmvn is None else tuple(np.ascontiguousarray(cmvn[k], np.float64).reshape(-1)
+                                                        for k in ("mean_inputs", "stddev_inputs"))
+
+        def features(i):                                                     # noqa: F811 -- [n, D * (L + 1 + R)] on the device
+            packed = pack_utterances([reader.read_utt_data_from_index(i)], FLAGS.left_context, FLAGS.right_context, *stats,
+                                     names=[reader.utt_ids[i]])
+            return featurize(packed, limit=chunk <= 0)[0][0]                 # (chunked decode cuts the utterance itself)
+
     if chunk > 0:
         from .stream import decode_streams
         outs = decode_streams(model, (features(i) for i in range(len(reader.utt_ids))), chunk, streams)
@@ -206,7 +224,7 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
         return write_scp_path
     for i, utt in enumerate(reader.utt_ids):
         x = features(i)[None]
-        activations = np.asarray(model.forward(x, np.array([x.shape[1]], np.int32)))
+        activations = host(model.forward(x, np.array([x.shape[1]], np.int32)))
         sequence = activations * cmvn["stddev_labels"] + cmvn["mean_labels"] if cmvn is not None else activations
         writer.write_next_utt(write_ark_path, utt, np.vstack(sequence))
         log("[{}/{}] Write inferred {} to {}".format(i + 1, len(reader.utt_ids), utt, write_ark_path))

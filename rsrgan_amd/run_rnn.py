@@ -22,7 +22,7 @@ from . import dist as rdist
 from . import run_gan_rnn as gan_loop
 from .io import prefetch
 from .run_gan_rnn import _cmvn, _reader, get_num_batch, str2bool
-from .train import _batches, _check_device, _on_stream, exponential_decay
+from .train import _batches, _check_device, _on_stream, device_batch, exponential_decay
 from .trainer import RNNTrainer
 
 
@@ -54,6 +54,8 @@ def build_parser():
     p.add_argument("--decode_streams", type=int, default=1, help="decode with --decode_chunk: utterances decoded side by side")
     p.add_argument("--decode_lean", default=False, action="store_true", help="decode on an inference-only model (inference_only=True: "
                    "the generator alone, no BPTT stash; --g_type bnlstm with --decode_chunk always decodes on it)")
+    p.add_argument("--device_features", type=str2bool, nargs="?", const=True, default=False, help="CMVN, context splice and padding on the "
+                   "device (run_gan_rnn --device_features)")
     return p
 
 
@@ -71,7 +73,8 @@ def _run_batches(model, num_batch, iteration, queue, num_gpu, train):
             break
         if x.shape[0] != full:
             continue
-        tw = model.g_step(x, lab, ln, train=train, sync=False, gather=False).mean(0)      # this tower's (adv = 0, mse, l2, total)
+        x, lab, ln = device_batch(model, x, lab, ln, d_run=False)      # (--device_features: packed raw frames, expanded on the device)
+        tw =model.g_step(x, lab, ln, train=train, sync=False, gather=False).mean(0)      # this tower's (adv = 0, mse, l2, total)
         acc = tw if acc is None else acc + tw
         n += 1
         last = (x, lab, ln)

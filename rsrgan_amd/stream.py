@@ -20,6 +20,11 @@ def _model_dims(model):
     return batch, (int(cap) if cap else None)
 
 
+def _on_device(a):
+    """a torch tensor (an utterance the device-side front end produced) rather than a host array"""
+    return hasattr(a, "new_zeros") and hasattr(a, "detach")
+
+
 class StreamEnhancer(object):
     """One live stream on batch row 0 of `model`.
 
@@ -142,7 +147,8 @@ def decode_streams(model, utterances: Iterable[np.ndarray], chunk: int, streams:
                 except StopIteration:
                     exhausted = True
                     break
-                x = np.asarray(x, np.float32)
+                if not _on_device(x):        # (a device tensor -- run_gan_rnn --device_features -- stays where it is)
+                    x = np.asarray(x, np.float32)
                 if x.ndim != 2:
                     raise ValueError("utterance %d must be [T, D], got %s" % (i, x.shape))
                 if x.shape[0] == 0:
@@ -154,13 +160,15 @@ def decode_streams(model, utterances: Iterable[np.ndarray], chunk: int, streams:
         if busy:
             take = {r: min(chunk, rows[r][1].shape[0] - rows[r][2]) for r in busy}
             T = max(take.values())
-            xb = np.zeros((batch, T, rows[busy[0]][1].shape[1]), np.float32)
+            x0 = rows[busy[0]][1]
+            xb = x0.new_zeros((batch, T, x0.shape[1])) if _on_device(x0) else np.zeros((batch, T, x0.shape[1]), np.float32)
             ln = np.zeros(batch, np.int32)
             for r in busy:
                 _, x, pos, _ = rows[r]
                 xb[r, :take[r]] = x[pos:pos + take[r]]
                 ln[r] = take[r]
-            y = np.asarray(model.forward_stream(xb, ln, reset=fresh or None))
+            y = model.forward_stream(xb, ln, reset=fresh or None)
+            y = y.detach().cpu().numpy() if _on_device(y) else np.asarray(y)
             for r in busy:
                 rows[r][3].append(np.array(y[r, :take[r]]))
                 rows[r][2] += take[r]

@@ -39,6 +39,31 @@ def _on_stream(model):
     return f() if f is not None else contextlib.nullcontext()
 
 
+def _dpipe():
+    return os.environ.get("RSRGAN_DPIPE", "0") not in ("", "0")
+
+
+def is_packed(a):
+    """an io.PackedBatch: raw frames and offsets, to be normalised, spliced and padded on the device"""
+    return hasattr(a, "offsets") and hasattr(a, "rows") and hasattr(a, "data")
+
+
+def device_batch(model, inputs, labels, lengths, d_run=True):
+    """A queue item -> what d_step / g_step take.  Packed items (PaddedBatchReader(device_features=True)) are sharded by utterance and
+    expanded by the engine's device-side front end in place of the uploads: the labels and the lengths COMPLETE on return when a
+    pipelined D-run will read them (d_run and RSRGAN_DPIPE=1: what upload_ready gives), everything else in stream order.  Other items
+    pass through.  There is no host fallback: an engine without featurize cannot take packed items."""
+    if not is_packed(inputs):
+        return inputs, labels, lengths
+    f = getattr(model.engine, "featurize", None)
+    if f is None:
+        raise RuntimeError("packed batches (device_features) need an engine with a device-side front end (HipEngine.featurize)")
+    xp, yp = model._shard(inputs), model._shard(labels)
+    lab, ln = f(yp, ready=d_run and _dpipe())
+    x, _ = f(xp)
+    return x, lab, ln
+
+
 def _check_device(model, d, g):
     """A persistent recurrence launch whose bounded wait expired poisons its losses with NaN (csrc/dpersist.hip): say so instead of
     handing non-finite numbers to the accept / reject logic of the outer loop."""
@@ -81,7 +106,10 @@ def _train_one_iteration(sess, model, tr_num_batch, iteration, train_queue, num_
             break
         if queue_inputs.shape[0] != model.batch_size * num_gpu:   # :69-70
             continue
-        x = model._shard(queue_inputs); lab = model._shard(queue_labels); ln = model._shard(queue_lengths)
+        if is_packed(queue_inputs):           # raw frames: CMVN, splice and padding on the device, in place of the uploads below
+            x, lab, ln = device_batch(model, queue_inputs, queue_labels, queue_lengths)
+        else:
+            x = model._shard(queue_inputs); lab = model._shard(queue_labels); ln = model._shard(queue_lengths)
         ready = getattr(model.engine, "upload_ready", None) if os.environ.get("RSRGAN_DPIPE", "0") not in ("", "0") else None
         later = getattr(model.engine, "upload_async", None)
         if ready is not None and not (isinstance(lab, torch.Tensor) and lab.device == dev):
@@ -146,6 +174,7 @@ def _eval_one_iteration(sess, model, cv_num_batch, iteration, valid_queue, num_g
             _, x, lab, ln = next(it)
         except StopIteration:
             break
+        x, lab, ln = device_batch(model, x, lab, ln)
         td = model.d_step(x, lab, ln, train=False, sync=False).mean(0)
         tg = model.g_step(x, lab, ln, train=False, sync=False).mean(0)
         d_acc = td if d_acc is None else d_acc + td
