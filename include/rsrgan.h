@@ -458,6 +458,21 @@ int rsrgan_op_bn_last_plan(int32_t out[16]);
  * elements (a 16 GiB batch: the kernel divides flat indices in 32 bits); raw_rows * D above 2^40. */
 int rsrgan_feat_batch(const float* raw, int64_t raw_rows, const int32_t* offsets, int32_t B, int32_t T, int32_t D, int32_t left,
                       int32_t right, const double* mean, const double* stddev, float* out, int32_t* lengths, void* stream);
+/* The frame-level recipes' form (io_funcs/tfrecords_io.py:206-255: batches of single spliced frames drawn from a shuffle queue): the
+ * queue's utterances stay resident in pool [pool_rows][D] and one launch gathers the N drawn frames.  picks [N][3] = (row, lo, hi): the
+ * pool row of the frame and the pool row range [lo, hi) of the utterance it belongs to.  With Dout = D * (left + 1 + right):
+ *   out[i, c * D + d] = norm(pool[clamp(clamp(row + c - left, lo, hi - 1), 0, pool_rows - 1), d])   if hi > lo
+ *   out[i, :]         = +0.0                                                                        if hi <= lo
+ *   norm(v)           = mean ? (float)(((double)v - mean[d]) / stddev[d]) : v
+ * Columns as above; the context is clamped at the utterance's own first and last frame; the outer clamp makes the kernel memory-safe
+ * whatever the device-resident table holds.  The same row may appear in any number of picks, in any order.  mean = stddev = NULL reads
+ * a pool that already holds normalised frames (what HipEngine.featurize_frames keeps); with statistics the arithmetic is that of
+ * rsrgan_feat_batch.  All pointers are DEVICE pointers.  RSRGAN_ERR_INVALID before the first HIP call, rsrgan_last_error() naming the
+ * argument, for: a null pool, picks or out; only one of mean / stddev; pool or out not 16-byte aligned; picks not 4-byte, mean or
+ * stddev not 8-byte aligned; N, D or pool_rows below 1; left or right negative or above 1024; N * D * (left + 1 + right) above
+ * 2^32 - 1 elements; pool_rows * D above 2^40. */
+int rsrgan_feat_frames(const float* pool, int64_t pool_rows, const int32_t* picks, int32_t N, int32_t D, int32_t left, int32_t right,
+                       const double* mean, const double* stddev, float* out, void* stream);
 
 /* ---- the SEGAN operators (csrc/segan.hip and the window-GEMM primitives of csrc/segan.cpp).  Unit parity tests only
  * (tests/test_gpu_segan_ops.py, tests/test_op_args.py); no trainer calls them.  Each goes through the host function SeganModel calls

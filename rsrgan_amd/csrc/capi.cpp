@@ -940,6 +940,27 @@ int rsrgan_feat_batch(const float* raw, int64_t raw_rows, const int32_t* offsets
   return RSRGAN_OK;
 }
 
+int rsrgan_feat_frames(const float* pool, int64_t pool_rows, const int32_t* picks, int32_t N, int32_t D, int32_t left, int32_t right,
+                       const double* mean, const double* stddev, float* out, void* stream) {
+  OP_REFUSE(!pool || !picks || !out, "feat_frames: null pointer (pool, picks or out)");
+  OP_REFUSE((mean == nullptr) != (stddev == nullptr), "feat_frames: mean and stddev must both be given or both be null");
+  OP_REFUSE(((size_t)pool & 15) || ((size_t)out & 15), "feat_frames: pool or out not 16-byte aligned");
+  OP_REFUSE((size_t)picks & 3, "feat_frames: picks not 4-byte aligned");
+  OP_REFUSE(((size_t)mean & 7) || ((size_t)stddev & 7), "feat_frames: mean or stddev not 8-byte aligned");
+  OP_REFUSE(N < 1 || D < 1 || pool_rows < 1, "feat_frames: N, D, pool_rows must be positive (got %d, %d, %lld)", N, D, (long long)pool_rows);
+  OP_REFUSE(left < 0 || right < 0, "feat_frames: negative context (left %d, right %d)", left, right);
+  OP_REFUSE(left > 1024 || right > 1024, "feat_frames: context above the entry's 1024 (left %d, right %d)", left, right);
+  const unsigned long long lim = 0xFFFFFFFFull;            // flat indices are divided in 32 bits (feat.hip)
+  const unsigned long long nd = (unsigned long long)N * (unsigned long long)D;       // (< 2^62: no overflow before the checks)
+  OP_REFUSE(nd > lim || nd * (unsigned long long)(left + 1 + right) > lim,
+            "feat_frames: N x D x (left + 1 + right) = %d x %d x %d above the entry's 2^32 - 1 elements", N, D, left + 1 + right);
+  OP_REFUSE((unsigned long long)pool_rows > ((1ull << 40) / (unsigned long long)D), "feat_frames: pool_rows x D = %lld x %d above the entry's 2^40",
+            (long long)pool_rows, D);
+  launch_feat_frames(pool, (long long)pool_rows, picks, N, D, left, right, mean, stddev, out, (hipStream_t)stream);
+  if (hipGetLastError() != hipSuccess) { set_error("feat_frames launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
+
 // ---- the SEGAN operators (segan.hip, and the window-GEMM primitives of segan.cpp) through the host functions SeganModel calls, on
 // caller-owned buffers (tests/test_gpu_segan_ops.py).  One entry per family: op selects the launcher, ptrs is a HOST table of device
 // pointers, dims a host table of sizes, fl of float parameters, each in the order include/rsrgan.h lists.

@@ -111,4 +111,89 @@ void launch_feat_batch(const float* raw, long long raw_rows, const int* offsets,
                        stddev, out, lengths, total);
 }
 
+// ---- the frame-level recipes' front end: gather spliced frames from a device-resident pool of utterances.  picks [N][3] = (row, lo, hi): pool
+// row of the drawn frame and the pool row range [lo, hi) of its utterance.  With C = left + 1 + right, Dout = D * C:
+//   out[i, c * D + d] = norm(pool[clamp(clamp(row + c - left, lo, hi - 1), 0, pool_rows - 1), d])     hi > lo
+//   out[i, :]         = +0.0                                                                          hi <= lo
+// The same layout as k_feat_batch: `out` is one flat 16-byte aligned array of N * Dout floats, a lane owns four consecutive elements and
+// issues one 16-byte store, the last (N * Dout) % 4 elements are stored one by one, grid-stride, at most 2048 workgroups of 256.  The pick
+// triple is read where a quad starts and where it crosses into the next pick; the source row is worked out once per (i, c).  The outer clamp
+// is memory safety: whatever the table holds, no lane reads outside pool.  No atomics, no LDS, no scratch memory.
+struct FramePos { uint32_t i, c, d; };
+
+__device__ __forceinline__ FramePos frame_pos(uint32_t e, uint32_t D, uint32_t Dout) {
+  FramePos p;
+  p.i = e / Dout;
+  const uint32_t col = e - p.i * Dout;
+  p.c = col / D; p.d = col - p.c * D;
+  return p;
+}
+
+struct FramePick { int row, lo, hi; };
+
+__device__ __forceinline__ FramePick frame_pick(const int* __restrict__ picks, uint32_t i) {
+  const int* t = picks + (size_t)i * 3;
+  FramePick k;
+  k.row = t[0]; k.lo = t[1]; k.hi = t[2];
+  return k;
+}
+
+// the source row of (pick, c): a pointer to its D floats, or null where the output row is zero (hi <= lo)
+__device__ __forceinline__ const float* frame_row(const float* __restrict__ pool, long long pool_rows, const FramePick& k, uint32_t c, int left,
+                                                  uint32_t D) {
+  if (k.hi <= k.lo) return nullptr;
+  const long long j = min(max((long long)k.row + (long long)c - left, (long long)k.lo), (long long)k.hi - 1);      // the utterance's own first and last frame
+  const long long row = min(max(j, 0ll), pool_rows - 1);              // memory safety, whatever picks holds
+  return pool + (size_t)row * D;
+}
+
+template <bool NORM>
+__global__ __launch_bounds__(256) void k_feat_frames(const float* __restrict__ pool, long long pool_rows, const int* __restrict__ picks, uint32_t D,
+                                                     int left, uint32_t C, const double* __restrict__ mean, const double* __restrict__ stddev,
+                                                     float* __restrict__ out, unsigned long long total) {
+  const uint32_t Dout = D * C;
+  const unsigned long long gid = (unsigned long long)blockIdx.x * 256 + threadIdx.x, stride = (unsigned long long)gridDim.x * 256;
+  const unsigned long long quads = total >> 2;
+  for (unsigned long long q = gid; q < quads; q += stride) {
+    FramePos p = frame_pos((uint32_t)(q << 2), D, Dout);              // (total < 2^32)
+    FramePick k = frame_pick(picks, p.i);
+    const float* src = frame_row(pool, pool_rows, k, p.c, left, D);
+    float v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      v[i] = feat_value<NORM>(src, p.d, mean, stddev);
+      if (i == 3) break;
+      if (++p.d == D) {
+        p.d = 0;
+        if (++p.c == C) {                                             // (a quad never runs past the last pick: 4 q + 3 < total)
+          p.c = 0; ++p.i;
+          k = frame_pick(picks, p.i);
+        }
+        src = frame_row(pool, pool_rows, k, p.c, left, D);
+      }
+    }
+    *reinterpret_cast<float4*>(out + (q << 2)) = make_float4(v[0], v[1], v[2], v[3]);
+  }
+  const uint32_t tail = (uint32_t)(total & 3);
+  if (gid < tail) {
+    const unsigned long long e = (quads << 2) + gid;
+    const FramePos p = frame_pos((uint32_t)e, D, Dout);
+    out[e] = feat_value<NORM>(frame_row(pool, pool_rows, frame_pick(picks, p.i), p.c, left, D), p.d, mean, stddev);
+  }
+}
+
+void launch_feat_frames(const float* pool, long long pool_rows, const int* picks, int N, int D, int left, int right, const double* mean,
+                        const double* stddev, float* out, hipStream_t s) {
+  const int C = left + 1 + right;
+  const unsigned long long total = (unsigned long long)N * D * C;
+  // (one workgroup at least: the tail is written by the first lanes of the grid)
+  const int grid = (int)std::min<unsigned long long>(2048, std::max<unsigned long long>(1, ((total >> 2) + 255) / 256));
+  if (mean)
+    hipLaunchKernelGGL(k_feat_frames<true>, dim3(grid), dim3(256), 0, s, pool, pool_rows, picks, (uint32_t)D, left, (uint32_t)C, mean, stddev, out,
+                       total);
+  else
+    hipLaunchKernelGGL(k_feat_frames<false>, dim3(grid), dim3(256), 0, s, pool, pool_rows, picks, (uint32_t)D, left, (uint32_t)C, mean, stddev, out,
+                       total);
+}
+
 }  // namespace rsr

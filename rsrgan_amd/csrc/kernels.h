@@ -456,6 +456,11 @@ void launch_bn_seq_fold(float* W, int ldw, int K, int cols, const BnVars& v, flo
 // out [B][T][D * (left + 1 + right)] (16-byte aligned, B * T * Dout < 2^32), lengths [B] or null, mean / stddev [D] double or both null.
 void launch_feat_batch(const float* raw, long long raw_rows, const int* offsets, int B, int T, int D, int left, int right, const double* mean,
                        const double* stddev, float* out, int* lengths, hipStream_t s);
+// the frame-level recipes' form: N spliced frames gathered from a device-resident pool [pool_rows][D] by picks [N][3] = (row, lo, hi), the
+// context clamped into the utterance's rows [lo, hi); a pick with hi <= lo gives a zero row.  out [N][D * (left + 1 + right)] (16-byte
+// aligned, N * Dout < 2^32), mean / stddev [D] double or both null (the pool already normalised).
+void launch_feat_frames(const float* pool, long long pool_rows, const int* picks, int N, int D, int left, int right, const double* mean,
+                        const double* stddev, float* out, hipStream_t s);
 void launch_colsum(const float* a, int lda, const float* b, int ldb, float* out, int rows, int cols,
                    float* scratch /* >= 64*cols floats */, hipStream_t s);
 

@@ -287,6 +287,95 @@ class HipEngine:
         out.record_stream(cur); ln.record_stream(cur)
         return out, ln
 
+    # -- the frame-level recipes' front end (include/rsrgan.h rsrgan_feat_frames, csrc/feat.hip k_feat_frames) ------------------
+    def op_feat_frames(self, pool, picks, N, D, left, right, mean, stddev, out, pool_rows=None, stream=None):
+        """rsrgan_feat_frames on caller-owned device tensors (pool [rows, D] f32, picks [N, 3] i32 = (row, lo, hi), mean / stddev [D] f64 or
+        None, out N * D * (left + 1 + right) f32), on `stream` (default: the current one)"""
+        check(self.lib.rsrgan_feat_frames(_ptr(pool), pool.shape[0] if pool_rows is None else pool_rows, _ptr(picks), N, D, left, right,
+                                          _ptr(mean), _ptr(stddev), _ptr(out),
+                                          self._stream() if stream is None else C.c_void_p(stream.cuda_stream)))
+
+    def featurize_frames(self, item, ready=False):
+        """io.FrameDraw (FrameBatchReader(device_features=True)) -> (x [N, D * (left + 1 + right)] f32, labels [N, Dl] f32) on the device, bit
+        for bit the default reader's batch.  The engine keeps one pool per reader: inputs [pool_rows, D] and labels [pool_rows, Dl], holding
+        the queue's utterances NORMALISED (float64 arithmetic, one rounding: rsrgan_feat_batch with B = 1, context 0 / 0, writing straight
+        into the slot).  Per item: grow the pools if the reader's allocator did (old rows keep their numbers), normalise the new utterances
+        once, then gather the drawn frames with two rsrgan_feat_frames launches (inputs with the recipe's context, labels with none; mean =
+        NULL).  Gathering rows commutes with the elementwise cast to float32, which is why normalise -> cast -> gather gives the bits of the
+        host's normalise -> splice -> cast.  ready as in featurize.  ValueError before any device work for an item that is not the next one
+        of its reader."""
+        from .io.frame_pool import PoolLedger
+        pools = self.__dict__.setdefault("_frame_pools", {})
+        st = pools.get(item.reader_id)
+        if st is None:
+            st = pools[item.reader_id] = {"ledger": PoolLedger(item.reader_id), "x": None, "y": None, "items": 0, "uploads": 0, "growths": 0}
+        st["ledger"].admit(item)                                   # (raises before anything is queued)
+        N, D, Dl, left, right = item.picks.shape[0], item.input_dim, item.label_dim, item.left, item.right
+        us = getattr(self, "_upload_stream", None)
+        if us is None:
+            us = self._upload_stream = torch.cuda.Stream(self.device)
+        mi = si = ml = sl = None
+        if item.stats is not None:
+            if any(np.size(v) != d for v, d in zip(item.stats, (D, D, Dl, Dl))):
+                raise ValueError("featurize_frames: the statistics must hold %d / %d entries" % (D, Dl))
+            mi, si = self._cmvn_device(item.stats[0], item.stats[1], us)
+            ml, sl = self._cmvn_device(item.stats[2], item.stats[3], us)
+        # EVERYTHING below is queued on the upload stream, item after item: pool growth, uploads, normalisation and the gathers.  Slot reuse
+        # rests on that order alone: the reader hands a slot out again once its utterance's last frame was drawn, so an upload into a freed
+        # slot belongs to a LATER item than the last gather that read the slot, and runs behind it on this stream.  The same order keeps a
+        # grown pool's copy of the old rows behind every write to them and in front of every later read.
+        with torch.cuda.stream(us):
+            if st["x"] is None or item.pool_rows > st["x"].shape[0]:
+                nx = torch.empty(item.pool_rows, D, dtype=torch.float32, device=self.device)
+                ny = torch.empty(item.pool_rows, Dl, dtype=torch.float32, device=self.device)
+                if st["x"] is not None:
+                    old = st["x"].shape[0]
+                    nx[:old].copy_(st["x"]); ny[:old].copy_(st["y"])
+                    st["growths"] += 1
+                st["x"], st["y"] = nx, ny
+            px, py = st["x"], st["y"]
+            for first, rx, ry in item.uploads:
+                n = rx.shape[0]
+                if mi is None:
+                    px[first:first + n].copy_(torch.from_numpy(rx), non_blocking=True)
+                    py[first:first + n].copy_(torch.from_numpy(ry), non_blocking=True)
+                    continue
+                off = torch.tensor([0, n], dtype=torch.int32).to(self.device, non_blocking=True)
+                sx = torch.from_numpy(rx).to(self.device, non_blocking=True)
+                sy = torch.from_numpy(ry).to(self.device, non_blocking=True)
+                # (a slot starts on a multiple of 4 rows: its address is 16-byte aligned at any D, as the entry asks of `out`)
+                self.op_feat_batch(sx, off, 1, n, D, 0, 0, mi, si, px[first:first + n], None, stream=us)
+                self.op_feat_batch(sy, off, 1, n, Dl, 0, 0, ml, sl, py[first:first + n], None, stream=us)
+            picks = torch.from_numpy(item.picks).to(self.device, non_blocking=True)
+            x = torch.empty(N, D * (left + 1 + right), dtype=torch.float32, device=self.device)
+            lab = torch.empty(N, Dl, dtype=torch.float32, device=self.device)
+            self.op_feat_frames(px, picks, N, D, left, right, None, None, x, stream=us)
+            self.op_feat_frames(py, picks, N, Dl, 0, 0, None, None, lab, stream=us)
+            if not ready:
+                ev = torch.cuda.Event()
+                ev.record(us)
+        st["items"] += 1; st["uploads"] += len(item.uploads)
+        cur = torch.cuda.current_stream(self.device)
+        if ready:
+            us.synchronize()
+            self._vouch(x); self._vouch(lab)
+        else:
+            cur.wait_event(ev)
+        x.record_stream(cur); lab.record_stream(cur)
+        return x, lab
+
+    def frame_pool_stats(self, reader_id):
+        """{'pool_rows', 'bytes', 'items', 'uploads', 'growths'} of one reader's pool (None before its first item)"""
+        st = self.__dict__.get("_frame_pools", {}).get(reader_id)
+        if st is None or st["x"] is None:
+            return None
+        return {"pool_rows": st["x"].shape[0], "bytes": (st["x"].numel() + st["y"].numel()) * 4, "items": st["items"], "uploads": st["uploads"],
+                "growths": st["growths"]}
+
+    def drop_frame_pool(self, reader_id):
+        """forget a reader's pool (its device memory goes back to torch once the last batch gathered from it is consumed)"""
+        self.__dict__.get("_frame_pools", {}).pop(reader_id, None)
+
     def _i32(self, a) -> torch.Tensor:
         t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
         return t.to(self.device).to(torch.int32).contiguous()       # placeholder is float32, cast like dynamic_rnn

@@ -3,4 +3,5 @@ ark/scp reader and writer, global CMVN, Kaldi-style splicing, length-bucketed pa
 from .kaldi_ark import ArkReader, ArkWriter, read_binary_file, convert_cmvn_to_numpy     # noqa: F401
 from .features import apply_cmvn, splice_feats, PaddedBatchReader, FrameBatchReader                          # noqa: F401
 from .features import PackedBatch, pack_utterances                                         # noqa: F401
+from .frame_pool import FrameDraw, PoolLedger, RowAllocator                                 # noqa: F401
 from .prefetch import prefetch                                                             # noqa: F401

@@ -187,10 +187,18 @@ class FrameBatchReader(object):
     min_after_dequeue = 1000); `dequeue_many(batch_size)` draws that many frames uniformly at random from the queue.  Yields
     [inputs [N, D*(L+1+R)] f32, labels [N, Dout] f32].  Utterances are visited in shuffled order once per pass
     (string_input_producer(shuffle=True, num_epochs)); the frames left over at the end of the data that do not fill a batch are
-    dropped, as dequeue_many does when the queue closes."""
+    dropped, as dequeue_many does when the queue closes.
+
+    device_features=True: the queue is bookkeeping only.  The utterances live in a pool of rows on the device (HipEngine.featurize_frames
+    normalises each ONCE into the slot the reader's RowAllocator gave it) and every batch is an io.frame_pool.FrameDraw: the raw utterances
+    enqueued since the previous batch and a table of the drawn frames (pool row, the utterance's row range) from which one kernel gathers the
+    spliced batch.  Enqueuing follows the rules of __iter__ and drawing makes the same calls on self.rng, so the same seed draws the same
+    frames in the same order as the default reader, and the expanded batches are its batches bit for bit.  `initial_pool_rows`: the
+    pool's first capacity (default: the queue's capacity; it doubles when an utterance does not fit)."""
 
     def __init__(self, inputs_scp, labels_scp, batch_size, left_context=0, right_context=0, cmvn=None, num_threads=4,
-                 shuffle=True, seed=None):
+                 shuffle=True, seed=None, device_features=False, initial_pool_rows=None):
+        self.device_features = bool(device_features)
         self.inputs, self.labels = ArkReader(), ArkReader()
         self.inputs(inputs_scp)
         self.labels(labels_scp)
@@ -199,6 +207,14 @@ class FrameBatchReader(object):
         self.capacity = 1000 + (num_threads + 1) * batch_size
         self.min_after_dequeue = 1000 if shuffle else 0
         self.rng = np.random.default_rng(seed)
+        if self.device_features:
+            from . import frame_pool
+            self.reader_id, self._serial = frame_pool.new_reader_id(), 0
+            self.allocator = frame_pool.RowAllocator(self.capacity if initial_pool_rows is None else initial_pool_rows)
+            self._stats = None
+            if cmvn is not None:
+                self._stats = tuple(np.ascontiguousarray(cmvn[k], np.float64).reshape(-1)
+                                    for k in ("mean_inputs", "stddev_inputs", "mean_labels", "stddev_labels"))
 
     def num_frames(self):
         return sum(self.inputs.utt_shape_from_index(i)[0] for i in range(len(self.inputs.utt_ids)))
@@ -214,7 +230,74 @@ class FrameBatchReader(object):
             x, y = apply_cmvn(x, y, self.cmvn)
         return splice_feats(x, self.left, self.right).astype(np.float32), y.astype(np.float32)
 
+    def _raw(self, i):
+        x, y = self.inputs.read_utt_data_from_index(i), self.labels.read_utt_data_from_index(i)
+        for m, what in ((x, "inputs"), (y, "labels")):
+            if not isinstance(m, np.ndarray) or m.dtype != np.float32 or m.ndim != 2:
+                raise ValueError("utterance %s: the device-side front end takes float32 [frames, dim] matrices only, got %s %s %s" % (
+                    self.inputs.utt_ids[i], what, getattr(m, "dtype", type(m).__name__), getattr(m, "shape", "")))
+        if x.shape[0] != y.shape[0]:
+            raise ValueError("utterance %s: %d input frames, %d label frames" % (self.inputs.utt_ids[i], x.shape[0], y.shape[0]))
+        return np.array(x, order="C"), np.array(y, order="C")          # (private, writable copies: the ark reader's views are read-only)
+
+    def _iter_draws(self):
+        """__iter__ with the queue as a table: one row (pool row, lo, hi, slot) per held frame, in the order the default reader's
+        concatenated queue holds them.  A new pass drops what the previous one left in the queue, slots included."""
+        from .frame_pool import FrameDraw
+        order = np.arange(len(self.inputs.utt_ids))
+        if self.shuffle:
+            self.rng.shuffle(order)
+        alloc = self.allocator
+        alloc.free_all()
+        table, held = np.zeros((0, 4), np.int32), 0
+        left_in = {}                               # slot -> frames of it still in the queue
+        uploads, dims = [], None
+        todo = list(order)
+        N = self.batch_size
+
+        def draw():
+            nonlocal table, held, uploads
+            pick = self.rng.choice(held, N, replace=False) if self.shuffle else np.arange(N)
+            keep = np.ones(held, bool); keep[pick] = False
+            drawn = table[pick]
+            table, held = table[keep], held - N
+            slots, counts = np.unique(drawn[:, 3], return_counts=True)
+            for s, c in zip(slots.tolist(), counts.tolist()):
+                left_in[s] -= c
+                if left_in[s] == 0:                # the utterance's last held frame was drawn: its rows may be handed out again.  The
+                    del left_in[s]                 # consumer writes them no sooner than a LATER item's uploads, behind this item's gather
+                    alloc.free(s)
+            item = FrameDraw(self._serial, self.reader_id, uploads, alloc.pool_rows, np.ascontiguousarray(drawn[:, :3]), self.left, self.right,
+                             self._stats, dims[0], dims[1])
+            self._serial += 1
+            uploads = []
+            return item
+        while todo or held >= N:
+            while todo and (held < N or held + self.inputs.utt_shape_from_index(int(todo[0]))[0] <= self.capacity):
+                x, y = self._raw(int(todo.pop(0)))
+                n = x.shape[0]
+                dims = (x.shape[1], y.shape[1])
+                if n == 0:
+                    continue
+                first = alloc.alloc(n)
+                if alloc.pool_rows >= 2 ** 31:
+                    raise ValueError("a frame pool of %d rows does not fit the int32 pick table" % alloc.pool_rows)
+                block = np.empty((n, 4), np.int32)
+                block[:, 0] = np.arange(first, first + n); block[:, 1] = first; block[:, 2] = first + n; block[:, 3] = first
+                table = np.concatenate([table, block]); held += n
+                left_in[first] = n
+                uploads.append((first, x, y))
+            if held >= N and (held - N >= self.min_after_dequeue or not todo):
+                yield draw()
+            elif not todo:
+                break
+            elif held >= N:
+                yield draw()
+
     def __iter__(self):
+        if self.device_features:
+            yield from self._iter_draws()
+            return
         order = np.arange(len(self.inputs.utt_ids))
         if self.shuffle:
             self.rng.shuffle(order)

@@ -24,8 +24,9 @@ import numpy as np
 
 from . import dist as rdist
 from .gan import GAN
-from .io import ArkReader, ArkWriter, FrameBatchReader, splice_feats
+from .io import ArkReader, ArkWriter, FrameBatchReader, pack_utterances, splice_feats
 from .run_gan_rnn import _cmvn, str2bool
+from .train import device_frames
 
 LOSS_NAMES = ("d_rl_loss", "d_fk_loss", "d_loss", "g_adv_loss", "g_mse_loss", "g_l2_loss", "g_loss")
 
@@ -62,12 +63,16 @@ def build_parser():
     p.add_argument("--num_gpu", type=int, default=1)
     p.add_argument("--apply_cmvn", type=str2bool, nargs="?", default="true", help="normalise with data_dir/train_cmvn.npz "
                    "(make_tfrecords.py:84-87 did this when writing TFRecords)")
+    p.add_argument("--device_features", type=str2bool, nargs="?", const=True, default=False, help="CMVN and context splice on the device: "
+                   "the shuffle queue's utterances stay resident there, normalised once, and one HIP kernel gathers every batch "
+                   "(HipEngine.featurize_frames); same batches as the host path, bit for bit")
     return p
 
 
 def _reader(FLAGS, inputs_scp, labels_scp, cmvn, shuffle, seed):
     return FrameBatchReader(inputs_scp, labels_scp, FLAGS.batch_size, FLAGS.left_context, FLAGS.right_context, cmvn=cmvn,
-                            num_threads=FLAGS.num_threads, shuffle=shuffle, seed=seed)
+                            num_threads=FLAGS.num_threads, shuffle=shuffle, seed=seed,
+                            device_features=bool(getattr(FLAGS, "device_features", False)))
 
 
 def _one_epoch(model, batches, num_batch, epoch, FLAGS, train, log, report=True):
@@ -144,15 +149,15 @@ def train(FLAGS, model_factory=None, log=print, net_overrides=None):
                 fw.write("%d %d" % (cv_num_batch, tr_num_batch))
     tr_model.g_learning_rate = FLAGS.g_learning_rate
     tr_model.d_learning_rate = FLAGS.d_learning_rate
-    cv = eval_one_epoch(cv_model, cv_reader, cv_num_batch, 0, FLAGS, log)
+    cv = eval_one_epoch(cv_model, device_frames(cv_model, cv_reader), cv_num_batch, 0, FLAGS, log)
     log("CROSSVAL.LOSS PRERUN: " + _fmt(cv))
     g_loss_prev, decay_steps, history = cv[6], 1, []
     for epoch in range(FLAGS.max_epoches):
         start = datetime.datetime.now()
-        tr = train_one_epoch(tr_model, tr_reader, tr_num_batch, epoch + 1, FLAGS, log)
+        tr = train_one_epoch(tr_model, device_frames(tr_model, tr_reader), tr_num_batch, epoch + 1, FLAGS, log)
         if hasattr(tr_model, "sync_batch_norm_state"):
             tr_model.sync_batch_norm_state()           # one copy of the batch-norm statistics over the ranks, like the towers' shared variables
-        cv = eval_one_epoch(cv_model, cv_reader, cv_num_batch, epoch + 1, FLAGS, log)
+        cv = eval_one_epoch(cv_model, device_frames(cv_model, cv_reader), cv_num_batch, epoch + 1, FLAGS, log)
         end = datetime.datetime.now()
         log("Epoch {} (TRAIN AVG.LOSS): {}, d_lr = {:.3e}, g_lr = {:.3e}\nEpoch {} (CROSS AVG.LOSS): {}, time = {:.2f} h".format(
             epoch + 1, _fmt(tr), tr_model.d_learning_rate, tr_model.g_learning_rate, epoch + 1, _fmt(cv), (end - start).seconds / 3600.0))
@@ -209,14 +214,30 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None, moving_aver
     if os.path.exists(write_ark_path):
         os.remove(write_ark_path)
     writer = ArkWriter(write_scp_path)
+    featurize = None
+    if getattr(FLAGS, "device_features", False):
+        # --device_features: the raw utterance travels; CMVN, the splice and the zero rows up to `longest` come from rsrgan_feat_batch
+        # (B = 1, T = longest), the same bits as the host lines below.  De-normalising the output_dim-wide result stays on the host.
+        featurize = getattr(getattr(model, "engine", None), "featurize", None)
+        if featurize is None:
+            raise SystemExit("--device_features needs an engine with a device-side front end (HipEngine.featurize)")
+        stats = (None, None) if cmvn is None else tuple(np.ascontiguousarray(cmvn[k], np.float64).reshape(-1)
+                                                        for k in ("mean_inputs", "stddev_inputs"))
     for i, utt in enumerate(reader.utt_ids):
-        x = reader.read_utt_data_from_index(i).astype(np.float64)
-        if cmvn is not None:
-            x = (x - cmvn["mean_inputs"]) / cmvn["stddev_inputs"]
-        x = splice_feats(x, FLAGS.left_context, FLAGS.right_context).astype(np.float32)
-        n = x.shape[0]
-        pad = np.concatenate([x, np.zeros((longest - n, x.shape[1]), np.float32)]) if n < longest else x
-        activations = np.asarray(model.forward(pad))[:n]
+        if featurize is not None:
+            raw = reader.read_utt_data_from_index(i)
+            n = raw.shape[0]
+            packed = pack_utterances([raw], FLAGS.left_context, FLAGS.right_context, *stats, T=longest, names=[utt])
+            pad = featurize(packed, limit=False)[0][0]                # [longest, D * (L + 1 + R)] on the device (the engine's T is 1: frames are rows)
+        else:
+            x = reader.read_utt_data_from_index(i).astype(np.float64)
+            if cmvn is not None:
+                x = (x - cmvn["mean_inputs"]) / cmvn["stddev_inputs"]
+            x = splice_feats(x, FLAGS.left_context, FLAGS.right_context).astype(np.float32)
+            n = x.shape[0]
+            pad = np.concatenate([x, np.zeros((longest - n, x.shape[1]), np.float32)]) if n < longest else x
+        y = model.forward(pad)
+        activations = (y.cpu().numpy() if hasattr(y, "cpu") else np.asarray(y))[:n]
         sequence = activations * cmvn["stddev_labels"] + cmvn["mean_labels"] if cmvn is not None else activations
         writer.write_next_utt(write_ark_path, utt, np.vstack(sequence))
         log("Write inferred %s to %s" % (utt, write_ark_path))

@@ -24,7 +24,7 @@ import numpy as np
 from . import dist as rdist
 from .gan import GAN
 from .run_gan_dnn import LOSS_NAMES, _cmvn, _fmt, _one_epoch, _reader, build_parser as _epoch_parser, decode
-from .train import exponential_decay
+from .train import device_frames, exponential_decay
 
 CHECK_INTERVAL = 3            # train_gan_dnn_iter.py:411
 
@@ -106,7 +106,9 @@ def train(FLAGS, model_factory=None, log=print, net_overrides=None, batch_counts
         "LOG: #min_epoches = {}, #max_epoches = {}\nLOG: #min_iters = {}, #max_iters = {}, #itres_per_epoch = {:.2f}\n".format(
             tr_num_batch, cv_num_batch, train_batch_per_iter, valid_batch_per_iter, FLAGS.min_epoches, FLAGS.max_epoches, min_iters,
             max_iters, max_iters / FLAGS.max_epoches))
-    tr_batches, cv_batches = _stream(tr_reader, FLAGS.max_epoches), _stream(cv_reader, None)
+    # (--device_features: the readers yield frame draws, gathered on the device; host batches pass through.  Two readers, two pools)
+    tr_batches = device_frames(tr_model, _stream(tr_reader, FLAGS.max_epoches))
+    cv_batches = device_frames(cv_model, _stream(cv_reader, None))
     # Early stop counter (:407-411)
     g_loss_prev, g_rel_impr, windows_g_loss, history = 10000.0, 1.0, [], []
     tr_model.g_learning_rate = FLAGS.num_gpu * FLAGS.g_learning_rate

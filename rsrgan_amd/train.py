@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import dist as rdist
+from .io.frame_pool import is_frame_draw
 
 
 def exponential_decay(iteration, num_jobs, num_ietrs, init_learning_rate, multiply_jobs=True):
@@ -62,6 +63,32 @@ def device_batch(model, inputs, labels, lengths, d_run=True):
     lab, ln = f(yp, ready=d_run and _dpipe())
     x, _ = f(xp)
     return x, lab, ln
+
+
+def device_frames(model, reader):
+    """The frame-level twin of device_batch: FrameBatchReader(device_features=True) items -> (x [N, 1, Dout], labels [N, 1, Dl]) device
+    tensors, the frames as GAN.d_step / g_step hand them to the engine (T = 1), gathered by the engine's device-side front end.  Host
+    batches pass through unchanged.  The outer loop runs disc_updates D-runs then gen_updates G-runs on a fresh batch each: the batches
+    that will feed a pipelined D-run (RSRGAN_DPIPE=1) are COMPLETE when they are yielded and vouched for, so that d_backward's upload_ready
+    lets them pass without a device wait; a wrong guess costs that wait and nothing else.  There is no host fallback: an engine without
+    featurize_frames cannot take these items."""
+    cycle = max(int(getattr(model, "disc_updates", 1)) + int(getattr(model, "gen_updates", 1)), 1)
+    d_runs = int(getattr(model, "disc_updates", 1))
+    k = 0
+    for item in reader:
+        if not is_frame_draw(item):
+            yield item
+            continue
+        f = getattr(getattr(model, "engine", None), "featurize_frames", None)
+        if f is None:
+            raise RuntimeError("frame draws (device_features) need an engine with a device-side front end (HipEngine.featurize_frames)")
+        ready = k % cycle < d_runs and _dpipe()
+        k += 1
+        x, lab = f(item, ready=ready)
+        x, lab = x[:, None, :], lab[:, None, :]
+        if ready:
+            model.engine._vouch(lab)              # (the view d_backward will see: upload_ready knows tensor objects, not storages)
+        yield x, lab
 
 
 def _check_device(model, d, g):
