@@ -76,7 +76,7 @@ void Model::bnl_params() {
 // An inference handle's layers (RSRGAN_FLAG_INFER): one LstmLayer view per BNLSTMCell for the persistent forward -- input and
 // recurrent width P, the cell's own bias / peephole / projection tensors, no stacked kernel (tK = -1: input_kernel and state_kernel stay two
 // tensors; KxT / KhT receive their folded, transposed copies from bnl_refresh_fold)
-int Model::bnl_infer_layers() {
+void Model::bnl_infer_layers() {
   for (const BnlCell& C : bnl) {
     LstmLayer L;
     L.has_proj = true;
@@ -84,7 +84,6 @@ int Model::bnl_infer_layers() {
     L.tK = -1; L.tb = C.tb; L.twf = C.twf; L.twi = C.twi; L.two = C.two; L.tWp = C.tWp;
     gl.push_back(L);
   }
-  return RSRGAN_OK;
 }
 
 void Model::bnl_refresh_fold(hipStream_t s) {
@@ -99,7 +98,8 @@ void Model::bnl_refresh_fold(hipStream_t s) {
   }
 }
 
-int Model::bnl_alloc() {
+// (all required: alloc_generator tests the handle's allocation status behind this)
+void Model::bnl_alloc() {
   const size_t TB = (size_t)Tmax * B, TB1 = (size_t)(Tmax + 1) * B;
   const int H = cfg.g_cells, H4 = 4 * H, ldP = pad4(cfg.g_proj), ldH = pad4(H);
   g_h0 = alloc<float>(TB * ldP);
@@ -111,13 +111,7 @@ int Model::bnl_alloc() {
     C.out = alloc<float>(TB * ldP); C.dmn = alloc<float>(TB * ldP);
     C.mu = alloc<float>((size_t)Tmax * 9 * H); C.var = alloc<float>((size_t)Tmax * 9 * H);
     C.dcc = alloc<float>((size_t)B * ldH); C.dmc = alloc<float>((size_t)B * ldP);
-    if (!C.zx || !C.xh_in || !C.yin || !C.xh_s || !C.act || !C.dz || !C.cnew || !C.chat || !C.h || !C.dyc || !C.ccar || !C.mst ||
-        !C.out || !C.dmn || !C.mu || !C.var || !C.dcc || !C.dmc || !g_h0) {
-      set_error("hipMalloc failed (bnlstm buffers)");
-      return RSRGAN_ERR_HIP;
-    }
   }
-  return RSRGAN_OK;
 }
 
 // initial values (bnlstm.py:47-52,103-123, BNLSTMCell.py:20-47,176-215): input FC truncated_normal(0, sqrt(2 / num_proj)) redrawn

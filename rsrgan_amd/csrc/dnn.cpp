@@ -7,15 +7,6 @@
 
 namespace rsr {
 
-#define HIPC(expr)                                                                   \
-  do {                                                                               \
-    hipError_t e_ = (expr);                                                          \
-    if (e_ != hipSuccess) {                                                          \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return RSRGAN_ERR_HIP;                                                         \
-    }                                                                                \
-  } while (0)
-
 static const float kDClipLo = -0.5f, kDClipHi = 1.5f;     // discriminator_dnn.py:93 tf.clip_by_value(y, -0.5, 1.5)
 
 BnVars Model::bn_vars(const ParamSet& ps, const int (&tbn)[8]) const {

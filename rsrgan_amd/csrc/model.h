@@ -268,7 +268,7 @@ struct Model {
   bool g_bnl() const { return cfg.g_type == RSRGAN_G_BNLSTM; }
   int bnl_check(const rsrgan_cfg& c) const;                                // the configurations it is built for
   void bnl_params();                                                       // the variable table (reference creation order)
-  int bnl_alloc();
+  void bnl_alloc();
   void bnl_init(std::vector<float>& host, uint64_t seed) const;            // initial values of G
   BnlLayer bnl_args(int l, bool train) const;
   void bnl_forward(int T, bool train, hipStream_t s);
@@ -277,7 +277,7 @@ struct Model {
   // RSRGAN_FLAG_INFER with g_type bnlstm: gl holds one folded LstmLayer view per BNLSTMCell, the forward is
   // infer_forward's persistent branch with GPersistArgs::cnorm, and nothing of bnl_alloc exists
   bool bnl_infer() const { return g_bnl() && infer(); }
-  int bnl_infer_layers();                                                  // gl + the folded copies' buffers
+  void bnl_infer_layers();                                                 // gl: one folded view per cell (their buffers: alloc_params)
   void bnl_refresh_fold(hipStream_t s);                                    // with every refresh of the generator's forward copies
   // R-CED generator (dnn.cpp): rc_act[l] = input of conv layer l as [M][ldCin] positions x channels, rc_act[L] = its output
   std::vector<ConvLayer> gconv;
@@ -363,7 +363,36 @@ struct Model {
   std::vector<void*> allocs;
   size_t alloc_bytes = 0;          // bytes behind allocs (rsrgan_device_bytes)
 
+  // ---- handle construction (model_init.cpp, DESIGN.md "handle construction"): init runs the stages in this order and returns the
+  // first non-zero status.  check_cfg, build_tables and plan_rows are host-only: no HIP call.
   int init(const rsrgan_cfg& c, uint64_t seed);
+  int check_cfg() const;           // every refusal that depends on cfg and switches() alone, before the first ParamSet::add
+  void build_tables();             // G / D variable tables in graph-construction order
+  void plan_rows();                // B: the batch padded to the persistent generator launches' row groups
+  int alloc_params();              // variables, gradients, moments, shadows; chunk tables; per-layer weight copies
+  int alloc_generator();           // inputs / outputs, stashes, carried state, the g_type's activations, g_dA..C
+  void alloc_rced();               // ... the R-CED generator's part of it
+  int alloc_discriminator();       // xd, logits, the FC stack's buffers, d_st, the folded views, d_dA / d_dB
+  int alloc_shared();              // streams, events, device scalars, scratch, GEMM work spaces
+  int plan_persistent();           // residency probes, rings and control blocks of the persistent launches; trail_fits, lazy_sw, DPIPE
+  int plan_dpersist();
+  int plan_gpersist();
+  int init_values(uint64_t seed);  // initial variables, scalars, weight copies, gradient buckets
+  // values several stages share, all functions of cfg / B / Tmax
+  size_t frame_rows() const { return (size_t)Tmax * B; }
+  int g_ldP() const { return g_dnn() ? 4 : pad4(gR); }
+  int d_ldP() const { return d_dnn() ? 4 : pad4(dR); }
+  bool res_sums() const { return cfg.g_type == RSRGAN_G_RES_LSTM_L || cfg.g_type == RSRGAN_G_RES_LSTM_I; }   // (the output FC reads g_res, not the top layer's out)
+  bool ema_on() const { return cfg.ema_decay > 0.f && !infer(); }
+  // Device memory.  alloc: a REQUIRED buffer -- nullptr on failure, and the failure is recorded (sticky; the bytes of the first failing
+  // request); each allocating stage tests it with alloc_status(label) and refuses the handle with RSRGAN_ERR_HIP.  alloc_opt: a buffer
+  // whose absence its caller handles by switching a path off or shrinking a size -- nullptr, nothing recorded.
+  template <typename T> T* alloc(size_t n);
+  template <typename T> T* alloc_opt(size_t n);
+  void* alloc_raw(size_t bytes, bool required);
+  int alloc_status(const char* stage) const;
+  bool alloc_fail = false;
+  size_t alloc_fail_bytes = 0;
   void destroy();
 
   // steps
@@ -486,11 +515,19 @@ struct Model {
   hipStream_t enter(hipStream_t caller);
   void leave(hipStream_t caller, hipStream_t work);
   const float* stage_noise(const float* src, float* buf, hipStream_t s);
-
-  template <typename T> T* alloc(size_t n);
 };
 
 void set_error(const char* fmt, ...);
 const char* get_error();
+
+// a HIP runtime call inside a function that returns a status code
+#define HIPC(expr)                                                                   \
+  do {                                                                               \
+    hipError_t e_ = (expr);                                                          \
+    if (e_ != hipSuccess) {                                                          \
+      rsr::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+      return RSRGAN_ERR_HIP;                                                         \
+    }                                                                                \
+  } while (0)
 
 }  // namespace rsr
