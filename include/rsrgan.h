@@ -534,6 +534,46 @@ int rsrgan_op_segan_elem(int32_t op, const void* const* ptrs, const int64_t* dim
  * op 1 launch_dhead_bwd: ptrs dlogit, h, conv_out, W, wfc, dW?, dwfc?, dbfc? (all three or none), dh */
 int rsrgan_op_segan_dhead(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream);
 
+/* ---- the step's small kernels (csrc/kernels.hip: the LSGAN and MSE terms, discriminator_lstm's fused head, L2, the per-tensor
+ * clip_by_norm, SGD / Adam / EMA, frame-level dropout, lrelu').  Unit parity tests only (tests/test_gpu_update_ops.py,
+ * tests/test_gpu_loss_ops.py, tests/test_update_op_args.py); no trainer calls them.  Each goes through the launch_* function the
+ * model calls and never launches a kernel directly.  ptrs / dims / fl as in the SEGAN entries above ("?" = may be NULL).  A null
+ * table or required pointer, a misaligned pointer (16 bytes for the flat buffers w, g, m, v, ema, ws and for the head's top / dout;
+ * 4 bytes elsewhere), a size below 1, a leading dimension below its row (or no multiple of 4 where a kernel moves float4: ldt, ldo),
+ * a tensor offset or length that is no multiple of 4, dR % 4 != 0 or dR > 60, Bp > 0 with Bt outside 1 .. Bp or a row count that Bp
+ * does not divide, or a scratch below the launcher's need returns RSRGAN_ERR_INVALID before the first HIP call, rsrgan_last_error()
+ * naming it.
+ *
+ * Device scalars `dyn` [16 floats], by slot: 0 g_lr, 1 d_lr, 2 lambda, 3 d_real, 4 d_fake, 5 l2_scale, 6 clip, 7 beta1, 8 beta2,
+ * 9 eps, 10 ema_decay, 11 Adam's lr_t of G, 12 of D.
+ *
+ * rsrgan_op_chunks (no device): the chunk table the model builds for its flat parameter buffer, from tensors [n_tensors][3] =
+ * (float offset, floats, l2 flag), 1 .. 4096 of them: *n_chunks, and, where out is not NULL (out_ints >= 3 * n_chunks + 3 *
+ * n_tensors), out = tensor[n_chunks], off[n_chunks], len[n_chunks], t_first[n_tensors], t_count[n_tensors], t_l2[n_tensors]. */
+int rsrgan_op_chunks(const int64_t* tensors, int32_t n_tensors, int32_t* out, int64_t out_ints, int32_t* n_chunks);
+/* the chunked kernels; the entry builds the table of rsrgan_op_chunks, uploads it for the call and synchronises the stream.
+ * Every op: dims n_tensors, buf_floats (of each flat buffer), partial_floats (>= n_chunks), three op-specific values (0 where none),
+ * then the n_tensors triples.  partial [n_chunks] is an output of ops 0 - 2 and the input of ops 3 - 4.
+ * op 0 launch_sumsq:      ptrs g, partial
+ * op 1 launch_dw_reduce:  ptrs ws, g, partial;  dims .., stride, ntiles (1 .. 64), ws_floats, triples, then src[n_tensors]: the tensor's
+ *                         float offset inside a record (a multiple of 4, the tensor inside the stride) or -1
+ * op 2 launch_l2:         ptrs w, g, l2_scale, partial
+ * op 3 launch_apply_sgd:  ptrs w, g, ema?, partial, dyn
+ * op 4 launch_apply_adam: ptrs w, g, m, v, ema?, partial, dyn;  dims .., lrt_slot (11 or 12) */
+int rsrgan_op_update(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream);
+/* the losses and the element-wise kernels.
+ * op 0 launch_lsgan:       ptrs logits, dlogits?, t_real, t_fake, loss3;  dims T, Nd, n_real, ldl, clip_on, Bp, Bt;  fl clip_lo, clip_hi
+ * op 1 launch_dhead:       ptrs top, w, b, logits, dlogits?, dout?, gw?, gb?, t_real, t_fake, loss3, part;  dims T, Nd, n_real, dR, ldt,
+ *                          ldw, ldl, ldo, want_grads (dlogits, dout), want_wgrads (gw, gb), Bp, Bt, part_floats (>= ceil(T Nd / 64) x 67)
+ * op 2 launch_mse:         ptrs y, lab, dy?, lambda, loss, scratch;  dims rows, D, ld, accumulate, Bp, Bt, scratch_floats (>= 1024)
+ * op 3 launch_g_total:     ptrs l4, lambda  (dims may be NULL)
+ * op 4 launch_l2_total:    ptrs partial, l2_scale, out;  dims n
+ * op 5 launch_adam_tick:   ptrs dyn, t (int32);  dims lr_slot, lrt_slot ((0, 11) or (1, 12));  fl beta1, beta2
+ * op 6 launch_dropout_fwd: ptrs y;  dims rows, cols, ld, key (the 64 bits of the unsigned key), thr (0 .. 2^24);  fl keep
+ * op 7 launch_dropout_bwd: ptrs y, d;  dims rows, cols, ld;  fl keep
+ * op 8 launch_lrelu_bwd:   ptrs h, d;  dims rows, cols, ld;  fl alpha */
+int rsrgan_op_step_elem(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream);
+
 /* ---- SEGAN-style conv G/D (models/segan.py:SEGAN with generator.py:AEGenerator, discriminator.py:discriminator, utils/bnorm.py:VBN;
  * BASELINE.json configs[4]).  The reference's trainer cannot run as shipped (segan.py:136 calls an undefined variables_on_gpu0(),
  * scripts/train_segan.py:20 imports a missing module); the graph it would build is fully specified and is what these entry

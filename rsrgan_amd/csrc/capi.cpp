@@ -1307,4 +1307,211 @@ int rsrgan_op_segan_dhead(int32_t op, const void* const* ptrs, const int64_t* di
 }
 #undef WHO
 
+// ---- unit-test entries of the step's small kernels (kernels.hip: losses, the discriminator's fused head, L2, clip_by_norm, the updates,
+// dropout, lrelu') on caller-owned buffers (tests/test_gpu_update_ops.py, test_gpu_loss_ops.py, test_update_op_args.py).  Same form as
+// the SEGAN entries: op selects the launcher the model calls, ptrs / dims / fl are HOST tables in the order include/rsrgan.h lists.
+#define UP_BP(rows_name, rows, Bp, Bt) do { \
+    OP_REFUSE((Bp) < 0 || (Bp) > (1 << 20), WHO ": Bp = %lld outside 0 .. 2^20", (long long)(Bp)); \
+    if ((Bp) > 0) { \
+      OP_REFUSE((Bt) < 1 || (Bt) > (Bp), WHO ": Bt = %lld outside 1 .. Bp = %lld", (long long)(Bt), (long long)(Bp)); \
+      OP_REFUSE((rows) % (Bp), WHO ": %s = %lld is not divisible by Bp = %lld", rows_name, (long long)(rows), (long long)(Bp)); \
+    } } while (0)
+static const int64_t g_up_max_tensors = 4096;
+
+// tensors [n][3] = (float offset, floats, l2 flag): every error named; 0 = fine.  buf_floats < 0: no buffer to fit
+static int up_tensors_ok(const char* who, const int64_t* tensors, int64_t n, int64_t buf_floats) {
+  OP_REFUSE(!tensors, "%s: null pointer (tensors)", who);
+  OP_REFUSE(n < 1 || n > g_up_max_tensors, "%s: n_tensors = %lld outside 1 .. %lld", who, (long long)n, (long long)g_up_max_tensors);
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t off = tensors[3 * i], fl = tensors[3 * i + 1], l2 = tensors[3 * i + 2];
+    OP_REFUSE(off < 0 || (off & 3), "%s: offset %lld of tensor %lld is negative or not a multiple of 4", who, (long long)off, (long long)i);
+    OP_REFUSE(fl < 1 || (fl & 3), "%s: length %lld of tensor %lld is below 1 or not a multiple of 4", who, (long long)fl, (long long)i);
+    OP_REFUSE(off > ((int64_t)1 << 30) || fl > ((int64_t)1 << 30), "%s: tensor %lld reaches beyond 2^30 floats", who, (long long)i);
+    OP_REFUSE(l2 < 0 || l2 > 1, "%s: l2 flag %lld of tensor %lld is neither 0 nor 1", who, (long long)l2, (long long)i);
+    OP_REFUSE(buf_floats >= 0 && off + fl > buf_floats, "%s: tensor %lld ends at %lld, beyond the buffer's %lld floats", who, (long long)i,
+              (long long)(off + fl), (long long)buf_floats);
+  }
+  return RSRGAN_OK;
+}
+static void up_table(const int64_t* tensors, int n, ChunkTableHost& h) {
+  std::vector<int64_t> off(n), fl(n);
+  std::vector<int> l2(n);
+  for (int i = 0; i < n; ++i) { off[i] = tensors[3 * i]; fl[i] = tensors[3 * i + 1]; l2[i] = (int)tensors[3 * i + 2]; }
+  chunk_table_host(off.data(), fl.data(), l2.data(), n, h);
+}
+
+#define WHO "op_chunks"
+int rsrgan_op_chunks(const int64_t* tensors, int32_t n_tensors, int32_t* out, int64_t out_ints, int32_t* n_chunks) {
+  return guard(WHO, [&]() -> int {
+    OP_REFUSE(!n_chunks, WHO ": null pointer (n_chunks)");
+    if (int rc = up_tensors_ok(WHO, tensors, n_tensors, -1)) return rc;
+    ChunkTableHost h;
+    up_table(tensors, n_tensors, h);
+    *n_chunks = (int32_t)h.tensor.size();
+    if (!out) return RSRGAN_OK;
+    const int64_t need = 3 * (int64_t)h.tensor.size() + 3 * (int64_t)n_tensors;
+    OP_REFUSE(out_ints < need, WHO ": out of %lld ints below the table's %lld", (long long)out_ints, (long long)need);
+    for (const std::vector<int>* v : {&h.tensor, &h.off, &h.len, &h.t_first, &h.t_count, &h.t_l2})
+      for (int x : *v) *out++ = x;
+    return RSRGAN_OK;
+  });
+}
+#undef WHO
+
+#define WHO "op_update"
+int rsrgan_op_update(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream) {
+  (void)fl;
+  return guard(WHO, [&]() -> int {
+    SG_TABLES(0);
+    OP_REFUSE(op < 0 || op > 4, WHO ": op = %d outside 0 (sumsq), 1 (dw_reduce), 2 (l2), 3 (apply_sgd), 4 (apply_adam)", op);
+    const int64_t* d = dims;
+    const int64_t nt = d[0], buf_floats = d[1], partial_floats = d[2];
+    SG_DIM("buf_floats", buf_floats, 4);
+    if (int rc = up_tensors_ok(WHO, d + 6, nt, buf_floats)) return rc;
+    ChunkTableHost h;
+    up_table(d + 6, (int)nt, h);
+    const int nc = (int)h.tensor.size();
+    OP_REFUSE(partial_floats < nc, WHO ": partial of %lld floats below the table's %d chunks", (long long)partial_floats, nc);
+    static const char* const names[5][7] = {{"g", "partial"}, {"ws", "g", "partial"}, {"w", "g", "l2_scale", "partial"},
+                                            {"w", "g", "ema", "partial", "dyn"}, {"w", "g", "m", "v", "ema", "partial", "dyn"}};
+    // bytes of alignment, beside the names: 16 for the flat buffers the kernels move as float4, 4 for scalars and partial; negative: may be NULL
+    static const int align[5][7] = {{16, 4}, {16, 16, 4}, {16, 16, 4, 4}, {16, 16, -16, 4, 4}, {16, 16, 16, 16, -16, 4, 4}};
+    static const int np[5] = {2, 3, 4, 5, 7};
+    for (int i = 0; i < np[op]; ++i) {
+      if (align[op][i] < 0) SG_OPT(names[op][i], ptrs[i], -align[op][i]); else SG_PTR(names[op][i], ptrs[i], align[op][i]);
+    }
+    std::vector<long long> src;
+    if (op == 1) {                                       // dims[3..5] stride, ntiles, ws_floats; src [n_tensors] behind the tensors
+      const int64_t stride = d[3], ntiles = d[4], ws_floats = d[5];
+      SG_DIM("stride", stride, 4); SG_MUL4("stride", stride); SG_DIM("ws_floats", ws_floats, 4);
+      OP_REFUSE(ntiles < 1 || ntiles > 64, WHO ": ntiles = %lld outside 1 .. 64", (long long)ntiles);
+      for (int64_t i = 0; i < nt; ++i) {
+        const int64_t so = d[6 + 3 * nt + i], n = d[6 + 3 * i + 1];
+        OP_REFUSE(so < -1 || (so >= 0 && (so & 3)), WHO ": src %lld of tensor %lld is neither -1 nor a non-negative multiple of 4", (long long)so, (long long)i);
+        OP_REFUSE(so >= 0 && so + n > stride, WHO ": tensor %lld at src %lld does not fit a record of stride %lld", (long long)i, (long long)so, (long long)stride);
+        OP_REFUSE(so >= 0 && (ntiles - 1) * stride + so + n > ws_floats, WHO ": ws of %lld floats below tensor %lld's last record", (long long)ws_floats, (long long)i);
+        src.push_back(so);
+      }
+    }
+    if (op == 4) OP_REFUSE(d[3] != DYN_ADAM_LRT && d[3] != DYN_ADAM_LRT_D, WHO ": lrt_slot = %lld is neither %d (G) nor %d (D)", (long long)d[3], (int)DYN_ADAM_LRT, (int)DYN_ADAM_LRT_D);
+    // the table on the device for the length of the call
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> host;
+    for (const std::vector<int>* v : {&h.tensor, &h.off, &h.len, &h.t_first, &h.t_count, &h.t_l2}) host.insert(host.end(), v->begin(), v->end());
+    int* dev = nullptr;
+    long long* dsrc = nullptr;
+    HIPC(hipMalloc((void**)&dev, host.size() * sizeof(int)));
+    struct Free { int*& a; long long*& b; ~Free() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } fr{dev, dsrc};
+    HIPC(hipMemcpy(dev, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (op == 1) {
+      HIPC(hipMalloc((void**)&dsrc, src.size() * sizeof(long long)));
+      HIPC(hipMemcpy(dsrc, src.data(), src.size() * sizeof(long long), hipMemcpyHostToDevice));
+    }
+    ChunkTable ct{};
+    ct.tensor = dev; ct.off = dev + nc; ct.len = dev + 2 * nc;
+    ct.t_first = dev + 3 * nc; ct.t_count = dev + 3 * nc + nt; ct.t_l2 = dev + 3 * nc + 2 * nt;
+    ct.n_chunks = nc; ct.n_tensors = (int)nt;
+    switch (op) {
+      case 0: launch_sumsq(FP(0), ct, FP(1), s); break;
+      case 1: launch_dw_reduce(FP(0), (size_t)d[3], (int)d[4], dsrc, FP(1), ct, FP(2), s); break;
+      case 2: launch_l2(FP(0), FP(1), ct, FP(2), FP(3), s); break;
+      case 3: launch_apply_sgd(FP(0), FP(1), FP(2), ct, FP(3), FP(4), s); break;
+      default: launch_apply_adam(FP(0), FP(1), FP(2), FP(3), FP(4), ct, FP(5), FP(6), s, (int)d[3]); break;
+    }
+    if (hipGetLastError() != hipSuccess) { set_error(WHO " launch failed"); return RSRGAN_ERR_HIP; }
+    HIPC(hipStreamSynchronize(s));                       // (the table is freed on return)
+    return RSRGAN_OK;
+  });
+}
+#undef WHO
+
+#define WHO "op_step_elem"
+int rsrgan_op_step_elem(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream) {
+  OP_REFUSE(!ptrs, WHO ": null table (ptrs)");
+  OP_REFUSE(op < 0 || op > 8, WHO ": op = %d outside 0 .. 8", op);
+  OP_REFUSE(op != 3 && !dims, WHO ": null table (dims)");
+  OP_REFUSE((op == 0 || op >= 5) && !fl, WHO ": null table (fl: the clip bounds, the betas, keep or alpha)");
+  const int64_t* d = dims;
+  hipStream_t s = (hipStream_t)stream;
+  switch (op) {
+    case 0: {                                            // lsgan: ptrs logits, dlogits?, t_real, t_fake, loss3;  dims T, Nd, n_real, ldl, clip_on, Bp, Bt;  fl lo, hi
+      SG_DIM("T", d[0], 1); SG_DIM("Nd", d[1], 1); SG_LD("ldl", d[3], 1); SG_FLAG("clip_on", d[4]);
+      OP_REFUSE(d[2] < 0 || d[2] > d[1], WHO ": n_real = %lld outside 0 .. Nd = %lld", (long long)d[2], (long long)d[1]);
+      OP_REFUSE(d[0] * d[1] > (1 << 24), WHO ": T x Nd above the entry's 2^24");
+      UP_BP("Nd", d[1], d[5], d[6]); UP_BP("n_real", d[2], d[5], d[6]);
+      SG_PTR("logits", ptrs[0], 4); SG_OPT("dlogits", ptrs[1], 4); SG_PTR("t_real", ptrs[2], 4); SG_PTR("t_fake", ptrs[3], 4); SG_PTR("loss3", ptrs[4], 4);
+      launch_lsgan(FP(0), (int)d[3], FP(1), (int)d[0], (int)d[1], (int)d[2], FP(2), FP(3), FP(4), s, d[4] != 0, fl[0], fl[1], (int)d[5], (int)d[6]);
+      break;
+    }
+    case 1: {                                            // dhead: ptrs top, w, b, logits, dlogits?, dout?, gw?, gb?, t_real, t_fake, loss3, part
+      // dims T, Nd, n_real, dR, ldt, ldw, ldl, ldo, want_grads, want_wgrads, Bp, Bt, part_floats
+      SG_DIM("T", d[0], 1); SG_DIM("Nd", d[1], 1); SG_DIM("dR", d[3], 1); SG_MUL4("dR", d[3]);
+      OP_REFUSE(d[3] + 3 > 64, WHO ": dR = %lld above 60 (k_dhead2 sums 3 + dR <= 64 quantities)", (long long)d[3]);
+      OP_REFUSE(d[2] < 0 || d[2] > d[1], WHO ": n_real = %lld outside 0 .. Nd = %lld", (long long)d[2], (long long)d[1]);
+      OP_REFUSE(d[0] * d[1] > (1 << 24), WHO ": T x Nd above the entry's 2^24");
+      SG_FLAG("want_grads", d[8]); SG_FLAG("want_wgrads", d[9]);
+      SG_LD("ldt", d[4], d[3]); SG_MUL4("ldt", d[4]); SG_LD("ldw", d[5], 1); SG_LD("ldl", d[6], 1);
+      if (d[8]) { SG_LD("ldo", d[7], d[3]); SG_MUL4("ldo", d[7]); }
+      UP_BP("Nd", d[1], d[10], d[11]); UP_BP("n_real", d[2], d[10], d[11]);
+      static const char* const names[12] = {"top", "w", "b", "logits", "dlogits", "dout", "gw", "gb", "t_real", "t_fake", "loss3", "part"};
+      for (int i = 0; i < 12; ++i) {
+        const bool wanted = i < 4 || i > 7 || (i < 6 ? d[8] != 0 : d[9] != 0);
+        const int align = (i == 0 || i == 5) ? 16 : 4;
+        if (wanted) SG_PTR(names[i], ptrs[i], align); else SG_OPT(names[i], ptrs[i], align);
+      }
+      const int64_t need = (d[0] * d[1] + 63) / 64 * (DH_MAXR + 3);
+      OP_REFUSE(d[12] < need, WHO ": part of %lld floats below ceil(T x Nd / 64) x %d = %lld", (long long)d[12], DH_MAXR + 3, (long long)need);
+      DHeadArgs a{};
+      a.top = FP(0); a.ldt = (int)d[4]; a.w = FP(1); a.ldw = (int)d[5]; a.b = FP(2);
+      a.logits = FP(3); a.ldl = (int)d[6]; a.dlogits = FP(4); a.dout = FP(5); a.ldo = (int)d[7]; a.gw = FP(6); a.gb = FP(7);
+      a.T = (int)d[0]; a.Nd = (int)d[1]; a.n_real = (int)d[2]; a.dR = (int)d[3]; a.t_real = FP(8); a.t_fake = FP(9); a.loss3 = FP(10); a.part = FP(11);
+      a.want_grads = (int)d[8]; a.want_wgrads = (int)d[9]; a.Bp = (int)d[10]; a.Bt = (int)d[11];
+      launch_dhead(a, s);
+      break;
+    }
+    case 2: {                                            // mse: ptrs y, lab, dy?, lambda, loss, scratch;  dims rows, D, ld, accumulate, Bp, Bt, scratch_floats
+      SG_DIM("rows", d[0], 1); SG_DIM("D", d[1], 1); SG_LD("ld", d[2], d[1]); SG_FLAG("accumulate", d[3]);
+      OP_REFUSE(d[0] * d[2] > ((int64_t)1 << 30), WHO ": rows x ld above the entry's 2^30");
+      UP_BP("rows", d[0], d[4], d[5]);
+      OP_REFUSE(d[6] < 1024, WHO ": scratch of %lld floats below launch_mse's 1024", (long long)d[6]);
+      SG_PTR("y", ptrs[0], 4); SG_PTR("lab", ptrs[1], 4); SG_OPT("dy", ptrs[2], 4); SG_PTR("lambda", ptrs[3], 4); SG_PTR("loss", ptrs[4], 4); SG_PTR("scratch", ptrs[5], 4);
+      launch_mse(FP(0), FP(1), (int)d[2], FP(2), (int)d[0], (int)d[1], FP(3), d[3] != 0, FP(4), FP(5), s, (int)d[4], (int)d[5]);
+      break;
+    }
+    case 3:                                              // g_total: ptrs l4, lambda
+      SG_PTR("l4", ptrs[0], 4); SG_PTR("lambda", ptrs[1], 4);
+      launch_g_total(FP(0), FP(1), s);
+      break;
+    case 4:                                              // l2_total: ptrs partial, l2_scale, out;  dims n
+      SG_DIM("n", d[0], 1);
+      SG_PTR("partial", ptrs[0], 4); SG_PTR("l2_scale", ptrs[1], 4); SG_PTR("out", ptrs[2], 4);
+      launch_l2_total(FP(0), (int)d[0], FP(1), FP(2), s);
+      break;
+    case 5: {                                            // adam_tick: ptrs dyn, t;  dims lr_slot, lrt_slot;  fl beta1, beta2
+      const bool g = d[0] == DYN_G_LR && d[1] == DYN_ADAM_LRT, dd = d[0] == DYN_D_LR && d[1] == DYN_ADAM_LRT_D;
+      OP_REFUSE(!g && !dd, WHO ": slots (%lld, %lld) are neither (%d, %d) (G) nor (%d, %d) (D)", (long long)d[0], (long long)d[1], (int)DYN_G_LR,
+                (int)DYN_ADAM_LRT, (int)DYN_D_LR, (int)DYN_ADAM_LRT_D);
+      OP_REFUSE(!(fl[0] >= 0.f && fl[0] < 1.f) || !(fl[1] >= 0.f && fl[1] < 1.f), WHO ": beta1 = %g or beta2 = %g outside [0, 1)", (double)fl[0], (double)fl[1]);
+      SG_PTR("dyn", ptrs[0], 4); SG_PTR("t", ptrs[1], 4);
+      launch_adam_tick(FP(0), (int*)ptrs[1], (double)fl[0], (double)fl[1], s, (int)d[0], (int)d[1]);
+      break;
+    }
+    case 6: case 7: case 8: {                            // dropout_fwd: ptrs y;  dims rows, cols, ld, key, thr;  fl keep
+      // dropout_bwd: ptrs y, d;  dims rows, cols, ld;  fl keep.   lrelu_bwd: ptrs h, d;  dims rows, cols, ld;  fl alpha
+      SG_DIM("rows", d[0], 1); SG_DIM("cols", d[1], 1); SG_LD("ld", d[2], d[1]);
+      OP_REFUSE(d[0] * d[2] > ((int64_t)1 << 30), WHO ": rows x ld above the entry's 2^30");
+      if (op != 8) OP_REFUSE(!(fl[0] > 0.f && fl[0] <= 1.f), WHO ": keep = %g outside (0, 1]", (double)fl[0]);
+      if (op == 6) OP_REFUSE(d[4] < 0 || d[4] > (1 << 24), WHO ": thr = %lld outside 0 .. 2^24", (long long)d[4]);
+      SG_PTR(op == 8 ? "h" : "y", ptrs[0], 4);
+      if (op != 6) SG_PTR("d", ptrs[1], 4);
+      if (op == 6) launch_dropout_fwd(FP(0), (size_t)d[0], (int)d[1], (int)d[2], (unsigned long long)d[3], (unsigned)d[4], fl[0], s);
+      else if (op == 7) launch_dropout_bwd(FP(0), FP(1), (size_t)d[0], (int)d[1], (int)d[2], fl[0], s);
+      else launch_lrelu_bwd(FP(0), FP(1), (size_t)d[0], (int)d[1], (int)d[2], fl[0], s);
+      break;
+    }
+  }
+  SG_LAUNCHED();
+}
+#undef WHO
+
 }  // extern "C"

@@ -40,6 +40,10 @@ struct ParamSet {
   float* Gd(int i) const { return g + t[i].off; }
 };
 
+// the six arrays of a ChunkTable (kernels.h) on the host, from tensors given as (float offset, floats, l2 flag): model_init.cpp
+struct ChunkTableHost { std::vector<int> tensor, off, len, t_first, t_count, t_l2; };
+void chunk_table_host(const int64_t* toff, const int64_t* floats, const int* l2, int n, ChunkTableHost& out);
+
 struct LstmLayer {               // one tf.contrib.rnn.LSTMCell(H, use_peepholes, num_proj): P = output/recurrent width
   bool has_proj = true;          // num_proj=None: m = h, P == H, no projection kernel (tWp = -1)
   int I, H, P, ldI, ldP, ldH;

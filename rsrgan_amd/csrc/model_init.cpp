@@ -63,32 +63,45 @@ static void add_lstm(ParamSet& ps, std::vector<LstmLayer>& out, const std::strin
   out.push_back(L);
 }
 
-static int build_chunks(Model& M, ParamSet& ps) {
+// the host half of a ChunkTable (no HIP call): tensor i is floats[i] floats at float offset off[i] of the flat buffer, cut into
+// 4096-float chunks in tensor order, the last chunk of a tensor short.  build_chunks below and the rsrgan_op_update test entry call it.
+void chunk_table_host(const int64_t* toff, const int64_t* floats, const int* l2, int n, ChunkTableHost& out) {
   constexpr int CH = 4096;
-  std::vector<int> tensor, off, len, tfirst, tcount, tl2;
-  for (size_t i = 0; i < ps.t.size(); ++i) {
-    const int64_t n = (int64_t)ps.t[i].rows * ps.t[i].ld;
-    tfirst.push_back((int)tensor.size());
+  out = ChunkTableHost();
+  for (int i = 0; i < n; ++i) {
+    out.t_first.push_back((int)out.tensor.size());
     int cnt = 0;
-    for (int64_t o = 0; o < n; o += CH) {
-      tensor.push_back((int)i);
-      off.push_back((int)(ps.t[i].off + o));
-      len.push_back((int)std::min<int64_t>(CH, n - o));
+    for (int64_t o = 0; o < floats[i]; o += CH) {
+      out.tensor.push_back(i);
+      out.off.push_back((int)(toff[i] + o));
+      out.len.push_back((int)std::min<int64_t>(CH, floats[i] - o));
       ++cnt;
     }
-    tcount.push_back(cnt);
-    tl2.push_back(ps.t[i].l2 ? 1 : 0);
+    out.t_count.push_back(cnt);
+    out.t_l2.push_back(l2[i] ? 1 : 0);
   }
+}
+
+static int build_chunks(Model& M, ParamSet& ps) {
+  std::vector<int64_t> toff, floats;
+  std::vector<int> l2;
+  for (const TensorDesc& d : ps.t) {
+    toff.push_back(d.off);
+    floats.push_back((int64_t)d.rows * d.ld);
+    l2.push_back(d.l2 ? 1 : 0);
+  }
+  ChunkTableHost h;
+  chunk_table_host(toff.data(), floats.data(), l2.data(), (int)ps.t.size(), h);
   auto up = [&](const std::vector<int>& v, const int*& dst) -> hipError_t {      // (a failed allocation is the stage's to report)
     int* d = M.alloc<int>(v.size());
     dst = d;
     return d ? hipMemcpy(d, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice) : hipSuccess;
   };
-  HIPC(up(tensor, ps.ct.tensor)); HIPC(up(off, ps.ct.off)); HIPC(up(len, ps.ct.len));
-  HIPC(up(tfirst, ps.ct.t_first)); HIPC(up(tcount, ps.ct.t_count)); HIPC(up(tl2, ps.ct.t_l2));
-  ps.ct.n_chunks = (int)tensor.size();
+  HIPC(up(h.tensor, ps.ct.tensor)); HIPC(up(h.off, ps.ct.off)); HIPC(up(h.len, ps.ct.len));
+  HIPC(up(h.t_first, ps.ct.t_first)); HIPC(up(h.t_count, ps.ct.t_count)); HIPC(up(h.t_l2, ps.ct.t_l2));
+  ps.ct.n_chunks = (int)h.tensor.size();
   ps.ct.n_tensors = (int)ps.t.size();
-  ps.partial = M.alloc<float>(tensor.size());
+  ps.partial = M.alloc<float>(h.tensor.size());
   return RSRGAN_OK;
 }
 

@@ -782,6 +782,37 @@ class HipEngine:
         check(self.lib.rsrgan_op_segan_last_plan(out))
         return dict(zip(SEGAN_PLAN_FIELDS, list(out)))
 
+    def op_chunks(self, tensors) -> dict:
+        """the model's chunk table of tensors [(float offset, floats, l2 flag)] (no device)"""
+        flat = [int(v) for t in tensors for v in t]
+        tt = (C.c_int64 * len(flat))(*flat)
+        nc = C.c_int32()
+        check(self.lib.rsrgan_op_chunks(tt, len(tensors), None, 0, C.byref(nc)))
+        n = 3 * nc.value + 3 * len(tensors)
+        out = (C.c_int32 * n)()
+        check(self.lib.rsrgan_op_chunks(tt, len(tensors), out, n, C.byref(nc)))
+        o, res, at = list(out), {}, 0
+        for name, cnt in (("tensor", nc.value), ("off", nc.value), ("len", nc.value), ("t_first", len(tensors)), ("t_count", len(tensors)),
+                          ("t_l2", len(tensors))):
+            res[name] = o[at:at + cnt]
+            at += cnt
+        return res
+
+    def op_update(self, op, tensors, ptrs, buf_floats, partial_floats, extra=(), src=()):
+        """rsrgan_op_update, op by name (_lib.UPDATE_OPS); tensors [(offset, floats, l2)], extra: the op's own dims, src: dw_reduce's offsets"""
+        from ._lib import UPDATE_OPS
+        dims = [len(tensors), buf_floats, partial_floats] + (list(extra) + [0, 0, 0])[:3] + [v for t in tensors for v in t] + list(src)
+        pt = (C.c_void_p * len(ptrs))(*[None if t is None else t.data_ptr() for t in ptrs])
+        check(self.lib.rsrgan_op_update(UPDATE_OPS.index(op), pt, (C.c_int64 * len(dims))(*[int(v) for v in dims]), None, self._stream()))
+
+    def op_step_elem(self, op, ptrs, dims=(), fl=()):
+        """rsrgan_op_step_elem, op by name (_lib.STEP_ELEM_OPS); ptrs: tensors or None, dims: ints (a dropout key: any 64-bit value), fl: floats"""
+        from ._lib import STEP_ELEM_OPS
+        pt = (C.c_void_p * max(len(ptrs), 1))(*[None if t is None else t.data_ptr() for t in ptrs])
+        dm = (C.c_int64 * max(len(dims), 1))(*[(int(v) + 2 ** 63) % 2 ** 64 - 2 ** 63 for v in dims])
+        ff = (C.c_float * max(len(fl), 1))(*[float(v) for v in fl])
+        check(self.lib.rsrgan_op_step_elem(STEP_ELEM_OPS.index(op), pt, dm, ff, self._stream()))
+
     def op_lstm_colsums(self, dz, cprev, ccur, db, dwi, dwf, dwo, rows, H):
         """lists of nb tensors each: dz [rows][4H], cprev / ccur [rows][H], db [>= 4H], dwi / dwf / dwo [>= H]"""
         check(self.lib.rsrgan_op_lstm_colsums(len(dz), self._table(dz), self._table(cprev), self._table(ccur), self._table(db),

@@ -225,6 +225,11 @@ def seq_dropout_mask(seed, run, layer, B, T, P, keep_prob):
 
 def _mask_of_tag(seed, run, tag, rows, cols, keep_prob):
     key = _splitmix64_int((_splitmix64_int((seed ^ ((run * 0xD1342543DE82EF95) & _M64)) & _M64) + tag) & _M64)
+    return mask_of_key(key, rows, cols, keep_prob)
+
+
+def mask_of_key(key, rows, cols, keep_prob):
+    """the mask launch_dropout_fwd draws for `key`: element i = row * cols + col is kept iff (splitmix64(key + i) >> 40) < floor(keep * 2^24)"""
     with np.errstate(over="ignore"):
         x = np.uint64(key) + np.arange(rows * cols, dtype=np.uint64)
         x = x + np.uint64(0x9E3779B97F4A7C15)
