@@ -124,6 +124,51 @@ struct FcStage {
   bool accumulate = false;
 };
 
+// Everything a G-run (Model::g_backward) decides before its first launch (Model::plan_g_run).  Decided on the host and
+// outside run_seg because a replayed graph segment does not run its body: what must survive the call cannot be set in there.
+struct GRunPlan {
+  int T = 0, R = 0;               // frames, T * B rows
+  bool want_grads = false, reuse = false;
+  const float* nf = nullptr;      // the staged noise_fake (never the caller's pointer: it would enter a graph)
+  bool l2_on = false;
+  bool wave_bwd = false;          // ONE backward wave / the persistent BPTT launches (gradients, discriminator_lstm, RSRGAN_FLAG_WAVEFRONT)
+  // per-layer weight-gradient segments exist for the caller's bucketed all-reduce; rsrgan_g_step applies the update itself, so nothing
+  // can run between the backward pass and the optimizer: one segment, no graph boundaries between the layers
+  bool bucketed = false;
+  bool g_bptt_persist = false;    // persist_backward_g takes the wired generator chain (asked once, check_only)
+  // Without gradient buckets and with the generator's BPTT as a persistent launch, the two FCs' parameter gradients -- eight short
+  // launches that used to FOLLOW the dK GEMMs -- ride the side stream beside them
+  bool fcs_inside = false;
+  bool trail_plan = false;        // the discriminator's BPTT in its trailing form beside the generator's (persist_backward_trail)
+  // RSRGAN_DPIPE: the next D-run's D(real) may start as soon as the fused backward launch has finished -- ev_dfree is recorded between
+  // two graph segments: the launch closes the first, the weight gradients (and the inlined update) are the second
+  bool gsplit = false;
+  // rsrgan_g_step with nothing left between the backward segment and the update (no input-FC segment, no buckets): the loss tail and
+  // the update's launches close the main segment -- ONE graph per G-run instead of three
+  bool inl = false;
+  unsigned kbits = 0;             // the segment keys' configuration bits
+  Chain dch, gch;                 // wave_bwd: the discriminator's chain (data gradient only, layer 0 accumulates into dy) and the generator's, wired
+  float* dy = nullptr;            // [T*B][ldDout] d(loss)/dy of the wavefront backward
+  float* dh0 = nullptr;           // the buffer that holds d(h0) behind the generator's BPTT (lstm: feeds the input FC)
+};
+// The same for a D-run (Model::d_backward).
+struct DRunPlan {
+  int T = 0;
+  bool want_grads = false;
+  const float *nr = nullptr, *nf = nullptr;      // the staged noise tensors
+  bool dsplit = false;            // RSRGAN_DPIPE: D(real) on the side stream ahead of the call, the run itself is k_glstm_fwd_dt
+  bool inl = false;               // rsrgan_d_step: the update's launches close the segment
+  unsigned kbits = 0;
+};
+// sets a member for a scope: an early return cannot leave it set
+template <class V> struct ScopedSet {
+  V& ref; V old;
+  ScopedSet(V& r, V v) : ref(r), old(r) { r = v; }
+  ~ScopedSet() { ref = old; }
+  ScopedSet(const ScopedSet&) = delete;
+  ScopedSet& operator=(const ScopedSet&) = delete;
+};
+
 // ---- recurrent batch-norm LSTMP generator (bnlstm.cpp / bnlstm.hip; models/bnlstm.py, models/BNLSTMCell.py) ----
 // Device view of one BNLSTMCell layer for the step kernels (by value: a captured graph holds it).  Row-major [t][b][...] buffers
 // over exactly the caller's B rows (never padded: every row enters every step's batch statistics).
@@ -207,6 +252,7 @@ struct Model {
   unsigned* dp_ctl = nullptr;                             // kernels.h DP_CTL_*
   size_t dp_gran_bytes = 0;
   int dp_live = sw.dpersist;                              // RSRGAN_DPERSIST's bits (0 forward, 1 backward) until persist_disable clears them
+  bool dpersist_fill(DPersistArgs& a, const Chain& ch, int T, unsigned flags, unsigned long long* gran, unsigned* ctl) const;      // the one chain -> launch arguments fill (model.cpp DPA_*)
   bool persist_forward(Chain& ch, int T, hipStream_t s);  // false: not applicable -> caller falls back to fold_forward
   bool persist_backward(Chain& ch, int T, hipStream_t s); // BPTT of the chain + its weight gradients; false: not applicable
   // the G-run's discriminator BPTT in its trailing form (dpersist_dev.h): fills dt_args for the k_glstm_bwd_dt launch that
@@ -257,7 +303,7 @@ struct Model {
   bool g_carry = false;                                   // the forward being issued is the stateful one
   void gstate_xfer(int dir, int T, int rows, const int* mask, hipStream_t s);
   typedef std::function<void(hipStream_t)> StreamFn;
-  bool persist_backward_g(Chain& ch, int T, hipStream_t s, bool check_only = false, const StreamFn& pre = nullptr, const StreamFn& post = nullptr);   // BPTT of the generator chain (k_glstm_bwd), layer 0's input gradient as a GEMM, the weight gradients unless deferred
+  bool persist_backward_g(const Chain& ch, int T, hipStream_t s, bool check_only = false, const StreamFn& pre = nullptr, const StreamFn& post = nullptr);   // BPTT of the generator chain (k_glstm_bwd), layer 0's input gradient as a GEMM, the weight gradients unless deferred
   // fully-connected stacks: models/dnn.py generator and models/discriminator_dnn.py discriminator
   std::vector<FcLayer> gfc, dfc;
   std::vector<float*> g_act, d_act;        // act[l] = input of FC layer l, act[L] = output of the stack
@@ -409,6 +455,29 @@ struct Model {
   void d_backward_pass(int N, int T, bool want_wgrads, bool need_dx0, const float* dlog, hipStream_t s, bool head_done = false);
   bool d_head(int N, int T, int n_real, const float* t_real, const float* t_fake, float* loss3, bool want_grads, bool want_wgrads, hipStream_t s);
   void g_backward_pass(int T, float* dy, hipStream_t s);
+  // pieces both drivers and the layer-by-layer passes share (model_step.cpp, in front of the drivers)
+  void g_fc_out_wgrads(const float* dy, int R, hipStream_t q);                 // the output FC's dW and db (the side stream's scratch on the side stream)
+  float* wire_g_bptt(Chain& ch, float* a, float* b);                            // dout / din of the generator's BPTT over ping-pong a, b; returns where d(h0) ends up
+  float* wire_d_bptt(Chain& ch, bool want_wgrads, float* din0, bool accumulate0);      // the discriminator's over d_dB, d_dA; returns the buffer layer 0 leaves free
+  FcStage g_out_fc_stage(const float* nf, int Ns2, int row02);                 // the output FC riding a forward wave: y_t and the discriminator's input rows
+  bool d_head_or_logits(int N, int T, int n_real, const float* t_fake, float* loss3, bool want_grads, bool want_wgrads, hipStream_t s);
+  void g_loss_tail(bool l2, hipStream_t s);                                    // the L2 term (or its zero) and g_loss = adv + lambda * mse + l2
+  // the G-run's plan and stages
+  GRunPlan plan_g_run(int T, const float* nf, bool want_grads, bool reuse, hipStream_t s);
+  void g_fc_side_pair(const GRunPlan& p, StreamFn& pre, StreamFn& post);
+  bool g_run_forward(const GRunPlan& p, hipStream_t s);
+  void g_run_d_forward(const GRunPlan& p, hipStream_t s);
+  bool g_run_loss_head(const GRunPlan& p, hipStream_t s);
+  bool g_run_backward(const GRunPlan& p, bool g_head, hipStream_t s);
+  bool g_run_bptt_fused(const GRunPlan& p, hipStream_t s);
+  void g_run_bwd_rest(const GRunPlan& p, hipStream_t s);
+  void g_run_tail(const GRunPlan& p, hipStream_t s);
+  int g_supervised_step(const float* x, const float* labels, const int32_t* lengths, int T, float* out_losses, bool want_grads, hipStream_t s);
+  // the D-run's
+  DRunPlan plan_d_run(int T, const float* nr, const float* nf, bool want_grads, hipStream_t s);
+  void d_run_forward(const DRunPlan& p, hipStream_t s);
+  void d_run_head_backward(const DRunPlan& p, hipStream_t s);
+  bool g_forward_persist(int T, hipStream_t s);                                // head (done by the caller) + ONE persistent launch + tail; false: not applicable
   int d_backward(const float* x, const float* labels, const int32_t* lengths, int T, const float* nr, const float* nf,
                  float* out_losses, bool want_grads, hipStream_t s);
   int g_backward(const float* x, const float* labels, const int32_t* lengths, int T, const float* nf,
@@ -426,10 +495,10 @@ struct Model {
   void rnn_backward(std::vector<Chain>& chains, int T, hipStream_t s, const std::vector<int>* offsets = nullptr,
                     const std::vector<FcStage>* fcs = nullptr);
   void layer_wgrads(const LayerRun& R, int T, hipStream_t s);
-  void chain_wgrads(Chain& ch, int T, hipStream_t s, const StreamFn& between, const StreamFn& pre = nullptr, const StreamFn& post = nullptr);   // all layers of a finished BPTT, on two streams
+  void chain_wgrads(const Chain& ch, int T, hipStream_t s, const StreamFn& between, const StreamFn& pre = nullptr, const StreamFn& post = nullptr);   // all layers of a finished BPTT, on two streams
   void layer_wgrads_gemms(const LayerRun& R, int t0, int t1, bool accumulate, hipStream_t s, bool do_dK = true, bool do_dWp = true);
   int trail_nrt() const;
-  bool batch_wgrads(Chain& ch, int T, hipStream_t s, bool dK_too, bool* dK_done, bool check_only = false);      // all layers of one shape: one launch per kind
+  bool batch_wgrads(const Chain& ch, int T, hipStream_t s, bool dK_too, bool* dK_done, bool check_only = false);      // all layers of one shape: one launch per kind
   void layer_wgrads_colsums(const LayerRun& R, int T, hipStream_t s, float* scr);
   // side stream: weight-gradient GEMMs (MFMA-bound) overlap the byte-bound backward wave
   hipStream_t side = nullptr;

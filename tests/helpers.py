@@ -218,7 +218,7 @@ def dropout_mask(seed, run, net, layer, call, rows, cols, keep_prob):
 
 
 def seq_dropout_mask(seed, run, layer, B, T, P, keep_prob):
-    """DropoutWrapper masks of the sequence generators (csrc/kernels.h DropSpec; csrc/model.cpp g_chain: tag = 1<<40 | layer<<20 | t,
+    """DropoutWrapper masks of the sequence generators (csrc/kernels.h DropSpec; csrc/model_step.cpp g_chain: tag = 1<<40 | layer<<20 | t,
     element = row * P + col) as a [B, T, P] array"""
     return np.stack([_mask_of_tag(seed, run, (1 << 40) | (layer << 20) | t, B, P, keep_prob) for t in range(T)], axis=1)
 
