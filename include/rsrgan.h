@@ -473,6 +473,38 @@ int rsrgan_feat_batch(const float* raw, int64_t raw_rows, const int32_t* offsets
  * 2^32 - 1 elements; pool_rows * D above 2^40. */
 int rsrgan_feat_frames(const float* pool, int64_t pool_rows, const int32_t* picks, int32_t N, int32_t D, int32_t left, int32_t right,
                        const double* mean, const double* stddev, float* out, void* stream);
+/* The live path's form (rsrgan_amd/stream.py StreamBank): streaming append and splice on a device-resident ring, one launch, no handle.
+ * hist [B][H][D] holds each row's NORMALISED frames, utterance frame j of row r in slot j mod H (mod: the non-negative remainder);
+ * fresh [fresh_rows][D] holds the raw frames that arrived with this call, packed over all rows; table [B][6] =
+ * (src, app0, napp, emit0, nemit, last) per row.  With Dout = D * (left + 1 + right):
+ *   append:  hist[r][(app0 + i) mod H][d] = norm(fresh[clamp(src + i, 0, fresh_rows - 1)][d])      i in [0, napp)
+ *   emit:    out[r, t, c * D + d] = hist'[r][clamp(emit0 + t + c - left, 0, last) mod H][d]         t < min(nemit, T)
+ *            out[r, t, :]         = +0.0                                             otherwise (every t when nemit <= 0 or last < 0)
+ *            lengths[r]           = clamp(nemit, 0, T)
+ *   norm(v)  = mean ? (float)(((double)v - mean[d]) / stddev[d]) : v
+ * hist' is the ring after this call's append: the emit behaves as if the append had happened first.  Columns as above.  The clamp at 0
+ * and at `last` is the utterance's own edge (a caller that never asks for a frame whose right context is incomplete makes the clamp at
+ * `last` inert until the utterance ends, where it repeats the last frame).  Negative napp or nemit count as 0; with fresh_rows == 0
+ * every napp counts as 0 (a flush-only call); where napp > H the last write to a slot stands.  Normalising once on append and gathering
+ * fp32 afterwards gives the host path's bits.  With these rules and the clamp on `fresh`, the kernel reads and writes nothing outside
+ * its buffers, whatever the table holds.  The values are the utterance's only while the window fits the ring,
+ * last - (emit0 - left) + 1 <= H with emit0 - left <= app0 and app0 + napp - 1 <= last: that is the caller's to keep.  All pointers are
+ * DEVICE pointers; lengths may be NULL; mean and stddev ([D] double) are both given or both NULL.  RSRGAN_ERR_INVALID before the first
+ * HIP call, rsrgan_last_error() naming the argument, for: a null table, hist or out; a null fresh unless fresh_rows == 0; only one of
+ * mean / stddev; fresh, hist or out not 16-byte aligned; table or lengths not 4-byte, mean or stddev not 8-byte aligned; B, H, T or D
+ * below 1; fresh_rows negative; left or right negative or above 1024; B * T * D * (left + 1 + right) or B * H * D above 2^32 - 1
+ * elements; fresh_rows * D above 2^40. */
+int rsrgan_feat_stream(const float* fresh, int64_t fresh_rows, const int32_t* table, float* hist, int32_t B, int32_t H, int32_t T, int32_t D,
+                       int32_t left, int32_t right, const double* mean, const double* stddev, float* out, int32_t* lengths, void* stream);
+/* The output side: de-normalise G(x) y [B][T][D] (fp32) with the label statistics into out [B][T][D] (fp64), one launch, no handle:
+ *   out[b, t, d] = t < len_b ? fl64(fl64((double)y[b, t, d] * stddev[d]) + mean[d]) : 0.0     len_b = lengths ? clamp(lengths[b], 0, T) : T
+ * The product and the sum are rounded separately, which is what NumPy's `y * stddev + mean` computes on a float32 array and float64
+ * statistics: the results are equal bit for bit (a fused multiply-add would give other bits).  All pointers are DEVICE pointers;
+ * lengths may be NULL.  RSRGAN_ERR_INVALID before the first HIP call, rsrgan_last_error() naming the argument, for: a null y, out, mean or
+ * stddev; y not 16-byte aligned; lengths not 4-byte aligned; mean, stddev or out not 8-byte aligned; B, T or D below 1; B * T * D above
+ * 2^32 - 1 elements. */
+int rsrgan_feat_denorm(const float* y, const int32_t* lengths, int32_t B, int32_t T, int32_t D, const double* mean, const double* stddev,
+                       double* out, void* stream);
 
 /* ---- the SEGAN operators (csrc/segan.hip and the window-GEMM primitives of csrc/segan.cpp).  Unit parity tests only
  * (tests/test_gpu_segan_ops.py, tests/test_op_args.py); no trainer calls them.  Each goes through the host function SeganModel calls

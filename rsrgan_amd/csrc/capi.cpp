@@ -961,6 +961,47 @@ int rsrgan_feat_frames(const float* pool, int64_t pool_rows, const int32_t* pick
   return RSRGAN_OK;
 }
 
+int rsrgan_feat_stream(const float* fresh, int64_t fresh_rows, const int32_t* table, float* hist, int32_t B, int32_t H, int32_t T, int32_t D,
+                       int32_t left, int32_t right, const double* mean, const double* stddev, float* out, int32_t* lengths, void* stream) {
+  OP_REFUSE(!table || !hist || !out, "feat_stream: null pointer (table, hist or out)");
+  OP_REFUSE(fresh_rows < 0, "feat_stream: fresh_rows = %lld is negative", (long long)fresh_rows);
+  OP_REFUSE(!fresh && fresh_rows != 0, "feat_stream: null pointer (fresh) with fresh_rows = %lld: fresh may be null only when fresh_rows is 0",
+            (long long)fresh_rows);
+  OP_REFUSE((mean == nullptr) != (stddev == nullptr), "feat_stream: mean and stddev must both be given or both be null");
+  OP_REFUSE(((size_t)fresh & 15) || ((size_t)hist & 15) || ((size_t)out & 15), "feat_stream: fresh, hist or out not 16-byte aligned");
+  OP_REFUSE(((size_t)table & 3) || ((size_t)lengths & 3), "feat_stream: table or lengths not 4-byte aligned");
+  OP_REFUSE(((size_t)mean & 7) || ((size_t)stddev & 7), "feat_stream: mean or stddev not 8-byte aligned");
+  OP_REFUSE(B < 1 || H < 1 || T < 1 || D < 1, "feat_stream: B, H, T, D must be positive (got %d, %d, %d, %d)", B, H, T, D);
+  OP_REFUSE(left < 0 || right < 0, "feat_stream: negative context (left %d, right %d)", left, right);
+  OP_REFUSE(left > 1024 || right > 1024, "feat_stream: context above the entry's 1024 (left %d, right %d)", left, right);
+  const unsigned long long lim = 0xFFFFFFFFull;            // flat indices are divided in 32 bits (feat.hip)
+  const unsigned long long bt = (unsigned long long)B * (unsigned long long)T, bh = (unsigned long long)B * (unsigned long long)H;      // (< 2^62)
+  OP_REFUSE(bt > lim || bt * (unsigned long long)D > lim || bt * (unsigned long long)D * (unsigned long long)(left + 1 + right) > lim,
+            "feat_stream: B x T x D x (left + 1 + right) = %d x %d x %d x %d above the entry's 2^32 - 1 elements", B, T, D, left + 1 + right);
+  OP_REFUSE(bh > lim || bh * (unsigned long long)D > lim, "feat_stream: B x H x D = %d x %d x %d above the entry's 2^32 - 1 elements", B, H, D);
+  OP_REFUSE((unsigned long long)fresh_rows > ((1ull << 40) / (unsigned long long)D), "feat_stream: fresh_rows x D = %lld x %d above the entry's 2^40",
+            (long long)fresh_rows, D);
+  launch_feat_stream(fresh, (long long)fresh_rows, table, hist, B, H, T, D, left, right, mean, stddev, out, lengths, (hipStream_t)stream);
+  if (hipGetLastError() != hipSuccess) { set_error("feat_stream launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
+
+int rsrgan_feat_denorm(const float* y, const int32_t* lengths, int32_t B, int32_t T, int32_t D, const double* mean, const double* stddev,
+                       double* out, void* stream) {
+  OP_REFUSE(!y || !out, "feat_denorm: null pointer (y or out)");
+  OP_REFUSE(!mean || !stddev, "feat_denorm: null pointer (mean or stddev): both are needed");
+  OP_REFUSE((size_t)y & 15, "feat_denorm: y not 16-byte aligned");
+  OP_REFUSE((size_t)lengths & 3, "feat_denorm: lengths not 4-byte aligned");
+  OP_REFUSE(((size_t)mean & 7) || ((size_t)stddev & 7) || ((size_t)out & 7), "feat_denorm: mean, stddev or out not 8-byte aligned");
+  OP_REFUSE(B < 1 || T < 1 || D < 1, "feat_denorm: B, T, D must be positive (got %d, %d, %d)", B, T, D);
+  const unsigned long long lim = 0xFFFFFFFFull;            // flat indices are divided in 32 bits (feat.hip)
+  const unsigned long long bt = (unsigned long long)B * (unsigned long long)T;       // (< 2^62: no overflow before the checks)
+  OP_REFUSE(bt > lim || bt * (unsigned long long)D > lim, "feat_denorm: B x T x D = %d x %d x %d above the entry's 2^32 - 1 elements", B, T, D);
+  launch_feat_denorm(y, lengths, B, T, D, mean, stddev, out, (hipStream_t)stream);
+  if (hipGetLastError() != hipSuccess) { set_error("feat_denorm launch failed"); return RSRGAN_ERR_HIP; }
+  return RSRGAN_OK;
+}
+
 // ---- the SEGAN operators (segan.hip, and the window-GEMM primitives of segan.cpp) through the host functions SeganModel calls, on
 // caller-owned buffers (tests/test_gpu_segan_ops.py).  One entry per family: op selects the launcher, ptrs is a HOST table of device
 // pointers, dims a host table of sizes, fl of float parameters, each in the order include/rsrgan.h lists.

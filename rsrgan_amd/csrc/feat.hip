@@ -14,6 +14,11 @@
 // most 2048 workgroups of 256.  The flat index is 64 bits wide where it is an address or a loop counter; it is below 2^32 (the entry's
 // limit), so the divisions are 32-bit.  Source rows are clamped into [0, raw_rows): whatever the offset table holds, no lane reads
 // outside raw.  No atomics, no LDS, no scratch memory.
+// Further down, in the same layout: k_feat_frames (the frame-level recipes: a gather from a resident pool), k_feat_stream (the live path:
+// append to a per-row ring of normalised frames and emit the spliced rows) and k_feat_denorm (the output side, float64).  k_feat_stream is
+// ONE launch, not an append launch and an emit launch: a live round is a few hundred rows, so a launch costs more than the work in it, and
+// the emit needs no order against the append because it takes this call's frames from `fresh` (normalising them with the append's own
+// expression) and only older frames from the ring, which the window invariant stated at the kernel keeps in other slots.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -194,6 +199,201 @@ void launch_feat_frames(const float* pool, long long pool_rows, const int* picks
   else
     hipLaunchKernelGGL(k_feat_frames<false>, dim3(grid), dim3(256), 0, s, pool, pool_rows, picks, (uint32_t)D, left, (uint32_t)C, mean, stddev, out,
                        total);
+}
+
+// ---- the live path's front end: streaming append and splice on a device-resident ring.  hist [B][H][D] holds each row's NORMALISED frames,
+// utterance frame j of row r in slot j mod H (the non-negative remainder); fresh [fresh_rows][D] holds the raw frames that arrived with this
+// call, packed over all rows; table [B][6] = (src, app0, napp, emit0, nemit, last) per row.  With C = left + 1 + right, Dout = D * C:
+//   append:  hist[r][(app0 + i) mod H][d] = norm(fresh[clamp(src + i, 0, fresh_rows - 1)][d])      i in [0, napp)
+//   emit:    out[r, t, c * D + d] = hist'[r][clamp(emit0 + t + c - left, 0, last) mod H][d]         t < min(nemit, T)
+//            out[r, t, :]         = +0.0                                                           otherwise (every t when nemit <= 0 or last < 0)
+//            lengths[r]           = clamp(nemit, 0, T)
+// hist' is the ring after this call's append; negative napp / nemit count as 0, and every napp counts as 0 when fresh_rows == 0.  Where
+// napp > H the formula writes a slot more than once and the last write stands: the kernel writes only i in [max(0, napp - H), napp), which
+// is that result, each slot written by one lane, and bounds the work per row at H * D whatever the table holds.
+//
+// ONE launch, not an append launch followed by an emit launch.  A live round is tiny (32 rows x 10 frames in the record of
+// profiles/feat_stream.txt): a second launch would cost more than everything the first one computes.  The emit therefore does not read
+// this call's frames from the ring, where another lane of the same launch may not have stored them yet: a frame j in
+// [app0 + max(0, napp - H), app0 + napp) is taken from `fresh` and normalised on the spot -- the same expression on the same operands as
+// the append evaluates, so the same bits as the slot will hold -- and every other frame is read from `hist`.
+// The window invariant (the caller's; StreamBank asserts it before each call): last - (emit0 - left) + 1 <= H, with
+// emit0 - left <= app0 and app0 + napp - 1 <= last.  The frames the emit reads, j in [max(emit0 - left, 0), last], and the frames the append
+// stores, j in [app0, app0 + napp), then lie in ONE run of at most H consecutive frame numbers, which occupy pairwise different slots.  An
+// old frame (j < app0) and an appended one (j >= app0) are different numbers of that run, hence different slots: no slot the append writes
+// is a slot this call still reads as an old frame, and the launch has no read-after-write order to keep.  Outside the invariant the values
+// are not the utterance's (a slot may be read while it is rewritten) but nothing else happens: every slot index is a remainder below H,
+// every row of `fresh` is clamped into [0, fresh_rows), and the output row is decided by t and nemit alone.
+// Layout: the emit is k_feat_batch's (out as one flat 16-byte aligned array, a lane owns four consecutive elements, the last total % 4 are
+// stored one by one).  The append stores single floats: the slots it writes are scattered through the ring (D is no multiple of 4, and a
+// quad would cover elements of frames that are not rewritten).  Grid-stride, at most 2048 workgroups of 256; no atomics, no LDS, no
+// scratch memory.
+struct StreamRow { long long src, app0, napp, lo, emit0, nemit, last; };      // lo: first i the append writes (max(0, napp - H))
+
+__device__ __forceinline__ StreamRow stream_row(const int* __restrict__ table, uint32_t r, long long fresh_rows, uint32_t H) {
+  const int* t = table + (size_t)r * 6;
+  StreamRow k;
+  k.src = t[0]; k.app0 = t[1]; k.napp = fresh_rows > 0 ? max((long long)t[2], 0ll) : 0ll;
+  k.lo = max(k.napp - (long long)H, 0ll);
+  k.emit0 = t[3]; k.nemit = t[4]; k.last = t[5];
+  return k;
+}
+
+__device__ __forceinline__ uint32_t stream_slot(long long j, uint32_t H) {
+  const long long m = j % (long long)H;
+  return (uint32_t)(m < 0 ? m + (long long)H : m);
+}
+
+// the raw frame the append stores as utterance frame app0 + i
+__device__ __forceinline__ const float* stream_fresh(const float* __restrict__ fresh, long long fresh_rows, const StreamRow& k, long long i, uint32_t D) {
+  return fresh + (size_t)min(max(k.src + i, 0ll), fresh_rows - 1) * D;
+}
+
+struct StreamSrc { const float* p; bool raw; };      // D floats (null: a zero row); raw: from `fresh`, still to be normalised
+
+__device__ __forceinline__ StreamSrc stream_src(const float* __restrict__ fresh, long long fresh_rows, const float* hist, const StreamRow& k,
+                                                const FeatPos& p, int left, uint32_t H, uint32_t D) {
+  StreamSrc s;
+  s.p = nullptr; s.raw = false;
+  if ((long long)p.t >= k.nemit || k.last < 0) return s;
+  const long long j = min(max(k.emit0 + (long long)p.t + (long long)p.c - left, 0ll), k.last);      // clamped at the utterance's own first and last frame
+  const long long i = j - k.app0;
+  if (i >= k.lo && i < k.napp) { s.p = stream_fresh(fresh, fresh_rows, k, i, D); s.raw = true; }
+  else s.p = hist + ((size_t)p.b * H + stream_slot(j, H)) * D;
+  return s;
+}
+
+template <bool NORM>
+__device__ __forceinline__ float stream_value(const StreamSrc& s, uint32_t d, const double* __restrict__ mean, const double* __restrict__ stddev) {
+  if (!s.p) return 0.f;
+  return s.raw ? feat_value<NORM>(s.p, d, mean, stddev) : s.p[d];
+}
+
+template <bool NORM>
+__global__ __launch_bounds__(256) void k_feat_stream(const float* __restrict__ fresh, long long fresh_rows, const int* __restrict__ table, float* hist,
+                                                     int B, uint32_t H, uint32_t T, uint32_t D, int left, uint32_t C,
+                                                     const double* __restrict__ mean, const double* __restrict__ stddev, float* __restrict__ out,
+                                                     int* __restrict__ lengths, unsigned long long total, unsigned long long ring) {
+  const uint32_t Dout = D * C;
+  const unsigned long long gid = (unsigned long long)blockIdx.x * 256 + threadIdx.x, stride = (unsigned long long)gridDim.x * 256;
+  if (lengths) {
+    for (unsigned long long b = gid; b < (unsigned long long)B; b += stride)
+      lengths[b] = (int)min(max((long long)table[b * 6 + 4], 0ll), (long long)T);
+  }
+  // the append: element e of the ring is (r, slot, d); the one i in [lo, lo + H) whose frame app0 + i lives in that slot is stored if i < napp
+  if (fresh_rows > 0) {
+    for (unsigned long long e = gid; e < ring; e += stride) {       // (ring = B * H * D < 2^32)
+      const uint32_t fr = (uint32_t)e / D, d = (uint32_t)e - fr * D, r = fr / H, slot = fr - r * H;
+      const StreamRow k = stream_row(table, r, fresh_rows, H);
+      if (k.napp <= 0) continue;
+      const long long i = k.lo + (long long)stream_slot((long long)slot - k.app0 - k.lo, H);
+      if (i < k.napp) hist[e] = feat_value<NORM>(stream_fresh(fresh, fresh_rows, k, i, D), d, mean, stddev);
+    }
+  }
+  // the emit
+  const unsigned long long quads = total >> 2;
+  for (unsigned long long q = gid; q < quads; q += stride) {
+    FeatPos p = feat_pos((uint32_t)(q << 2), T, D, Dout);             // (total < 2^32)
+    StreamRow k = stream_row(table, p.b, fresh_rows, H);
+    StreamSrc src = stream_src(fresh, fresh_rows, hist, k, p, left, H, D);
+    float v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      v[i] = stream_value<NORM>(src, p.d, mean, stddev);
+      if (i == 3) break;
+      if (++p.d == D) {
+        p.d = 0;
+        if (++p.c == C) {
+          p.c = 0;
+          if (++p.t == T) {                                           // (a quad never runs past the last row: 4 q + 3 < total)
+            p.t = 0; ++p.b;
+            k = stream_row(table, p.b, fresh_rows, H);
+          }
+        }
+        src = stream_src(fresh, fresh_rows, hist, k, p, left, H, D);
+      }
+    }
+    *reinterpret_cast<float4*>(out + (q << 2)) = make_float4(v[0], v[1], v[2], v[3]);
+  }
+  const uint32_t tail = (uint32_t)(total & 3);
+  if (gid < tail) {
+    const unsigned long long e = (quads << 2) + gid;
+    const FeatPos p = feat_pos((uint32_t)e, T, D, Dout);
+    out[e] = stream_value<NORM>(stream_src(fresh, fresh_rows, hist, stream_row(table, p.b, fresh_rows, H), p, left, H, D), p.d, mean, stddev);
+  }
+}
+
+void launch_feat_stream(const float* fresh, long long fresh_rows, const int* table, float* hist, int B, int H, int T, int D, int left, int right,
+                        const double* mean, const double* stddev, float* out, int* lengths, hipStream_t s) {
+  const int C = left + 1 + right;
+  const unsigned long long total = (unsigned long long)B * T * D * C, ring = (unsigned long long)B * H * D;
+  if (!fresh) fresh_rows = 0;
+  // (sized by the emit's quads or the ring's elements, whichever asks for more lanes; one workgroup at least, as in launch_feat_batch)
+  const unsigned long long lanes = std::max<unsigned long long>(total >> 2, fresh_rows > 0 ? ring : 0);
+  const int grid = (int)std::min<unsigned long long>(2048, std::max<unsigned long long>(1, (lanes + 255) / 256));
+  if (mean)
+    hipLaunchKernelGGL(k_feat_stream<true>, dim3(grid), dim3(256), 0, s, fresh, fresh_rows, table, hist, B, (uint32_t)H, (uint32_t)T, (uint32_t)D, left,
+                       (uint32_t)C, mean, stddev, out, lengths, total, ring);
+  else
+    hipLaunchKernelGGL(k_feat_stream<false>, dim3(grid), dim3(256), 0, s, fresh, fresh_rows, table, hist, B, (uint32_t)H, (uint32_t)T, (uint32_t)D, left,
+                       (uint32_t)C, mean, stddev, out, lengths, total, ring);
+}
+
+// ---- the output side: de-normalise G(x) with the label statistics, into the float64 the host path produces.
+//   out[b, t, d] = t < len_b ? fl64(fl64((double)y[b, t, d] * stddev[d]) + mean[d]) : 0.0        len_b = lengths ? clamp(lengths[b], 0, T) : T
+// The product and the sum are rounded SEPARATELY, as NumPy's `y * stddev + mean` rounds them on a float32 array and float64 statistics:
+// contract(off) keeps the compiler from fusing them into one multiply-add, whose single rounding gives other bits.  y is one flat 16-byte
+// aligned array of B * T * D floats: a lane owns four consecutive elements, reads them with one 16-byte load and derives (b, t, d) of the
+// first by division and of the next three by carrying; the last (B * T * D) % 4 elements are handled one by one.  The entry asks only
+// 8-byte alignment of the float64 `out` (a caller may hand in any row of a larger matrix), so the four results leave as 8-byte stores.
+// Grid-stride, at most 2048 workgroups of 256; no atomics, no LDS, no scratch memory.
+__device__ __forceinline__ double denorm_value(float y, uint32_t d, const double* __restrict__ mean, const double* __restrict__ stddev) {
+#pragma clang fp contract(off)
+  const double p = (double)y * stddev[d];
+  return p + mean[d];
+}
+
+__device__ __forceinline__ long long denorm_len(const int* __restrict__ lengths, uint32_t b, uint32_t T) {
+  return lengths ? min(max((long long)lengths[b], 0ll), (long long)T) : (long long)T;
+}
+
+__global__ __launch_bounds__(256) void k_feat_denorm(const float* __restrict__ y, const int* __restrict__ lengths, uint32_t T, uint32_t D,
+                                                     const double* __restrict__ mean, const double* __restrict__ stddev, double* __restrict__ out,
+                                                     unsigned long long total) {
+  const unsigned long long gid = (unsigned long long)blockIdx.x * 256 + threadIdx.x, stride = (unsigned long long)gridDim.x * 256;
+  const unsigned long long quads = total >> 2;
+  for (unsigned long long q = gid; q < quads; q += stride) {
+    const uint32_t e = (uint32_t)(q << 2), row = e / D;              // (total < 2^32)
+    uint32_t d = e - row * D, b = row / T, t = row - b * T;
+    long long n = denorm_len(lengths, b, T);
+    const float4 in = *reinterpret_cast<const float4*>(y + (q << 2));
+    const float v[4] = {in.x, in.y, in.z, in.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      out[(q << 2) + i] = (long long)t < n ? denorm_value(v[i], d, mean, stddev) : 0.0;
+      if (i == 3) break;
+      if (++d == D) {
+        d = 0;
+        if (++t == T) {                                               // (a quad never runs past the last row: 4 q + 3 < total)
+          t = 0; ++b;
+          n = denorm_len(lengths, b, T);
+        }
+      }
+    }
+  }
+  const uint32_t tail = (uint32_t)(total & 3);
+  if (gid < tail) {
+    const unsigned long long e = (quads << 2) + gid;
+    const uint32_t row = (uint32_t)e / D, d = (uint32_t)e - row * D, b = row / T, t = row - b * T;
+    out[e] = (long long)t < denorm_len(lengths, b, T) ? denorm_value(y[e], d, mean, stddev) : 0.0;
+  }
+}
+
+void launch_feat_denorm(const float* y, const int* lengths, int B, int T, int D, const double* mean, const double* stddev, double* out,
+                        hipStream_t s) {
+  const unsigned long long total = (unsigned long long)B * T * D;
+  const int grid = (int)std::min<unsigned long long>(2048, std::max<unsigned long long>(1, ((total >> 2) + 255) / 256));
+  hipLaunchKernelGGL(k_feat_denorm, dim3(grid), dim3(256), 0, s, y, lengths, (uint32_t)T, (uint32_t)D, mean, stddev, out, total);
 }
 
 }  // namespace rsr

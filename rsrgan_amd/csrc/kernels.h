@@ -461,6 +461,16 @@ void launch_feat_batch(const float* raw, long long raw_rows, const int* offsets,
 // aligned, N * Dout < 2^32), mean / stddev [D] double or both null (the pool already normalised).
 void launch_feat_frames(const float* pool, long long pool_rows, const int* picks, int N, int D, int left, int right, const double* mean,
                         const double* stddev, float* out, hipStream_t s);
+// the live path's form: one launch appends the raw frames fresh [fresh_rows][D] (normalised) to the ring hist [B][H][D] (utterance frame j
+// of row r in slot j mod H) and emits out [B][T][D * (left + 1 + right)] from the ring as it stands after the append, by table [B][6] =
+// (src, app0, napp, emit0, nemit, last).  fresh may be null (fresh_rows = 0: nothing is appended).  out 16-byte aligned, B * T * Dout and
+// B * H * D < 2^32, lengths [B] or null, mean / stddev [D] double or both null.
+void launch_feat_stream(const float* fresh, long long fresh_rows, const int* table, float* hist, int B, int H, int T, int D, int left, int right,
+                        const double* mean, const double* stddev, float* out, int* lengths, hipStream_t s);
+// the output side: out [B][T][D] double = (double)y * stddev + mean, two roundings, zero rows from lengths[b] on (lengths null: none).
+// y 16-byte aligned, B * T * D < 2^32.
+void launch_feat_denorm(const float* y, const int* lengths, int B, int T, int D, const double* mean, const double* stddev, double* out,
+                        hipStream_t s);
 void launch_colsum(const float* a, int lda, const float* b, int ldb, float* out, int rows, int cols,
                    float* scratch /* >= 64*cols floats */, hipStream_t s);
 

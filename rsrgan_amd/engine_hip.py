@@ -376,6 +376,43 @@ class HipEngine:
         """forget a reader's pool (its device memory goes back to torch once the last batch gathered from it is consumed)"""
         self.__dict__.get("_frame_pools", {}).pop(reader_id, None)
 
+    # -- the live path's front end and the output side (include/rsrgan.h rsrgan_feat_stream / rsrgan_feat_denorm, csrc/feat.hip) ------
+    def op_feat_stream(self, fresh, table, hist, B, H, T, D, left, right, mean, stddev, out, lengths=None, fresh_rows=None, stream=None):
+        """rsrgan_feat_stream on caller-owned device tensors (fresh [rows, D] f32 or None, table [B, 6] i32 = (src, app0, napp, emit0, nemit,
+        last), hist [B, H, D] f32, mean / stddev [D] f64 or None, out B * T * D * (left + 1 + right) f32, lengths [B] i32 or None), on
+        `stream` (default: the current one)"""
+        rows = (0 if fresh is None else fresh.shape[0]) if fresh_rows is None else fresh_rows
+        check(self.lib.rsrgan_feat_stream(_ptr(fresh), rows, _ptr(table), _ptr(hist), B, H, T, D, left, right, _ptr(mean), _ptr(stddev),
+                                          _ptr(out), _ptr(lengths), self._stream() if stream is None else C.c_void_p(stream.cuda_stream)))
+
+    def op_feat_denorm(self, y, lengths, B, T, D, mean, stddev, out, stream=None):
+        """rsrgan_feat_denorm on caller-owned device tensors (y B * T * D f32, lengths [B] i32 or None, mean / stddev [D] f64, out B * T * D
+        f64), on `stream` (default: the current one)"""
+        check(self.lib.rsrgan_feat_denorm(_ptr(y), _ptr(lengths), B, T, D, _ptr(mean), _ptr(stddev), _ptr(out),
+                                          self._stream() if stream is None else C.c_void_p(stream.cuda_stream)))
+
+    def upload_stream(self):
+        """the stream the feature front end uploads and runs on (featurize, featurize_frames, StreamBank)"""
+        us = getattr(self, "_upload_stream", None)
+        if us is None:
+            us = self._upload_stream = torch.cuda.Stream(self.device)
+        return us
+
+    def denormalize(self, y, mean, stddev, lengths=None):
+        """G(x) y [B, T, D] f32 on the device -> y * stddev + mean as [B, T, D] f64 on the device (rows from lengths[b] on are zero), on the
+        current stream: bit for bit NumPy's result on the host copy.  mean / stddev: host arrays of D entries (uploaded once per pair)."""
+        y = y.contiguous()
+        B, T, D = y.shape
+        if np.size(mean) != D or np.size(stddev) != D:
+            raise ValueError("denormalize: mean / stddev must hold D = %d entries, got %d / %d" % (D, np.size(mean), np.size(stddev)))
+        us = self.upload_stream()
+        dm, ds = self._cmvn_device(mean, stddev, us)
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_stream(us)                                        # (the statistics' upload, the first time)
+        out = torch.empty(B, T, D, dtype=torch.float64, device=self.device)
+        self.op_feat_denorm(y, lengths, B, T, D, dm, ds, out)
+        return out
+
     def _i32(self, a) -> torch.Tensor:
         t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
         return t.to(self.device).to(torch.int32).contiguous()       # placeholder is float32, cast like dynamic_rnn

@@ -65,6 +65,8 @@ def build_parser():
                    "batch row")
     p.add_argument("--decode_lean", default=False, action="store_true", help="decode on an inference-only model (inference_only=True: "
                    "the generator alone, no BPTT stash)")
+    p.add_argument("--decode_push", type=int, default=0, help="decode with --decode_chunk: the live path -- every utterance arrives as pushes "
+                   "of this many raw frames through a StreamBank of --decode_streams rows (0: off)")
     p.add_argument("--device_features", type=str2bool, nargs="?", const=True, default=False, help="CMVN, context splice and padding on the "
                    "device (csrc/feat.hip): the reader ships packed raw frames and an offset table instead of the expanded batch; "
                    "training, cross-validation and --decode; the same numbers bit for bit")
@@ -169,6 +171,9 @@ def train(FLAGS, model_factory=None, log=print, net_overrides=None):
 def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
     """decode (:204-302): batch 1, G(x), de-normalise with the label CMVN, write feats.ark / feats.scp."""
     chunk, streams = int(getattr(FLAGS, "decode_chunk", 0) or 0), max(1, int(getattr(FLAGS, "decode_streams", 1) or 1))
+    push = int(getattr(FLAGS, "decode_push", 0) or 0)
+    if push < 0 or (push > 0 and chunk <= 0):
+        raise SystemExit("--decode_push needs a positive value and --decode_chunk")
     # (--decode_chunk N: the handle holds N frames of `streams` rows; an utterance is a sequence of calls that carry the state)
     mk = model_factory or (lambda: GAN_RNN(None, argparse.Namespace(**dict(vars(FLAGS), batch_size=streams if chunk > 0 else 1)),
                                            ["gpu:%d" % rdist.rank()], cross_validation=True, infer=True,
@@ -189,6 +194,27 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
     reader = ArkReader()
     reader(FLAGS.test_inputs_scp)
     start = datetime.datetime.now()
+    denorm = lambda a: a * cmvn["stddev_labels"] + cmvn["mean_labels"] if cmvn is not None else a
+
+    def write_all(outs, post):
+        """one matrix per utterance, in scp order"""
+        for i, (utt, activations) in enumerate(zip(reader.utt_ids, outs)):
+            writer.write_next_utt(write_ark_path, utt, post(np.asarray(activations)))
+            log("[{}/{}] Write inferred {} to {}".format(i + 1, len(reader.utt_ids), utt, write_ark_path))
+        writer.close()
+        log("Decoding time is {}s".format((datetime.datetime.now() - start).total_seconds()))
+        return write_scp_path
+
+    if push > 0:
+        # --decode_push N: the live path.  The raw utterance arrives N frames at a time on one row of a StreamBank, which owns CMVN, the
+        # splice and the de-normalising (on the device with --device_features)
+        from .stream import StreamBank, decode_live
+        try:
+            bank = StreamBank(model, cmvn, FLAGS.left_context, FLAGS.right_context, chunk, streams,
+                              device_features=bool(getattr(FLAGS, "device_features", False)))
+        except ValueError as e:
+            raise SystemExit("--decode_push: %s" % e)
+        return write_all(decode_live(bank, (reader.read_utt_data_from_index(i) for i in range(len(reader.utt_ids))), push), lambda a: a)
 
     def features(i):
         x = reader.read_utt_data_from_index(i).astype(np.float64)
@@ -197,12 +223,19 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
         return splice_feats(x, FLAGS.left_context, FLAGS.right_context).astype(np.float32)
 
     host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    finish = None
     if getattr(FLAGS, "device_features", False):
         # --device_features: the raw utterance travels, CMVN and the splice run on the device (HipEngine.featurize) and the generator reads
-        # the device tensor; the same bits as features() above.  De-normalising the output_dim-wide result stays on the host.
+        # the device tensor; the same bits as features() above.  The output is de-normalised on the device as well (HipEngine.denormalize,
+        # rsrgan_feat_denorm: the product and the sum rounded separately, NumPy's bits) and comes back as the float64 matrix that is written.
         featurize = getattr(getattr(model, "engine", None), "featurize", None)
-        if featurize is None:
-            raise SystemExit("--device_features needs an engine with a device-side front end (HipEngine.featurize)")
+        denormalize = getattr(getattr(model, "engine", None), "denormalize", None)
+        if featurize is None or denormalize is None:
+            raise SystemExit("--device_features needs an engine with a device-side front end (HipEngine.featurize, HipEngine.denormalize)")
+        if cmvn is not None:
+            label_stats = tuple(np.ascontiguousarray(cmvn[k], np.float64).reshape(-1) for k in ("mean_labels", "stddev_labels"))
+            finish = lambda y: denormalize(y, *label_stats)
+            denorm = lambda a: a                                             # (done where the activations were)
         stats = (None, None) if cmvn is None else tuple(np.ascontiguousarray(cmvn[k], np.float64).reshape(-1)
                                                         for k in ("mean_inputs", "stddev_inputs"))
 
@@ -213,19 +246,12 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
 
     if chunk > 0:
         from .stream import decode_streams
-        outs = decode_streams(model, (features(i) for i in range(len(reader.utt_ids))), chunk, streams)
-        for i, (utt, activations) in enumerate(zip(reader.utt_ids, outs)):         # (in scp order, as the loop below writes them)
-            activations = np.asarray(activations)
-            sequence = activations * cmvn["stddev_labels"] + cmvn["mean_labels"] if cmvn is not None else activations
-            writer.write_next_utt(write_ark_path, utt, sequence)
-            log("[{}/{}] Write inferred {} to {}".format(i + 1, len(reader.utt_ids), utt, write_ark_path))
-        writer.close()
-        log("Decoding time is {}s".format((datetime.datetime.now() - start).total_seconds()))
-        return write_scp_path
+        outs = decode_streams(model, (features(i) for i in range(len(reader.utt_ids))), chunk, streams, finish=finish)
+        return write_all(outs, denorm)                                             # (in scp order, as the loop below writes them)
     for i, utt in enumerate(reader.utt_ids):
         x = features(i)[None]
-        activations = host(model.forward(x, np.array([x.shape[1]], np.int32)))
-        sequence = activations * cmvn["stddev_labels"] + cmvn["mean_labels"] if cmvn is not None else activations
+        activations = model.forward(x, np.array([x.shape[1]], np.int32))
+        sequence = denorm(host(finish(activations) if finish is not None else activations))
         writer.write_next_utt(write_ark_path, utt, np.vstack(sequence))
         log("[{}/{}] Write inferred {} to {}".format(i + 1, len(reader.utt_ids), utt, write_ark_path))
     writer.close()

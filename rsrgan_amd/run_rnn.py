@@ -54,6 +54,8 @@ def build_parser():
     p.add_argument("--decode_streams", type=int, default=1, help="decode with --decode_chunk: utterances decoded side by side")
     p.add_argument("--decode_lean", default=False, action="store_true", help="decode on an inference-only model (inference_only=True: "
                    "the generator alone, no BPTT stash; --g_type bnlstm with --decode_chunk always decodes on it)")
+    p.add_argument("--decode_push", type=int, default=0, help="decode with --decode_chunk: the live path, pushes of this many raw frames "
+                   "(run_gan_rnn --decode_push)")
     p.add_argument("--device_features", type=str2bool, nargs="?", const=True, default=False, help="CMVN, context splice and padding on the "
                    "device (run_gan_rnn --device_features)")
     return p
