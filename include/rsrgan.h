@@ -310,6 +310,8 @@ int rsrgan_profile_launches(rsrgan_handle h, int64_t* n);
 int rsrgan_op_launch_floor(int32_t n, int32_t mode, double* us_per_launch, void* stream);
 
 /* ---- low-level operator entry points (unit parity tests + micro-benchmarks) ----
+ * Every rsrgan_op_* entry of this header is csrc/capi_ops.cpp's, apart from the product's ABI in csrc/capi.cpp; none takes a handle.
+ * Python reaches them through rsrgan_amd.ops.OpEntries.
  * C[M,N] = op(A)*op(B) (+bias) with fp32 MFMA.  a_kcontig: A is [M,K] row-major
  * (else stored [K,M]); b_kcontig: B is stored [N,K] (else [K,N] row-major).
  * All leading dimensions must be multiples of 4 floats, pointers 16-byte aligned.

@@ -627,8 +627,8 @@ BIG = case(8192 * 64 + 53, 64, "narrow", ex=(0, 0, 0), want=dict(egrid=8192, sli
 
 @pytest.fixture(scope="module")
 def eng():
-    from rsrgan_amd.engine_hip import HipEngine
-    return HipEngine(batch_size=2, max_frames=4, input_dim=9, output_dim=5, g_layers=1, g_cells=8, g_proj=8, d_layers=1, d_cells=8, d_proj=4)
+    from rsrgan_amd.ops import OpEntries
+    return OpEntries()
 
 
 @pytest.fixture(autouse=True)
@@ -809,9 +809,9 @@ def worker_main():
     """exit status 0: passed; CHILD_CHECK_FAILED: an assertion failed (the card is fine); any other exception -- a HIP error out of an
     entry or of the synchronize is one -- leaves with the interpreter's status 1, which the parent treats like an abort or a time-out"""
     import traceback
-    from rsrgan_amd.engine_hip import HipEngine
+    from rsrgan_amd.ops import OpEntries
     try:
-        e = HipEngine(batch_size=2, max_frames=4, input_dim=9, output_dim=5, g_layers=1, g_cells=8, g_proj=8, d_layers=1, d_cells=8, d_proj=4)
+        e = OpEntries()
         for c in CHILD:
             run_case(e, c, setting="narrow=1")
     except AssertionError:

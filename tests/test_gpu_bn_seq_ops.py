@@ -237,8 +237,8 @@ CASES = [(c, s, a, m) for c in COLS for s in SHAPES for a in ALPHAS for m in MOD
 
 @pytest.fixture(scope="module")
 def eng():
-    from rsrgan_amd.engine_hip import HipEngine
-    return HipEngine(batch_size=2, max_frames=4, input_dim=9, output_dim=5, g_layers=1, g_cells=8, g_proj=8, d_layers=1, d_cells=8, d_proj=4)
+    from rsrgan_amd.ops import OpEntries
+    return OpEntries()
 
 
 @pytest.fixture(autouse=True)

@@ -2,8 +2,8 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sys, time
 import torch
-from rsrgan_amd.engine_hip import HipEngine
-eng = HipEngine(batch_size=2, max_frames=4, input_dim=9, output_dim=5, g_layers=1, g_cells=8, g_proj=8, d_layers=1, d_cells=8, d_proj=4)
+from rsrgan_amd.ops import OpEntries
+eng = OpEntries()
 dev = eng.device
 def run(M, N, K, akc, bkc, reps=20):
     A = torch.randn((M, K) if akc else (K, M), device=dev); B = torch.randn((N, K) if bkc else (K, N), device=dev)
