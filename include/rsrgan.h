@@ -607,6 +607,39 @@ int rsrgan_op_update(int32_t op, const void* const* ptrs, const int64_t* dims, c
  * op 7 launch_dropout_bwd: ptrs y, d;  dims rows, cols, ld;  fl keep
  * op 8 launch_lrelu_bwd:   ptrs h, d;  dims rows, cols, ld;  fl alpha */
 int rsrgan_op_step_elem(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream);
+/* the layout, staging and weight-copy kernels (csrc/kernels.hip; tests/test_gpu_layout_ops.py, tests/test_layout_op_args.py): every one
+ * a copy, a single fp32 add or one fixed-order fp32 sum, so the tests ask for equal bits.  The list ops (2, 6, 7, 11, 13) build the
+ * launcher's job struct from dims and ptrs and name an argument "<name> of job <j>".  RSRGAN_ERR_INVALID before the first HIP call,
+ * rsrgan_last_error() naming it, for: a null table or required pointer; a size below 1 (below 0 where 0 is a no-op: rows of op 11, n of
+ * op 12; an offset, row0, slot, t0, Tw, dim, I, P, kx, c0); a leading dimension below its row; Bt outside 0 .. B; rows [row0, row0 + B)
+ * outside Ns; a list longer than the launcher's struct (16 transposes, 24 swizzles, 32 buffers, 4 layers); op 7: a dst that is not 16-byte
+ * aligned, gates outside 0 .. 4, with gates >= 1 nct below gates x ceil(H / 16) (the logical matrix must cover the source); ops 8, 9: M
+ * no multiple of S x W, ldk below kh x kw x C; op 8 where C % 4 == 0 and ldc % 4 == 0 (the float4 form): src or col not 16-byte aligned,
+ * row_stride or ldk no multiple of 4; op 9: dcol or dst not 16-byte aligned, C, ldc or ldk no multiple of 4; op 10: a dst that is not
+ * 16-byte aligned; op 11: dir outside 0 .. 2, a layer whose off + H + P exceeds SF.
+ * op 0 launch_pack_tm:         ptrs src, dst;  dims B, T, D, ld
+ * op 1 launch_unpack_bm:       ptrs src, dst;  dims B, T, D, ld, Bt (0: all B rows)
+ * op 2 launch_stage_inputs:    ptrs (src, dst) of pack 0, pack 1, copy 0 .. 3 (a NULL src skips the slot);  dims B, T, Bt, D0, ld0, D1, ld1,
+ *                              n0 .. n3 (32-bit words of each copy)
+ * op 3 launch_build_d_input:   ptrs lab (NULL without with_real), y, nr?, nf?, xd;  dims B, T, D, ld, with_real
+ * op 4 launch_add_noise_rows:  ptrs src, noise?, dst;  dims B, T, D, ld, Ns, row0
+ * op 5 launch_transpose:       ptrs src, dst;  dims lds, ldd, R, C
+ * op 6 launch_transpose_many:  ptrs (src, dst) per job;  dims n (1 .. 16), then lds, ldd, R, C per job
+ * op 7 launch_swizzle_many:    ptrs (src, dst) per job;  dims n (1 .. 24), then ld, gates, H, C, c0, K1, I, P, kx, nct, nkb per job (csrc/kernels.h
+ *                              SwizzleJob; dst [nct * nkb * 256])
+ * op 8 launch_im2col:          ptrs src, col;  dims row_stride, ldc, C, S, W, kh, kw, ldk, M
+ * op 9 launch_col2im:          ptrs dcol, dst;  dims ldk, C, S, W, kh, kw, ldc, M
+ * op 10 launch_expand_c4:      ptrs src, dst;  dims ld_src, n, rows
+ * op 11 launch_gstate:         ptrs state, mask? (int32), then (c, mst) per layer (unused by dir 2; mst NULL where ldP = 0);  dims nl (1 .. 4), SF,
+ *                              rows, dir, slot, then H, P, ldP, off per layer
+ * op 12 launch_window_len:     ptrs len, dst (int32);  dims n, t0, Tw
+ * op 13 launch_zero_many:      ptrs p per buffer;  dims n (1 .. 32), then the floats of each
+ * op 14 launch_fill:           ptrs p;  dims n;  fl v
+ * op 15 launch_build_joint:    ptrs x (NULL with dim = 0), tail, joint;  dims ldx, off, dim, ldt, Dt, ldj, row0, R
+ * op 16 launch_slice_cols:     ptrs src, dst;  dims lds, off, ldd, R, C
+ * op 17 launch_pad_copy:       ptrs dense, padded;  dims rows, cols, ld, to_padded
+ * op 18 launch_copy_f:         ptrs src, dst;  dims n */
+int rsrgan_op_layout(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream);
 
 /* ---- SEGAN-style conv G/D (models/segan.py:SEGAN with generator.py:AEGenerator, discriminator.py:discriminator, utils/bnorm.py:VBN;
  * BASELINE.json configs[4]).  The reference's trainer cannot run as shipped (segan.py:136 calls an undefined variables_on_gpu0(),

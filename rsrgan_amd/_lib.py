@@ -33,7 +33,7 @@ SYMBOLS = ["rsrgan_default_cfg", "rsrgan_create", "rsrgan_destroy", "rsrgan_last
            "rsrgan_feat_stream", "rsrgan_feat_denorm",
            "rsrgan_op_segan_sizes", "rsrgan_op_segan_conv2", "rsrgan_op_segan_conv1", "rsrgan_op_segan_colred", "rsrgan_op_segan_last_plan",
            "rsrgan_op_segan_vbn", "rsrgan_op_segan_elem", "rsrgan_op_segan_dhead",
-           "rsrgan_op_chunks", "rsrgan_op_update", "rsrgan_op_step_elem",
+           "rsrgan_op_chunks", "rsrgan_op_update", "rsrgan_op_step_elem", "rsrgan_op_layout",
            "rsrgan_segan_default_cfg", "rsrgan_segan_create", "rsrgan_segan_destroy", "rsrgan_segan_set_scalar",
            "rsrgan_segan_num_tensors", "rsrgan_segan_tensor_info", "rsrgan_segan_param_count", "rsrgan_segan_get_params",
            "rsrgan_segan_set_params", "rsrgan_segan_forward_g", "rsrgan_segan_d_backward", "rsrgan_segan_g_backward",
@@ -138,7 +138,7 @@ def load():
     lib.rsrgan_op_bn_last_plan.argtypes = [C.POINTER(i32)]
     lib.rsrgan_op_segan_sizes.argtypes = [i32, C.POINTER(i64), C.POINTER(i64)]
     for f in (lib.rsrgan_op_segan_conv2, lib.rsrgan_op_segan_conv1, lib.rsrgan_op_segan_colred, lib.rsrgan_op_segan_vbn, lib.rsrgan_op_segan_elem,
-              lib.rsrgan_op_segan_dhead, lib.rsrgan_op_update, lib.rsrgan_op_step_elem):
+              lib.rsrgan_op_segan_dhead, lib.rsrgan_op_update, lib.rsrgan_op_step_elem, lib.rsrgan_op_layout):
         f.argtypes = [i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_float), vp]
     lib.rsrgan_op_segan_last_plan.argtypes = [C.POINTER(i32)]
     lib.rsrgan_op_chunks.argtypes = [C.POINTER(i64), i32, C.POINTER(i32), i64, C.POINTER(i32)]
@@ -186,6 +186,9 @@ SEGAN_OPS = {"conv2": ("conv2_fwd", "conv2_wgrad", "tconv2"), "conv1": ("conv1_f
 # rsrgan_op_update / rsrgan_op_step_elem: the op codes, and the slots of the device scalars `dyn` (csrc/kernels.h DYN_*)
 UPDATE_OPS = ("sumsq", "dw_reduce", "l2", "apply_sgd", "apply_adam")
 STEP_ELEM_OPS = ("lsgan", "dhead", "mse", "g_total", "l2_total", "adam_tick", "dropout_fwd", "dropout_bwd", "lrelu_bwd")
+# rsrgan_op_layout: the op codes (one per launch_* function of the layout, staging and weight-copy kernels)
+LAYOUT_OPS = ("pack_tm", "unpack_bm", "stage_inputs", "build_d_input", "add_noise_rows", "transpose", "transpose_many", "swizzle_many", "im2col",
+              "col2im", "expand_c4", "gstate", "window_len", "zero_many", "fill", "build_joint", "slice_cols", "pad_copy", "copy_f")
 DYN_SLOTS = {"g_lr": 0, "d_lr": 1, "lambda": 2, "d_real": 3, "d_fake": 4, "l2": 5, "clip": 6, "beta1": 7, "beta2": 8, "eps": 9, "ema": 10,
              "adam_lrt": 11, "adam_lrt_d": 12}
 DYN_COUNT = 16

@@ -1,6 +1,6 @@
 // capi_ops.cpp -- the unit-test operator entries of include/rsrgan.h (rsrgan_op_*): the model's own host launch functions on
 // caller-owned buffers, no handle.  First the positional-argument entries (launch floor, gemm, column sums, bnl_fold, conv, bn), then
-// the table-form ones (op, ptrs, dims, fl: segan, chunks, update, step_elem).  The product's entries are capi.cpp's.
+// the table-form ones (op, ptrs, dims, fl: segan, chunks, update, step_elem, layout).  The product's entries are capi.cpp's.
 #include "capi_common.h"
 
 extern "C" {
@@ -929,5 +929,229 @@ int rsrgan_op_step_elem(int32_t op, const void* const* ptrs, const int64_t* dims
   OP_LAUNCHED(WHO);
 }
 #undef WHO
+
+// ---- unit-test entry of the layout, staging and weight-copy kernels (kernels.hip: the batch-major <-> time-major packs, the
+// discriminator's input rows, the transposed and fragment-tiled weight copies, R-CED's patch matrix and its adjoint, the carried state,
+// the small buffer kernels) on caller-owned buffers (tests/test_gpu_layout_ops.py, test_layout_op_args.py).  Same form as the entries
+// above; the list ops name a job's argument as "<name> of job <j>".
+#define OP_JOB_NAME(buf, name, j) char buf[48]; snprintf(buf, sizeof(buf), "%s of job %d", name, (int)(j))
+#define WHO "op_layout"
+int rsrgan_op_layout(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream) {
+  OP_REFUSE(!ptrs || !dims, WHO ": null table (ptrs or dims)");
+  OP_REFUSE(op < 0 || op > 18, WHO ": op = %d outside 0 .. 18", op);
+  OP_REFUSE(op == 14 && !fl, WHO ": null table (fl: the fill value)");
+  const int64_t* d = dims;
+  const int64_t lim = (int64_t)1 << 30;
+  hipStream_t s = (hipStream_t)stream;
+  switch (op) {
+    case 0: case 1: {                                    // pack_tm / unpack_bm: ptrs src, dst;  dims B, T, D, ld (+ Bt)
+      OP_DIM("B", d[0], 1); OP_DIM("T", d[1], 1); OP_DIM("D", d[2], 1); OP_LD("ld", d[3], d[2]);
+      OP_REFUSE(d[0] * d[1] * d[3] > lim || d[0] > 65535, WHO ": B x T x ld above the entry's 2^30, or B above the grid's 65535");
+      if (op == 1) OP_REFUSE(d[4] < 0 || d[4] > d[0], WHO ": Bt = %lld outside 0 (all rows) .. B = %lld", (long long)d[4], (long long)d[0]);
+      OP_PTR("src", ptrs[0], 4); OP_PTR("dst", ptrs[1], 4);
+      if (op == 0) launch_pack_tm(FP(0), FP(1), (int)d[0], (int)d[1], (int)d[2], (int)d[3], s);
+      else launch_unpack_bm(FP(0), (int)d[3], FP(1), (int)d[0], (int)d[1], (int)d[2], s, (int)d[4]);
+      break;
+    }
+    case 2: {                                            // stage_inputs: ptrs (src, dst) of pack 0, 1, of copy 0 .. 3;  dims B, T, Bt, D0, ld0, D1, ld1, n0 .. n3
+      OP_DIM("B", d[0], 1); OP_DIM("T", d[1], 1);
+      OP_REFUSE(d[0] > 65535, WHO ": B = %lld above the grid's 65535", (long long)d[0]);
+      OP_REFUSE(d[2] < 0 || d[2] > d[0], WHO ": Bt = %lld outside 0 (all rows) .. B = %lld", (long long)d[2], (long long)d[0]);
+      StageJobs j{};
+      j.B = (int)d[0]; j.T = (int)d[1]; j.Bt = (int)d[2];
+      for (int k = 0; k < 2; ++k) {
+        if (!ptrs[2 * k]) continue;                      // (a NULL src skips the slot: its dst and sizes are not looked at)
+        OP_JOB_NAME(ns, "src", k); OP_JOB_NAME(nd, "dst", k); OP_JOB_NAME(nD, "D", k); OP_JOB_NAME(nl, "ld", k);
+        OP_PTR(ns, ptrs[2 * k], 4); OP_PTR(nd, ptrs[2 * k + 1], 4);
+        OP_DIM(nD, d[3 + 2 * k], 1); OP_LD(nl, d[4 + 2 * k], d[3 + 2 * k]);
+        OP_REFUSE(d[0] * d[1] * d[4 + 2 * k] > lim, WHO ": B x T x ld of pack %d above the entry's 2^30", k);
+        j.pack[k] = StagePack{FP(2 * k), FP(2 * k + 1), (int)d[3 + 2 * k], (int)d[4 + 2 * k]};
+      }
+      for (int k = 0; k < 4; ++k) {
+        if (!ptrs[4 + 2 * k]) continue;
+        OP_JOB_NAME(ns, "copy src", k); OP_JOB_NAME(nd, "copy dst", k); OP_JOB_NAME(nn, "n", k);
+        OP_PTR(ns, ptrs[4 + 2 * k], 4); OP_PTR(nd, ptrs[5 + 2 * k], 4); OP_DIM(nn, d[7 + k], 1);
+        j.copy[k] = StageCopy{ptrs[4 + 2 * k], (void*)ptrs[5 + 2 * k], (int)d[7 + k]};
+      }
+      launch_stage_inputs(j, s);
+      break;
+    }
+    case 3: {                                            // build_d_input: ptrs lab (with_real), y, nr?, nf?, xd;  dims B, T, D, ld, with_real
+      OP_DIM("B", d[0], 1); OP_DIM("T", d[1], 1); OP_DIM("D", d[2], 1); OP_LD("ld", d[3], d[2]); OP_FLAG("with_real", d[4]);
+      OP_REFUSE(2 * d[0] * d[1] * d[3] > lim, WHO ": 2 B x T x ld above the entry's 2^30");
+      if (d[4]) OP_PTR("lab", ptrs[0], 4); else OP_OPT("lab", ptrs[0], 4);
+      OP_PTR("y", ptrs[1], 4); OP_OPT("nr", ptrs[2], 4); OP_OPT("nf", ptrs[3], 4); OP_PTR("xd", ptrs[4], 4);
+      launch_build_d_input(FP(0), FP(1), FP(2), FP(3), FP(4), (int)d[0], (int)d[1], (int)d[2], (int)d[3], d[4] != 0, s);
+      break;
+    }
+    case 4: {                                            // add_noise_rows: ptrs src, noise?, dst;  dims B, T, D, ld, Ns, row0
+      OP_DIM("B", d[0], 1); OP_DIM("T", d[1], 1); OP_DIM("D", d[2], 1); OP_LD("ld", d[3], d[2]); OP_DIM("Ns", d[4], 1); OP_DIM("row0", d[5], 0);
+      OP_REFUSE(d[5] + d[0] > d[4], WHO ": rows [row0 = %lld, row0 + B = %lld) outside Ns = %lld", (long long)d[5], (long long)(d[5] + d[0]), (long long)d[4]);
+      OP_REFUSE(d[4] * d[1] * d[3] > lim, WHO ": Ns x T x ld above the entry's 2^30");
+      OP_PTR("src", ptrs[0], 4); OP_OPT("noise", ptrs[1], 4); OP_PTR("dst", ptrs[2], 4);
+      launch_add_noise_rows(FP(0), FP(1), FP(2), (int)d[0], (int)d[1], (int)d[2], (int)d[3], (int)d[4], (int)d[5], s);
+      break;
+    }
+    case 5: {                                            // transpose: ptrs src, dst;  dims lds, ldd, R, C
+      OP_DIM("R", d[2], 1); OP_DIM("C", d[3], 1); OP_LD("lds", d[0], d[3]); OP_LD("ldd", d[1], d[2]);
+      OP_REFUSE(d[2] * d[0] > lim || d[3] * d[1] > lim || d[2] > (65535 << 5), WHO ": R x lds or C x ldd above the entry's 2^30, or R above the grid's 65535 tiles");
+      OP_PTR("src", ptrs[0], 4); OP_PTR("dst", ptrs[1], 4);
+      launch_transpose(FP(0), (int)d[0], FP(1), (int)d[1], (int)d[2], (int)d[3], s);
+      break;
+    }
+    case 6: {                                            // transpose_many: ptrs (src, dst) per job;  dims n, then lds, ldd, R, C per job
+      TransposeList tl{};
+      OP_REFUSE(d[0] < 1 || d[0] > (int64_t)(sizeof(tl.j) / sizeof(tl.j[0])), WHO ": n = %lld jobs outside the list (1 .. %d)", (long long)d[0],
+                (int)(sizeof(tl.j) / sizeof(tl.j[0])));
+      tl.n = (int)d[0];
+      for (int j = 0; j < tl.n; ++j) {
+        const int64_t* q = d + 1 + 4 * j;
+        OP_JOB_NAME(ns, "src", j); OP_JOB_NAME(nd, "dst", j); OP_JOB_NAME(nR, "R", j); OP_JOB_NAME(nC, "C", j); OP_JOB_NAME(n0, "lds", j); OP_JOB_NAME(n1, "ldd", j);
+        OP_DIM(nR, q[2], 1); OP_DIM(nC, q[3], 1); OP_LD(n0, q[0], q[3]); OP_LD(n1, q[1], q[2]);
+        OP_REFUSE(q[2] * q[0] > ((int64_t)1 << 26) || q[3] * q[1] > ((int64_t)1 << 26), WHO ": R x lds or C x ldd of job %d above the entry's 2^26", j);
+        OP_PTR(ns, ptrs[2 * j], 4); OP_PTR(nd, ptrs[2 * j + 1], 4);
+        tl.j[j] = TransposeJob{FP(2 * j), FP(2 * j + 1), (int)q[0], (int)q[1], (int)q[2], (int)q[3], 0};
+      }
+      launch_transpose_many(tl, s);
+      break;
+    }
+    case 7: {                                            // swizzle_many: ptrs (src, dst) per job;  dims n, then ld, gates, H, C, c0, K1, I, P, kx, nct, nkb per job
+      SwizzleList sl{};
+      OP_REFUSE(d[0] < 1 || d[0] > (int64_t)(sizeof(sl.j) / sizeof(sl.j[0])), WHO ": n = %lld jobs outside the list (1 .. %d)", (long long)d[0],
+                (int)(sizeof(sl.j) / sizeof(sl.j[0])));
+      sl.n = (int)d[0];
+      for (int j = 0; j < sl.n; ++j) {
+        const int64_t* q = d + 1 + 11 * j;
+        const int64_t ld = q[0], gates = q[1], H = q[2], C_ = q[3], c0 = q[4], K1 = q[5], I = q[6], P = q[7], kx = q[8], nct = q[9], nkb = q[10];
+        OP_JOB_NAME(ns, "src", j); OP_JOB_NAME(nd, "dst", j); OP_JOB_NAME(nl, "ld", j); OP_JOB_NAME(nn, "nct", j); OP_JOB_NAME(nk, "nkb", j);
+        OP_DIM(nn, nct, 1); OP_DIM(nk, nkb, 1);
+        OP_REFUSE(nct * nkb > ((int64_t)1 << 20), WHO ": nct x nkb of job %d above the entry's 2^20 tiles", j);
+        OP_REFUSE(gates < 0 || gates > 4, WHO ": gates = %lld of job %d outside 0 (rows of a k-contiguous matrix) .. 4", (long long)gates, j);
+        if (gates == 0) {
+          OP_JOB_NAME(nC, "C", j); OP_JOB_NAME(n0, "c0", j); OP_JOB_NAME(nK, "K1", j);
+          OP_DIM(nC, C_, 1); OP_DIM(n0, c0, 0); OP_DIM(nK, K1, 1); OP_LD(nl, ld, K1);
+          OP_REFUSE((c0 + C_) * ld > lim, WHO ": (c0 + C) x ld of job %d above the entry's 2^30", j);
+        } else {
+          OP_JOB_NAME(nH, "H", j); OP_JOB_NAME(nI, "I", j); OP_JOB_NAME(nP, "P", j); OP_JOB_NAME(nx, "kx", j);
+          OP_DIM(nH, H, 1); OP_DIM(nI, I, 0); OP_DIM(nP, P, 0); OP_DIM(nx, kx, 0); OP_LD(nl, ld, gates * H);
+          OP_REFUSE(I + P < 1 || (I + P) * ld > lim, WHO ": I + P = %lld source rows of job %d below 1, or (I + P) x ld above the entry's 2^30", (long long)(I + P), j);
+          OP_REFUSE(nct < gates * ((H + 15) / 16), WHO ": nct = %lld of job %d below gates x ceil(H / 16) = %lld: the logical matrix must cover the source",
+                    (long long)nct, j, (long long)(gates * ((H + 15) / 16)));
+        }
+        OP_PTR(ns, ptrs[2 * j], 4); OP_PTR(nd, ptrs[2 * j + 1], 16);
+        sl.j[j] = SwizzleJob{FP(2 * j), FP(2 * j + 1), (int)ld, (int)gates, (int)H, (int)C_, (int)c0, (int)K1, (int)I, (int)P, (int)kx, (int)nct, (int)nkb, 0};
+      }
+      launch_swizzle_many(sl, s);
+      break;
+    }
+    case 8: case 9: {                                    // im2col: ptrs src, col;  dims row_stride, ldc, C, S, W, kh, kw, ldk, M
+      // col2im: ptrs dcol, dst;  dims ldk, C, S, W, kh, kw, ldc, M
+      const int64_t rs = op == 8 ? d[0] : 0, ldc = op == 8 ? d[1] : d[6], C_ = op == 8 ? d[2] : d[1], S = op == 8 ? d[3] : d[2], W = op == 8 ? d[4] : d[3],
+                    kh = op == 8 ? d[5] : d[4], kw = op == 8 ? d[6] : d[5], ldk = op == 8 ? d[7] : d[0], M = op == 8 ? d[8] : d[7];
+      OP_DIM("C", C_, 1); OP_DIM("S", S, 1); OP_DIM("W", W, 1); OP_DIM("kh", kh, 1); OP_DIM("kw", kw, 1); OP_DIM("M", M, 1);
+      OP_REFUSE(kh * kw * C_ > ((int64_t)1 << 24), WHO ": kh x kw x C above the entry's 2^24");
+      OP_REFUSE(M % (S * W), WHO ": M = %lld positions are no whole frames of S x W = %lld", (long long)M, (long long)(S * W));
+      OP_LD("ldc", ldc, C_); OP_LD("ldk", ldk, kh * kw * C_);
+      OP_REFUSE(M * ldk > lim || M * ldc > lim, WHO ": M x ldk or M x ldc above the entry's 2^30");
+      if (op == 8) {
+        OP_LD("row_stride", rs, (S * W - 1) * ldc + C_);
+        const int al = (C_ % 4 == 0 && ldc % 4 == 0) ? 16 : 4;      // launch_im2col's float4 form looks at C and ldc alone
+        if (al == 16) { OP_MUL4("row_stride", rs); OP_MUL4("ldk", ldk); }
+        OP_PTR("src", ptrs[0], al); OP_PTR("col", ptrs[1], al);
+        launch_im2col(FP(0), (size_t)rs, (int)ldc, (int)C_, (int)S, (int)W, (int)kh, (int)kw, FP(1), (int)ldk, (size_t)M, s);
+      } else {
+        OP_MUL4("C", C_); OP_MUL4("ldc", ldc); OP_MUL4("ldk", ldk);
+        OP_PTR("dcol", ptrs[0], 16); OP_PTR("dst", ptrs[1], 16);
+        launch_col2im(FP(0), (int)ldk, (int)C_, (int)S, (int)W, (int)kh, (int)kw, FP(1), (int)ldc, (size_t)M, s);
+      }
+      break;
+    }
+    case 10: {                                           // expand_c4: ptrs src, dst;  dims ld_src, n, rows
+      OP_DIM("n", d[1], 1); OP_DIM("rows", d[2], 1); OP_LD("ld_src", d[0], d[1]);
+      OP_REFUSE(d[2] * d[0] > lim || d[2] * d[1] * 4 > lim, WHO ": rows x ld_src or rows x n x 4 above the entry's 2^30");
+      OP_PTR("src", ptrs[0], 4); OP_PTR("dst", ptrs[1], 16);
+      launch_expand_c4(FP(0), (int)d[0], (int)d[1], FP(1), (size_t)d[2], s);
+      break;
+    }
+    case 11: {                                           // gstate: ptrs state, mask?, then (c, mst) per layer;  dims nl, SF, rows, dir, slot, then H, P, ldP, off per layer
+      OP_REFUSE(d[0] < 1 || d[0] > GP_MAXL, WHO ": nl = %lld layers outside 1 .. %d", (long long)d[0], GP_MAXL);
+      OP_DIM("SF", d[1], 1); OP_DIM("rows", d[2], 0); OP_DIM("slot", d[4], 0);
+      OP_REFUSE(d[2] > 65535, WHO ": rows = %lld above the grid's 65535", (long long)d[2]);
+      OP_REFUSE(d[3] < 0 || d[3] > 2, WHO ": dir = %lld outside 0 (state -> slot), 1 (slot -> state), 2 (zero)", (long long)d[3]);
+      OP_PTR("state", ptrs[0], 4); OP_OPT("mask", ptrs[1], 4);
+      GStateArgs a{};
+      a.nl = (int)d[0]; a.SF = (int)d[1]; a.rows = (int)d[2]; a.dir = (int)d[3]; a.state = FP(0); a.slot = (size_t)d[4]; a.mask = (const int*)ptrs[1];
+      for (int l = 0; l < a.nl; ++l) {
+        const int64_t* q = d + 5 + 4 * l;
+        OP_JOB_NAME(nc, "c", l); OP_JOB_NAME(nm, "mst", l); OP_JOB_NAME(nH, "H", l); OP_JOB_NAME(nP, "P", l); OP_JOB_NAME(nl, "ldP", l);
+        OP_DIM(nH, q[0], 1); OP_DIM(nP, q[1], 0); OP_LD(nl, q[2], q[1]);
+        OP_REFUSE(q[3] < 0 || q[3] + q[0] + q[1] > d[1], WHO ": layer %d at offset %lld with H + P = %lld does not fit SF = %lld", l, (long long)q[3],
+                  (long long)(q[0] + q[1]), (long long)d[1]);
+        OP_REFUSE((d[4] + d[2]) * std::max(q[0], q[2]) > lim, WHO ": (slot + rows) x H or ldP of layer %d above the entry's 2^30", l);
+        if (a.dir < 2) {                                 // (dir 2 touches the state alone; a layer without a projection, ldP = 0, has no mst)
+          OP_PTR(nc, ptrs[2 + 2 * l], 4);
+          if (q[2] > 0) OP_PTR(nm, ptrs[3 + 2 * l], 4);
+        }
+        a.L[l] = GStateLayer{FP(2 + 2 * l), FP(3 + 2 * l), (int)q[0], (int)q[1], (int)q[2], (int)q[3]};
+      }
+      OP_REFUSE(d[2] * d[1] > lim, WHO ": rows x SF above the entry's 2^30");
+      launch_gstate(a, s);
+      break;
+    }
+    case 12: {                                           // window_len: ptrs len, dst (int32);  dims n, t0, Tw
+      OP_DIM("n", d[0], 0); OP_DIM("t0", d[1], 0); OP_DIM("Tw", d[2], 0);
+      OP_PTR("len", ptrs[0], 4); OP_PTR("dst", ptrs[1], 4);
+      launch_window_len((const int*)ptrs[0], (int*)ptrs[1], (int)d[0], (int)d[1], (int)d[2], s);
+      break;
+    }
+    case 13: {                                           // zero_many: ptrs p per buffer;  dims n, then the floats of each
+      ZeroList zl{};
+      OP_REFUSE(d[0] < 1 || d[0] > (int64_t)(sizeof(zl.p) / sizeof(zl.p[0])), WHO ": n = %lld buffers outside the list (1 .. %d)", (long long)d[0],
+                (int)(sizeof(zl.p) / sizeof(zl.p[0])));
+      zl.n = (int)d[0];
+      for (int j = 0; j < zl.n; ++j) {
+        OP_JOB_NAME(np_, "p", j); OP_JOB_NAME(nn, "len", j);
+        OP_DIM(nn, d[1 + j], 1); OP_PTR(np_, ptrs[j], 4);
+        zl.p[j] = FP(j); zl.len[j] = (unsigned)d[1 + j];
+      }
+      launch_zero_many(zl, s);
+      break;
+    }
+    case 14:                                             // fill: ptrs p;  dims n;  fl v
+      OP_DIM("n", d[0], 1); OP_PTR("p", ptrs[0], 4);
+      launch_fill(FP(0), (size_t)d[0], fl[0], s);
+      break;
+    case 15: {                                           // build_joint: ptrs x (dim > 0), tail, joint;  dims ldx, off, dim, ldt, Dt, ldj, row0, R
+      OP_DIM("off", d[1], 0); OP_DIM("dim", d[2], 0); OP_DIM("Dt", d[4], 1); OP_DIM("row0", d[6], 0); OP_DIM("R", d[7], 1);
+      if (d[2] > 0) { OP_LD("ldx", d[0], d[1] + d[2]); OP_PTR("x", ptrs[0], 4); } else OP_OPT("x", ptrs[0], 4);
+      OP_LD("ldt", d[3], d[4]); OP_LD("ldj", d[5], d[2] + d[4]);
+      OP_REFUSE((d[6] + d[7]) * d[5] > lim || d[7] * std::max(d[0], d[3]) > lim, WHO ": (row0 + R) x ldj, R x ldx or R x ldt above the entry's 2^30");
+      OP_PTR("tail", ptrs[1], 4); OP_PTR("joint", ptrs[2], 4);
+      launch_build_joint(FP(0), (int)d[0], (int)d[1], (int)d[2], FP(1), (int)d[3], (int)d[4], FP(2), (int)d[5], (int)d[6], (int)d[7], s);
+      break;
+    }
+    case 16: {                                           // slice_cols: ptrs src, dst;  dims lds, off, ldd, R, C
+      OP_DIM("off", d[1], 0); OP_DIM("R", d[3], 1); OP_DIM("C", d[4], 1); OP_LD("lds", d[0], d[1] + d[4]); OP_LD("ldd", d[2], d[4]);
+      OP_REFUSE(d[3] * std::max(d[0], d[2]) > lim, WHO ": R x lds or R x ldd above the entry's 2^30");
+      OP_PTR("src", ptrs[0], 4); OP_PTR("dst", ptrs[1], 4);
+      launch_slice_cols(FP(0), (int)d[0], (int)d[1], FP(1), (int)d[2], (int)d[3], (int)d[4], s);
+      break;
+    }
+    case 17: {                                           // pad_copy: ptrs dense, padded;  dims rows, cols, ld, to_padded
+      OP_DIM("rows", d[0], 1); OP_DIM("cols", d[1], 1); OP_LD("ld", d[2], d[1]); OP_FLAG("to_padded", d[3]);
+      OP_REFUSE(d[0] * d[2] > lim, WHO ": rows x ld above the entry's 2^30");
+      OP_PTR("dense", ptrs[0], 4); OP_PTR("padded", ptrs[1], 4);
+      launch_pad_copy(FP(0), FP(1), (int)d[0], (int)d[1], (int)d[2], d[3] != 0, s);
+      break;
+    }
+    default:                                             // copy_f: ptrs src, dst;  dims n
+      OP_DIM("n", d[0], 1); OP_PTR("src", ptrs[0], 4); OP_PTR("dst", ptrs[1], 4);
+      launch_copy_f(FP(0), FP(1), (int)d[0], s);
+      break;
+  }
+  OP_LAUNCHED(WHO);
+}
+#undef WHO
+#undef OP_JOB_NAME
 
 }  // extern "C"

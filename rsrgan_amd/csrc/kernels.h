@@ -338,6 +338,8 @@ void launch_pack_tm(const float* src_bm, float* dst_tm, int B, int T, int D, int
 void launch_unpack_bm(const float* src_tm, int ld, float* dst_bm, int B, int T, int D, hipStream_t s, int Bt = 0);    // [T][B][ld] -> [Bt or B,T,D]
 // xd[t][b] = labels[t][b] + noise_r[b]   (b <  B)   (only when with_real)
 // xd[t][B+b or b] = y[t][b] + noise_f[b]
+// One fp32 add per element here and in launch_add_noise_rows; a null noise adds +0.f (a -0.0 of the source comes out as +0.0).  Only
+// the D valid columns are written.
 void launch_build_d_input(const float* lab_tm, const float* y_tm, const float* noise_r, const float* noise_f,
                           float* xd, int B, int T, int D, int ld, bool with_real, hipStream_t s);
 // dst[t][row0 + b] = src[t][b] + noise[b]   for b < B; dst has Ns rows per time step

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import (BN_PLAN_FIELDS, BN_ROUTES, CONV_FAMILIES, CONV_FWD_BRANCHES, CONV_PLAN_FIELDS, CONV_WGRAD_BRANCHES, GEMM_CLASSES,
-                   GEMM_PLAN_FIELDS, SEGAN_OPS, SEGAN_PLAN_FIELDS, STEP_ELEM_OPS, UPDATE_OPS, check, ptr_table)
+                   GEMM_PLAN_FIELDS, LAYOUT_OPS, SEGAN_OPS, SEGAN_PLAN_FIELDS, STEP_ELEM_OPS, UPDATE_OPS, check, ptr_table)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -205,6 +205,19 @@ class OpEntries:
     def op_step_elem(self, op, ptrs, dims=(), fl=()):
         """rsrgan_op_step_elem, op by name (_lib.STEP_ELEM_OPS); ptrs: tensors or None, dims: ints (a dropout key: any 64-bit value), fl: floats"""
         check(self.lib.rsrgan_op_step_elem(STEP_ELEM_OPS.index(op), *self._tables(ptrs, dims, fl), self._stream()))
+
+    def op_layout(self, op, ptrs, dims=(), fl=()):
+        """rsrgan_op_layout, op by name (_lib.LAYOUT_OPS); ptrs: tensors or None, dims: ints, fl: floats (include/rsrgan.h)"""
+        check(self.lib.rsrgan_op_layout(LAYOUT_OPS.index(op), *self._tables(ptrs, dims, fl), self._stream()))
+
+    def device_status(self) -> int:
+        """the handle-free form of HipEngine.device_status: waits for the current stream; 0, or -2 (RSRGAN_ERR_HIP) where a launch or a
+        kernel of it failed"""
+        try:
+            torch.cuda.current_stream(self.device).synchronize()
+        except RuntimeError:
+            return -2
+        return 0
 
     def op_lstm_colsums(self, dz, cprev, ccur, db, dwi, dwf, dwo, rows, H):
         """lists of nb tensors each: dz [rows][4H], cprev / ccur [rows][H], db [>= 4H], dwi / dwf / dwo [>= H]"""
