@@ -507,6 +507,30 @@ int rsrgan_feat_stream(const float* fresh, int64_t fresh_rows, const int32_t* ta
  * 2^32 - 1 elements. */
 int rsrgan_feat_denorm(const float* y, const int32_t* lengths, int32_t B, int32_t T, int32_t D, const double* mean, const double* stddev,
                        double* out, void* stream);
+/* The archive side: decode a batch of utterances from their Kaldi archive encoding into NORMALISED float32 rows out [out_rows][D], one
+ * launch, no handle.  blob: the matrices' bytes as they lie in the file; seg [B][2] = (byte offset of utterance b's segment in blob, kind);
+ * scale [B][2] = (min, range), read for kind 2 only; offsets [B + 1]: utterance b has n_b = offsets[b + 1] - offsets[b] frames and goes
+ * to rows offsets[b] .. offsets[b + 1] - 1 of out.  Element (j, d), j < n_b, in IEEE double, no multiply-add:
+ *   kind 0 ('BFM ', float  [n][D] row-major):  x = (double)f32[j * D + d]
+ *   kind 1 ('BDM ', double [n][D] row-major):  x = f64[j * D + d]
+ *   kind 2 ('BCM ', Kaldi compressed format 1: 4 * D little-endian uint16 percentiles, then D * n bytes, column-major):
+ *            p_k = min + ((range * 1.52590218966964e-05) * (double)u16[4 * d + k])          k = 0 .. 3; min, range widened to double
+ *            v   = (double)byte[d * n + j]
+ *            x   = v <  64  ? p_0 + ((p_1 - p_0) *  v       ) * (1 / 64.0)
+ *                : v <= 192 ? p_1 + ((p_2 - p_1) * (v -  64)) * (1 / 128.0)
+ *                :            p_2 + ((p_3 - p_2) * (v - 192)) * (1 / 63.0)              (1 / 63.0: the rounded constant, multiplied)
+ *   out[offsets[b] + j][d] = mean ? (float)((x - mean[d]) / stddev[d]) : (float)x
+ * These are io.kaldi_ark's uint16_to_float and char_to_float, io.features.apply_cmvn and the reader's cast to float32: the results are
+ * equal to the host path's bit for bit; the decoded value is never rounded to float before it is normalised.  out is then an ordinary
+ * `raw` / `pool` for rsrgan_feat_batch / rsrgan_feat_frames with mean = stddev = NULL.  Rows of out that belong to no utterance are not
+ * written; n_b <= 0 writes nothing; an unknown kind writes +0.0.  Every byte index is clamped into [0, blob_bytes) and every destination
+ * row into [0, out_rows): the kernel reads and writes nothing outside its buffers, whatever the device-resident tables hold.  All
+ * pointers are DEVICE pointers; mean and stddev ([D] double) are both given or both NULL.  RSRGAN_ERR_INVALID before the first HIP call,
+ * rsrgan_last_error() naming the argument, for: a null blob, seg, offsets or out; a null scale (always required: the kinds are not
+ * visible to the host); only one of mean / stddev; blob or out not 16-byte aligned; seg, mean or stddev not 8-byte, scale or offsets not
+ * 4-byte aligned; B, D, blob_bytes or out_rows below 1; out_rows * D above 2^40. */
+int rsrgan_feat_decode(const uint8_t* blob, int64_t blob_bytes, const int64_t* seg, const float* scale, const int32_t* offsets, int32_t B,
+                       int32_t D, const double* mean, const double* stddev, float* out, int64_t out_rows, void* stream);
 
 /* ---- the SEGAN operators (csrc/segan.hip and the window-GEMM primitives of csrc/segan.cpp).  Unit parity tests only
  * (tests/test_gpu_segan_ops.py, tests/test_op_args.py); no trainer calls them.  Each goes through the host function SeganModel calls

@@ -30,7 +30,7 @@ SYMBOLS = ["rsrgan_default_cfg", "rsrgan_create", "rsrgan_destroy", "rsrgan_last
            "rsrgan_op_conv_fwd", "rsrgan_op_conv_wgrad", "rsrgan_op_conv_ws_floats", "rsrgan_op_conv_supported", "rsrgan_op_conv_last_plan",
            "rsrgan_op_bn_forward", "rsrgan_op_bn_backward", "rsrgan_op_bn_commit", "rsrgan_op_bn_last_plan",
            "rsrgan_op_bn_seq_forward", "rsrgan_op_bn_seq_backward", "rsrgan_feat_batch", "rsrgan_feat_frames",
-           "rsrgan_feat_stream", "rsrgan_feat_denorm",
+           "rsrgan_feat_stream", "rsrgan_feat_denorm", "rsrgan_feat_decode",
            "rsrgan_op_segan_sizes", "rsrgan_op_segan_conv2", "rsrgan_op_segan_conv1", "rsrgan_op_segan_colred", "rsrgan_op_segan_last_plan",
            "rsrgan_op_segan_vbn", "rsrgan_op_segan_elem", "rsrgan_op_segan_dhead",
            "rsrgan_op_chunks", "rsrgan_op_update", "rsrgan_op_step_elem", "rsrgan_op_layout",
@@ -134,6 +134,7 @@ def load():
     lib.rsrgan_feat_frames.argtypes = [p, i64, p, i32, i32, i32, i32, p, p, p, vp]
     lib.rsrgan_feat_stream.argtypes = [p, i64, p, p, i32, i32, i32, i32, i32, i32, p, p, p, p, vp]
     lib.rsrgan_feat_denorm.argtypes = [p, p, i32, i32, i32, p, p, p, vp]
+    lib.rsrgan_feat_decode.argtypes = [p, i64, p, p, p, i32, i32, p, p, p, i64, vp]
     lib.rsrgan_op_bn_commit.argtypes =[i32, pp, pp, C.POINTER(i32), i32, vp]
     lib.rsrgan_op_bn_last_plan.argtypes = [C.POINTER(i32)]
     lib.rsrgan_op_segan_sizes.argtypes = [i32, C.POINTER(i64), C.POINTER(i64)]

@@ -578,4 +578,21 @@ int rsrgan_feat_denorm(const float* y, const int32_t* lengths, int32_t B, int32_
   OP_LAUNCHED("feat_denorm");
 }
 
+int rsrgan_feat_decode(const uint8_t* blob, int64_t blob_bytes, const int64_t* seg, const float* scale, const int32_t* offsets, int32_t B, int32_t D,
+                       const double* mean, const double* stddev, float* out, int64_t out_rows, void* stream) {
+  OP_REFUSE(!blob || !seg || !offsets || !out, "feat_decode: null pointer (blob, seg, offsets or out)");
+  OP_REFUSE(!scale, "feat_decode: null pointer (scale): it is always needed, the kinds are not visible to the host");
+  OP_REFUSE((mean == nullptr) != (stddev == nullptr), "feat_decode: mean and stddev must both be given or both be null");
+  OP_REFUSE(((size_t)blob & 15) || ((size_t)out & 15), "feat_decode: blob or out not 16-byte aligned");
+  OP_REFUSE(((size_t)seg & 7) || ((size_t)mean & 7) || ((size_t)stddev & 7), "feat_decode: seg, mean or stddev not 8-byte aligned");
+  OP_REFUSE(((size_t)scale & 3) || ((size_t)offsets & 3), "feat_decode: scale or offsets not 4-byte aligned");
+  OP_REFUSE(B < 1 || D < 1 || blob_bytes < 1 || out_rows < 1, "feat_decode: B, D, blob_bytes, out_rows must be positive (got %d, %d, %lld, %lld)", B,
+            D, (long long)blob_bytes, (long long)out_rows);
+  OP_REFUSE((unsigned long long)out_rows > ((1ull << 40) / (unsigned long long)D), "feat_decode: out_rows x D = %lld x %d above the entry's 2^40",
+            (long long)out_rows, D);
+  launch_feat_decode(blob, (long long)blob_bytes, reinterpret_cast<const long long*>(seg), scale, offsets, B, D, mean, stddev, out,
+                     (long long)out_rows, (hipStream_t)stream);
+  OP_LAUNCHED("feat_decode");
+}
+
 }  // extern "C"

@@ -19,6 +19,7 @@
 // ONE launch, not an append launch and an emit launch: a live round is a few hundred rows, so a launch costs more than the work in it, and
 // the emit needs no order against the append because it takes this call's frames from `fresh` (normalising them with the append's own
 // expression) and only older frames from the ring, which the window invariant stated at the kernel keeps in other slots.
+// Last: k_feat_decode, the archive side (float, double and Kaldi-compressed matrices -> normalised float32 rows, tiled through LDS).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -394,6 +395,140 @@ void launch_feat_denorm(const float* y, const int* lengths, int B, int T, int D,
   const unsigned long long total = (unsigned long long)B * T * D;
   const int grid = (int)std::min<unsigned long long>(2048, std::max<unsigned long long>(1, ((total >> 2) + 255) / 256));
   hipLaunchKernelGGL(k_feat_denorm, dim3(grid), dim3(256), 0, s, y, lengths, (uint32_t)T, (uint32_t)D, mean, stddev, out, total);
+}
+
+// ---- the archive side: decode a batch of utterances from their Kaldi archive encoding into normalised float32 rows, one launch.
+// blob: the matrices' bytes as they lie in the file; seg [B][2] = (byte offset of utterance b's segment in blob, kind); scale [B][2] = (min,
+// range) of a compressed matrix's header; n_b = offsets[b + 1] - offsets[b].  Element (j, d) of utterance b, j < n_b:
+//   kind 0 (float  [n][D] row-major):  x = (double)f32[j * D + d]
+//   kind 1 (double [n][D] row-major):  x = f64[j * D + d]
+//   kind 2 (compressed, format 1: 4 * D little-endian uint16 percentiles, then D * n bytes, column-major):
+//            p_k = min + ((range * 1.52590218966964e-05) * (double)u16[4 * d + k])                 k = 0 .. 3
+//            v   = (double)byte[d * n + j]
+//            x   = v < 64 ? p_0 + ((p_1 - p_0) * v) * (1 / 64.0) : v <= 192 ? p_1 + ((p_2 - p_1) * (v - 64)) * (1 / 128.0)
+//                                                                            : p_2 + ((p_3 - p_2) * (v - 192)) * (1 / 63.0)
+//   out[offsets[b] + j][d] = mean ? (float)((x - mean[d]) / stddev[d]) : (float)x
+// which is io/kaldi_ark.py's uint16_to_float and char_to_float, io/features.py's apply_cmvn and the reader's cast, operation by operation
+// in IEEE double (contract(off): no multiply-add is formed; 1 / 63.0 is the rounded constant, multiplied): the host path's bits.  The
+// decoded value is never rounded to float before it is normalised, which is why decode and CMVN are one kernel.
+// Work: a tile is 64 frames x 64 dimensions of one utterance.  Tiles are numbered utterance by utterance, frames-major, and a workgroup
+// finds its (utterance, tile) by walking the offset table (B scalar loads): the host knows no n_b, only that sum ceil(n_b / 64) is at most
+// ceil(out_rows / 64) + B for utterances that lie in `out` without overlap, which is what the grid-stride loop runs to.
+// Layout: a compressed column is contiguous along FRAMES, a row of `out` along DIMENSIONS.  Load phase: a wave owns one column and its 64
+// lanes read 64 consecutive bytes (byte loads: a column starts at any byte address), decode, normalise and store the float into the LDS
+// tile [frame][dimension], rows padded to 65 floats (the 64 lanes of a store hit 64 different banks).  Store phase: a wave owns one frame
+// and its lanes write 64 consecutive floats of the output row.  The four percentiles of a column become doubles once per workgroup and
+// column (256 threads = 64 columns x 4), in LDS.  Kinds 0 and 1 are row-major like `out` and go straight through, no LDS.
+// Memory safety: the segment offset is clamped into [0, blob_bytes], every byte index into [0, blob_bytes) (the 4- and 8-byte loads into
+// [0, blob_bytes - size], aligned down; a blob shorter than the load gives +0.0), every destination row into [0, out_rows); an unknown kind
+// writes +0.0; n_b <= 0 writes nothing.  No atomics, no traffic between workgroups, no scratch memory.
+constexpr int DEC_TF = 64, DEC_TD = 64;
+
+template <bool NORM>
+__device__ __forceinline__ float decode_norm(double x, uint32_t d, const double* __restrict__ mean, const double* __restrict__ stddev) {
+#pragma clang fp contract(off)
+  if (!NORM) return (float)x;
+  const double c = x - mean[d];
+  return (float)(c / stddev[d]);
+}
+
+__device__ __forceinline__ double decode_byte(const double* __restrict__ p, uint32_t byte) {
+#pragma clang fp contract(off)
+  const double v = (double)byte;
+  if (byte < 64) return p[0] + ((p[1] - p[0]) * v) * (1 / 64.0);
+  if (byte <= 192) return p[1] + ((p[2] - p[1]) * (v - 64)) * (1 / 128.0);
+  return p[2] + ((p[3] - p[2]) * (v - 192)) * (1 / 63.0);
+}
+
+// a byte index clamped into the blob (both ends: sums of garbage table entries may wrap)
+__device__ __forceinline__ long long decode_at(long long i, long long blob_bytes) { return min(max(i, 0ll), blob_bytes - 1); }
+
+template <bool NORM>
+__global__ __launch_bounds__(256) void k_feat_decode(const uint8_t* __restrict__ blob, long long blob_bytes, const long long* __restrict__ seg,
+                                                      const float* __restrict__ scale, const int* __restrict__ offsets, int B, uint32_t D,
+                                                      const double* __restrict__ mean, const double* __restrict__ stddev, float* __restrict__ out,
+                                                      long long out_rows, unsigned long long row_tiles, uint32_t d_tiles) {
+#pragma clang fp contract(off)
+  __shared__ float tile[DEC_TF][DEC_TD + 1];
+  __shared__ double pc[DEC_TD][4];
+  const uint32_t tid = threadIdx.x;
+  const unsigned long long total = row_tiles * d_tiles;
+  for (unsigned long long w = blockIdx.x; w < total; w += gridDim.x) {
+    const unsigned long long rt = w / d_tiles;
+    const uint32_t d0 = (uint32_t)(w - rt * d_tiles) * DEC_TD;
+    // which utterance row tile rt belongs to (uniform over the workgroup)
+    int b = 0;
+    unsigned long long first = 0;
+    long long n = 0, rows = 0;
+    for (; b < B; ++b) {
+      n = max((long long)offsets[b + 1] - (long long)offsets[b], 0ll);
+      rows = min(n, out_rows);
+      const unsigned long long t = ((unsigned long long)rows + DEC_TF - 1) / DEC_TF;
+      if (rt < first + t) break;
+      first += t;
+    }
+    if (b == B) break;                                                // (rt grows with w: no later tile of this workgroup exists either)
+    const long long j0 = (long long)(rt - first) * DEC_TF, off = offsets[b];
+    const long long s = min(max(seg[2 * (size_t)b], 0ll), blob_bytes), kind = seg[2 * (size_t)b + 1];
+    const uint32_t nf = (uint32_t)min((long long)DEC_TF, rows - j0), nd = min((uint32_t)DEC_TD, D - d0);
+    if (kind == 2) {
+      {
+        const uint32_t col = tid >> 2, k = tid & 3;
+        if (col < nd) {
+          const long long i = s + 8ll * (d0 + col) + 2 * k;
+          const uint32_t u = (uint32_t)blob[decode_at(i, blob_bytes)] | ((uint32_t)blob[decode_at(i + 1, blob_bytes)] << 8);
+          pc[col][k] = (double)scale[2 * (size_t)b] + (((double)scale[2 * (size_t)b + 1] * 1.52590218966964e-05) * (double)u);
+        }
+      }
+      __syncthreads();
+      const long long payload = s + 8ll * D;
+      for (uint32_t e = tid; e < DEC_TF * DEC_TD; e += 256) {       // a wave: 64 frames of one column
+        const uint32_t jj = e & (DEC_TF - 1), dd = e / DEC_TF;
+        if (jj < nf && dd < nd) {
+          const long long i = payload + (long long)(d0 + dd) * n + j0 + jj;
+          tile[jj][dd] = decode_norm<NORM>(decode_byte(pc[dd], blob[decode_at(i, blob_bytes)]), d0 + dd, mean, stddev);
+        }
+      }
+      __syncthreads();
+      for (uint32_t e = tid; e < DEC_TF * DEC_TD; e += 256) {       // a wave: 64 dimensions of one frame
+        const uint32_t dd = e & (DEC_TD - 1), jj = e / DEC_TD;
+        if (jj < nf && dd < nd) {
+          const long long row = min(max(off + j0 + jj, 0ll), out_rows - 1);
+          out[(size_t)row * D + d0 + dd] = tile[jj][dd];
+        }
+      }
+      __syncthreads();                                                // (tile and pc are rewritten by the next tile of this workgroup)
+      continue;
+    }
+    const long long size = kind == 0 ? 4 : 8;
+    const bool known = (kind == 0 || kind == 1) && blob_bytes >= size;
+    for (uint32_t e = tid; e < DEC_TF * DEC_TD; e += 256) {
+      const uint32_t dd = e & (DEC_TD - 1), jj = e / DEC_TD;
+      if (jj < nf && dd < nd) {
+        float v = 0.f;
+        if (known) {
+          const long long i = min(max(s + size * ((j0 + jj) * (long long)D + d0 + dd), 0ll), blob_bytes - size) & ~(size - 1);
+          const double x = kind == 0 ? (double)*reinterpret_cast<const float*>(blob + i) : *reinterpret_cast<const double*>(blob + i);
+          v = decode_norm<NORM>(x, d0 + dd, mean, stddev);
+        }
+        const long long row = min(max(off + j0 + jj, 0ll), out_rows - 1);
+        out[(size_t)row * D + d0 + dd] = v;
+      }
+    }
+  }
+}
+
+void launch_feat_decode(const uint8_t* blob, long long blob_bytes, const long long* seg, const float* scale, const int* offsets, int B, int D,
+                        const double* mean, const double* stddev, float* out, long long out_rows, hipStream_t s) {
+  const unsigned long long row_tiles = ((unsigned long long)out_rows + DEC_TF - 1) / DEC_TF + (unsigned long long)B;
+  const uint32_t d_tiles = ((uint32_t)D + DEC_TD - 1) / DEC_TD;
+  const int grid = (int)std::min<unsigned long long>(16384, row_tiles * d_tiles);
+  if (mean)
+    hipLaunchKernelGGL(k_feat_decode<true>, dim3(grid), dim3(256), 0, s, blob, blob_bytes, seg, scale, offsets, B, (uint32_t)D, mean, stddev, out,
+                       out_rows, row_tiles, d_tiles);
+  else
+    hipLaunchKernelGGL(k_feat_decode<false>, dim3(grid), dim3(256), 0, s, blob, blob_bytes, seg, scale, offsets, B, (uint32_t)D, mean, stddev, out,
+                       out_rows, row_tiles, d_tiles);
 }
 
 }  // namespace rsr

@@ -473,6 +473,11 @@ void launch_feat_stream(const float* fresh, long long fresh_rows, const int* tab
 // y 16-byte aligned, B * T * D < 2^32.
 void launch_feat_denorm(const float* y, const int* lengths, int B, int T, int D, const double* mean, const double* stddev, double* out,
                         hipStream_t s);
+// the archive side: B utterances in their archive encoding (blob + seg [B][2] = (byte offset, kind: 0 float, 1 double, 2 Kaldi compressed
+// format 1) + scale [B][2] = (min, range)) -> normalised float32 rows out [out_rows][D], utterance b at rows offsets[b] .. offsets[b + 1] - 1.
+// blob and out 16-byte aligned, out_rows * D <= 2^40, mean / stddev [D] double or both null.
+void launch_feat_decode(const uint8_t* blob, long long blob_bytes, const long long* seg, const float* scale, const int* offsets, int B, int D,
+                        const double* mean, const double* stddev, float* out, long long out_rows, hipStream_t s);
 void launch_colsum(const float* a, int lda, const float* b, int ldb, float* out, int rows, int cols,
                    float* scratch /* >= 64*cols floats */, hipStream_t s);
 

@@ -233,13 +233,16 @@ class HipEngine(OpEntries):      # (the handle-free rsrgan_op_* wrappers and lau
         runs there: ready=True waits for THAT stream only and vouches for the results (what upload_ready gives the labels and lengths of
         a D-run under RSRGAN_DPIPE=1); ready=False hands them over by event, as upload_async does.  ValueError before any device work
         if an utterance is longer than max_frames (limit=False: the caller cuts the result into chunks itself, as the chunked decode
-        does)."""
+        does).  An io.CodedBatch (the archive's bytes: float, double or Kaldi-compressed matrices) is decoded on the device first
+        (_featurize_coded); everything else is the same."""
         left = packed.left if left is None else int(left)
         right = packed.right if right is None else int(right)
         if mean is None and stddev is None:
             mean, stddev = packed.mean, packed.stddev
         if (mean is None) != (stddev is None):
             raise ValueError("featurize: mean and stddev must both be given or both be None")
+        if hasattr(packed, "blob"):
+            return self._featurize_coded(packed, left, right, mean, stddev, ready, limit)
         data, offsets = packed.data, packed.offsets
         if not isinstance(data, np.ndarray) or data.dtype != np.float32 or data.ndim != 2:
             raise ValueError("featurize: packed.data must be a float32 [rows, D] array")
@@ -277,6 +280,52 @@ class HipEngine(OpEntries):      # (the handle-free rsrgan_op_* wrappers and lau
         out.record_stream(cur); ln.record_stream(cur)
         return out, ln
 
+    # -- the archive side (include/rsrgan.h rsrgan_feat_decode, csrc/feat.hip k_feat_decode) -----------------------------------
+    def op_feat_decode(self, blob, seg, scale, offsets, B, D, mean, stddev, out, blob_bytes=None, out_rows=None, stream=None):
+        """rsrgan_feat_decode on caller-owned device tensors (blob uint8, seg [B, 2] i64 = (byte offset, kind), scale [B, 2] f32 = (min,
+        range), offsets [B + 1] i32, mean / stddev [D] f64 or None, out [rows, D] f32), on `stream` (default: the current one)"""
+        check(self.lib.rsrgan_feat_decode(_ptr(blob), blob.numel() if blob_bytes is None else blob_bytes, _ptr(seg), _ptr(scale), _ptr(offsets),
+                                          B, D, _ptr(mean), _ptr(stddev), _ptr(out), out.shape[0] if out_rows is None else out_rows,
+                                          self._stream() if stream is None else C.c_void_p(stream.cuda_stream)))
+
+    def _featurize_coded(self, coded, left, right, mean, stddev, ready, limit):
+        """featurize for an io.CodedBatch: the blob and the three tables travel on the upload stream, rsrgan_feat_decode turns them into
+        normalised float32 rows [frames, D] and rsrgan_feat_batch (mean = NULL) splices and pads those -- the decode normalises, because the
+        host path never rounds the decoded value to float32 before it does."""
+        blob, seg, scale, offsets = coded.blob, coded.seg, coded.scale, coded.offsets
+        B, T, D = int(coded.shape[0]), int(coded.shape[1]), int(coded.dim)
+        rows = int(offsets[-1]) if offsets.shape[0] else 0
+        if B < 1 or T < 1 or rows < 1 or offsets.shape != (B + 1,):
+            raise ValueError("featurize: B = %d, T = %d, %d rows, %d offsets" % (B, T, rows, offsets.shape[0]))
+        n = np.diff(offsets.astype(np.int64))
+        if limit and max(int(n.max()), T) > self.max_frames:
+            raise ValueError("featurize: an utterance of %d frames (T = %d) is longer than max_frames = %d" % (int(n.max()), T, self.max_frames))
+        if mean is not None and (np.size(mean) != D or np.size(stddev) != D):
+            raise ValueError("featurize: mean / stddev must hold D = %d entries, got %d / %d" % (D, np.size(mean), np.size(stddev)))
+        us = self.upload_stream()
+        dm, ds = self._cmvn_device(mean, stddev, us) if mean is not None else (None, None)
+        with torch.cuda.stream(us):
+            dblob = torch.from_numpy(np.ascontiguousarray(blob)).to(self.device, non_blocking=True)
+            dseg = torch.from_numpy(np.ascontiguousarray(seg)).to(self.device, non_blocking=True)
+            dscale = torch.from_numpy(np.ascontiguousarray(scale)).to(self.device, non_blocking=True)
+            off = torch.from_numpy(np.ascontiguousarray(offsets)).to(self.device, non_blocking=True)
+            raw = torch.empty(rows, D, dtype=torch.float32, device=self.device)
+            out = torch.empty(B, T, D * (left + 1 + right), dtype=torch.float32, device=self.device)
+            ln = torch.empty(B, dtype=torch.int32, device=self.device)
+            self.op_feat_decode(dblob, dseg, dscale, off, B, D, dm, ds, raw, stream=us)
+            self.op_feat_batch(raw, off, B, T, D, left, right, None, None, out, ln, stream=us)
+            if not ready:
+                ev = torch.cuda.Event()
+                ev.record(us)
+        cur = torch.cuda.current_stream(self.device)
+        if ready:
+            us.synchronize()
+            self._vouch(out); self._vouch(ln)
+        else:
+            cur.wait_event(ev)
+        out.record_stream(cur); ln.record_stream(cur)
+        return out, ln
+
     # -- the frame-level recipes' front end (include/rsrgan.h rsrgan_feat_frames, csrc/feat.hip k_feat_frames) ------------------
     def op_feat_frames(self, pool, picks, N, D, left, right, mean, stddev, out, pool_rows=None, stream=None):
         """rsrgan_feat_frames on caller-owned device tensors (pool [rows, D] f32, picks [N, 3] i32 = (row, lo, hi), mean / stddev [D] f64 or
@@ -292,10 +341,12 @@ class HipEngine(OpEntries):      # (the handle-free rsrgan_op_* wrappers and lau
         into the slot).  Per item: grow the pools if the reader's allocator did (old rows keep their numbers), normalise the new utterances
         once, then gather the drawn frames with two rsrgan_feat_frames launches (inputs with the recipe's context, labels with none; mean =
         NULL).  Gathering rows commutes with the elementwise cast to float32, which is why normalise -> cast -> gather gives the bits of the
-        host's normalise -> splice -> cast.  ready as in featurize.  ValueError before any device work for an item that is not the next one
+        host's normalise -> splice -> cast.  Coded admissions (FrameBatchReader(device_decode=True): the archive's bytes) are decoded and
+        normalised into the slot by rsrgan_feat_decode instead.  ready as in featurize.  ValueError before any device work for an item that is not the next one
         of its reader."""
-        from .io.frame_pool import PoolLedger
-        pools = self.__dict__.setdefault("_frame_pools", {})
+        from .io.features import pack_coded
+        from .io.frame_pool import PoolLedger, is_coded
+        pools =self.__dict__.setdefault("_frame_pools", {})
         st = pools.get(item.reader_id)
         if st is None:
             st = pools[item.reader_id] = {"ledger": PoolLedger(item.reader_id), "x": None, "y": None, "items": 0, "uploads": 0, "growths": 0}
@@ -324,7 +375,23 @@ class HipEngine(OpEntries):      # (the handle-free rsrgan_op_* wrappers and lau
                     st["growths"] += 1
                 st["x"], st["y"] = nx, ny
             px, py = st["x"], st["y"]
+            coded = [u for u in item.uploads if is_coded(u[1])]
+            if coded:
+                # coded admissions (FrameBatchReader(device_decode=True)): the item's bytes travel as ONE blob per side with one set of
+                # tables, and every utterance is decoded and normalised straight into its pool rows by a launch of its own (B = 1, the
+                # table pointers advanced to its entry, offsets = (first, first + n), out = the whole pool): slots are not adjacent
+                # rows, and rows between them belong to other utterances
+                offs = torch.tensor([[f, f + u.rows] for f, u, _ in coded], dtype=torch.int32).to(self.device, non_blocking=True)
+                for side, pool, Dp, m, s in ((1, px, D, mi, si), (2, py, Dl, ml, sl)):
+                    cb = pack_coded([u[side] for u in coded])
+                    dblob = torch.from_numpy(cb.blob).to(self.device, non_blocking=True)
+                    dseg = torch.from_numpy(cb.seg).to(self.device, non_blocking=True)
+                    dscale = torch.from_numpy(cb.scale).to(self.device, non_blocking=True)
+                    for b in range(len(coded)):
+                        self.op_feat_decode(dblob, dseg[b], dscale[b], offs[b], 1, Dp, m, s, pool, stream=us)
             for first, rx, ry in item.uploads:
+                if is_coded(rx):
+                    continue
                 n = rx.shape[0]
                 if mi is None:
                     px[first:first + n].copy_(torch.from_numpy(rx), non_blocking=True)

@@ -1,7 +1,7 @@
 """NumPy / Kaldi-ark data path replacing the reference's io_funcs (TFRecords + tf.data):
 ark/scp reader and writer, global CMVN, Kaldi-style splicing, length-bucketed padded batches."""
-from .kaldi_ark import ArkReader, ArkWriter, read_binary_file, convert_cmvn_to_numpy     # noqa: F401
+from .kaldi_ark import ArkReader, ArkWriter, CodedMatrix, read_binary_file, convert_cmvn_to_numpy     # noqa: F401
 from .features import apply_cmvn, splice_feats, PaddedBatchReader, FrameBatchReader                          # noqa: F401
-from .features import PackedBatch, pack_utterances                                         # noqa: F401
+from .features import PackedBatch, pack_utterances, CodedBatch, pack_coded                # noqa: F401
 from .frame_pool import FrameDraw, PoolLedger, RowAllocator                                 # noqa: F401
 from .prefetch import prefetch                                                             # noqa: F401

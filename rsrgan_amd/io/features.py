@@ -8,7 +8,7 @@ from typing import Iterator, List, Optional
 
 import numpy as np
 
-from .kaldi_ark import ArkReader
+from .kaldi_ark import ArkReader, coded_bytes
 
 
 def apply_cmvn(inputs, labels, cmvn):
@@ -84,6 +84,102 @@ def pack_utterances(mats, left=0, right=0, mean=None, stddev=None, T=None, names
                        mean, stddev)
 
 
+ALIGN = 16                                 # every utterance's segment starts at a multiple of this in a CodedBatch's blob
+
+
+class CodedBatch(object):
+    """PackedBatch's sibling for archives that are not float32: the utterances in their ARCHIVE encoding, to be decoded, normalised,
+    spliced and padded on the device (HipEngine.featurize, csrc/feat.hip k_feat_decode).  `blob` uint8: the matrices' bytes as the files
+    hold them, every utterance's segment starting at a multiple of 16; `seg` int64 [B, 2] = (byte offset of the segment, kind:
+    kaldi_ark.KIND_*); `scale` float32 [B, 2] = (min, range) of a compressed matrix's header; `offsets` int32 [B + 1]: utterance b has
+    offsets[b + 1] - offsets[b] frames.  `shape`, `left`, `right`, `mean`, `stddev` as in PackedBatch; `dim` = the matrices' columns.
+    The constructor checks what the device cannot: known kinds, monotone offsets, every segment aligned and inside the blob with the
+    size its kind, frames and dim imply."""
+
+    def __init__(self, blob, seg, scale, offsets, shape, left=0, right=0, mean=None, stddev=None):
+        self.blob, self.seg, self.scale, self.offsets = blob, seg, scale, offsets
+        self.shape = tuple(int(v) for v in shape)
+        self.left, self.right, self.mean, self.stddev = int(left), int(right), mean, stddev
+        B, C = self.shape[0], self.left + 1 + self.right
+        if self.shape[2] < C or self.shape[2] % C:
+            raise ValueError("shape[2] = %d is no multiple of left + 1 + right = %d" % (self.shape[2], C))
+        self.dim = self.shape[2] // C
+        if blob.dtype != np.uint8 or blob.ndim != 1:
+            raise ValueError("blob must be a flat uint8 array, got %s %s" % (blob.dtype, blob.shape))
+        if offsets.shape != (B + 1,) or offsets.dtype != np.int32:
+            raise ValueError("offsets must hold B + 1 = %d int32 entries, got %s %s" % (B + 1, offsets.dtype, offsets.shape))
+        if seg.shape != (B, 2) or seg.dtype != np.int64 or scale.shape != (B, 2) or scale.dtype != np.float32:
+            raise ValueError("seg must be int64 [%d, 2] and scale float32 [%d, 2], got %s %s and %s %s" % (
+                B, B, seg.dtype, seg.shape, scale.dtype, scale.shape))
+        n = np.diff(offsets.astype(np.int64))
+        if (B and n.min() < 0) or offsets[0] < 0:
+            raise ValueError("offsets must start at 0 or above and never decrease")
+        for b in range(B):
+            size = coded_bytes(int(seg[b, 1]), int(n[b]), self.dim)
+            if size is None:
+                raise ValueError("utterance %d: unknown kind %d" % (b, seg[b, 1]))
+            if seg[b, 0] < 0 or seg[b, 0] % ALIGN or seg[b, 0] + size > blob.shape[0]:
+                raise ValueError("utterance %d: a segment of %d bytes at byte %d does not lie in the blob of %d (segments start at multiples "
+                                 "of %d)" % (b, size, seg[b, 0], blob.shape[0], ALIGN))
+
+    def __len__(self):
+        return self.shape[0]
+
+    def lengths(self):
+        """frames of every utterance after truncation at T (int32 [B]): what the splice kernel writes as `lengths`"""
+        return np.minimum(np.diff(self.offsets), self.shape[1]).astype(np.int32)
+
+    def nbytes(self):
+        """what travels to the device: the blob and the three tables"""
+        return int(self.blob.nbytes + self.seg.nbytes + self.scale.nbytes + self.offsets.nbytes)
+
+    def rows(self, lo, hi):
+        """utterances [lo, hi) as a batch of their own -- this rank's shard of a fed batch (GAN_RNN._shard): only their bytes, segment
+        offsets and frame offsets rebased to 0, the same T"""
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo <= hi <= self.shape[0]:
+            raise ValueError("rows [%d, %d) outside the batch of %d" % (lo, hi, self.shape[0]))
+        n = np.diff(self.offsets[lo:hi + 1].astype(np.int64))
+        sizes = [coded_bytes(int(self.seg[b, 1]), int(n[b - lo]), self.dim) for b in range(lo, hi)]
+        parts = [self.blob[int(self.seg[b, 0]):int(self.seg[b, 0]) + s] for b, s in zip(range(lo, hi), sizes)]
+        blob, starts = _join_aligned(parts)
+        seg = np.stack([starts, self.seg[lo:hi, 1]], 1).astype(np.int64).reshape(hi - lo, 2)
+        return CodedBatch(blob, seg, np.ascontiguousarray(self.scale[lo:hi]), (self.offsets[lo:hi + 1] - self.offsets[lo]).astype(np.int32),
+                          (hi - lo,) + self.shape[1:], self.left, self.right, self.mean, self.stddev)
+
+
+def _join_aligned(parts):
+    """byte strings / uint8 arrays -> (one uint8 array in which part i starts at starts[i], a multiple of ALIGN; the gaps are zero)"""
+    starts = np.zeros(len(parts), np.int64)
+    at = 0
+    for i, p in enumerate(parts):
+        starts[i] = at
+        at += (len(p) + ALIGN - 1) // ALIGN * ALIGN
+    blob = np.zeros(max(at, ALIGN), np.uint8)
+    for s, p in zip(starts.tolist(), parts):
+        blob[s:s + len(p)] = np.frombuffer(p, np.uint8) if isinstance(p, (bytes, bytearray)) else p
+    return blob, starts
+
+
+def pack_coded(mats, left=0, right=0, mean=None, stddev=None, T=None, names=None):
+    """kaldi_ark.CodedMatrix items (ArkReader.read_coded) -> CodedBatch padded to T (default: the longest): the bytes are copied once,
+    nothing is decoded."""
+    D = mats[0].cols
+    for i, m in enumerate(mats):
+        if m.cols != D:
+            raise ValueError("utterance %s: %d columns, the batch has %d" % (names[i] if names is not None else i, m.cols, D))
+    n = [m.rows for m in mats]
+    offsets = np.zeros(len(mats) + 1, np.int64)
+    np.cumsum(n, out=offsets[1:])
+    if offsets[-1] >= 2 ** 31:
+        raise ValueError("a coded batch of %d frames does not fit the int32 offset table" % offsets[-1])
+    blob, starts = _join_aligned([m.data for m in mats])
+    seg = np.stack([starts, np.array([m.kind for m in mats], np.int64)], 1)
+    scale = np.array([[m.min, m.range] for m in mats], np.float32).reshape(len(mats), 2)
+    return CodedBatch(blob, seg, scale, offsets.astype(np.int32), (len(mats), max(n) if T is None else int(T), D * (left + 1 + right)), left,
+                      right, mean, stddev)
+
+
 class PaddedBatchReader(object):
     """get_padded_batch (tfrecords_dataset.py:53-180) without TFRecords: reads (inputs, labels)
     utterance pairs from two scp files, applies CMVN and splicing, groups utterances into windows of
@@ -95,11 +191,16 @@ class PaddedBatchReader(object):
 
     device_features=True: CMVN, splicing and padding are left to the device (HipEngine.featurize).  materialize only reads and
     concatenates the raw utterances and yields [utt_ids, PackedBatch(inputs), PackedBatch(labels), lengths]; plan() is the same, so
-    the same seed draws the same batches in the same order, and the expanded items are bit for bit the default reader's."""
+    the same seed draws the same batches in the same order, and the expanded items are bit for bit the default reader's.
+
+    device_decode=True (implies device_features): the archives' bytes travel UNDECODED -- float, double and Kaldi-compressed matrices
+    alike -- and the device decodes them too (csrc/feat.hip k_feat_decode).  materialize reads each matrix's bytes (ArkReader.read_coded,
+    no NumPy decode) and yields [utt_ids, CodedBatch(inputs), CodedBatch(labels), lengths]; plan() is the same again."""
 
     def __init__(self, inputs_scp, labels_scp, batch_size, left_context=0, right_context=0, cmvn=None,
-                 num_buckets=20, shuffle=True, seed=None, device_features=False):
-        self.device_features = bool(device_features)
+                 num_buckets=20, shuffle=True, seed=None, device_features=False, device_decode=False):
+        self.device_decode = bool(device_decode)
+        self.device_features = bool(device_features) or self.device_decode
         self._stats = None
         if self.device_features and cmvn is not None:
             self._stats = tuple(np.ascontiguousarray(cmvn[k], np.float64).reshape(-1)
@@ -171,7 +272,21 @@ class PaddedBatchReader(object):
         Y = pack_utterances(ys, 0, 0, ml, sl, names=ids)
         return [ids, X, Y, X.lengths()]
 
+    def _coded(self, indices):
+        ids = [self.inputs.utt_ids[i] for i in indices]
+        xs = [self.inputs.read_coded_from_index(i) for i in indices]
+        ys = [self.labels.read_coded_from_index(i) for i in indices]
+        for u, x, y in zip(ids, xs, ys):
+            if x.rows != y.rows:
+                raise ValueError("utterance %s: %d input frames, %d label frames" % (u, x.rows, y.rows))
+        mi, si, ml, sl = self._stats if self._stats is not None else (None,) * 4
+        X = pack_coded(xs, self.left, self.right, mi, si, names=ids)
+        Y = pack_coded(ys, 0, 0, ml, sl, names=ids)
+        return [ids, X, Y, X.lengths()]
+
     def materialize(self, indices: List[int]) -> List:
+        if self.device_decode:
+            return self._coded(indices)
         if self.device_features:
             return self._packed(indices)
         return self._pad([self._utt(i) for i in indices])
@@ -194,11 +309,16 @@ class FrameBatchReader(object):
     enqueued since the previous batch and a table of the drawn frames (pool row, the utterance's row range) from which one kernel gathers the
     spliced batch.  Enqueuing follows the rules of __iter__ and drawing makes the same calls on self.rng, so the same seed draws the same
     frames in the same order as the default reader, and the expanded batches are its batches bit for bit.  `initial_pool_rows`: the
-    pool's first capacity (default: the queue's capacity; it doubles when an utterance does not fit)."""
+    pool's first capacity (default: the queue's capacity; it doubles when an utterance does not fit).
+
+    device_decode=True (implies device_features): an admission carries the matrices' bytes as the archive holds them
+    (kaldi_ark.CodedMatrix: float, double or Kaldi-compressed) and the device decodes and normalises them into the pool rows in one
+    launch (csrc/feat.hip k_feat_decode); the queue's bookkeeping and the draws are the same."""
 
     def __init__(self, inputs_scp, labels_scp, batch_size, left_context=0, right_context=0, cmvn=None, num_threads=4,
-                 shuffle=True, seed=None, device_features=False, initial_pool_rows=None):
-        self.device_features = bool(device_features)
+                 shuffle=True, seed=None, device_features=False, initial_pool_rows=None, device_decode=False):
+        self.device_decode = bool(device_decode)
+        self.device_features = bool(device_features) or self.device_decode
         self.inputs, self.labels = ArkReader(), ArkReader()
         self.inputs(inputs_scp)
         self.labels(labels_scp)
@@ -231,6 +351,11 @@ class FrameBatchReader(object):
         return splice_feats(x, self.left, self.right).astype(np.float32), y.astype(np.float32)
 
     def _raw(self, i):
+        if self.device_decode:
+            x, y = self.inputs.read_coded_from_index(i), self.labels.read_coded_from_index(i)
+            if x.rows != y.rows:
+                raise ValueError("utterance %s: %d input frames, %d label frames" % (self.inputs.utt_ids[i], x.rows, y.rows))
+            return x, y
         x, y = self.inputs.read_utt_data_from_index(i), self.labels.read_utt_data_from_index(i)
         for m, what in ((x, "inputs"), (y, "labels")):
             if not isinstance(m, np.ndarray) or m.dtype != np.float32 or m.ndim != 2:

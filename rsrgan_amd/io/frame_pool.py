@@ -84,7 +84,8 @@ class FrameDraw(object):
     `uploads`: [(first_row, raw_inputs float32 [n, D], raw_labels float32 [n, Dl])] of the utterances enqueued since the previous item, to be
     normalised once into rows first_row .. first_row + n - 1; `pool_rows`: the capacity the pool must have by now (monotone); `picks` int32
     [N, 3] = (row, lo, hi): the drawn frames, each with its utterance's row range; `left`, `right`; `stats`: (mean_inputs, stddev_inputs,
-    mean_labels, stddev_labels) in float64, or None for no CMVN.  Stateful: consumed once, in order (PoolLedger)."""
+    mean_labels, stddev_labels) in float64, or None for no CMVN.  Under FrameBatchReader(device_decode=True) an upload's two matrices are
+    kaldi_ark.CodedMatrix items instead (the archive's bytes, decoded on the device).  Stateful: consumed once, in order (PoolLedger)."""
 
     def __init__(self, serial, reader_id, uploads, pool_rows, picks, left, right, stats, input_dim, label_dim):
         self.serial, self.reader_id, self.uploads, self.pool_rows, self.picks = int(serial), reader_id, uploads, int(pool_rows), picks
@@ -99,6 +100,11 @@ class FrameDraw(object):
 def is_frame_draw(a):
     """a FrameDraw (by its fields, as train.is_packed tells a PackedBatch)"""
     return hasattr(a, "picks") and hasattr(a, "uploads") and hasattr(a, "serial")
+
+
+def is_coded(m):
+    """a kaldi_ark.CodedMatrix (by its fields): an admission whose bytes the device decodes"""
+    return hasattr(m, "kind") and hasattr(m, "data") and hasattr(m, "rows")
 
 
 class PoolLedger(object):
@@ -118,7 +124,13 @@ class PoolLedger(object):
             raise ValueError("frame draw %d: pool_rows = %d (the pool holds %d rows and never shrinks; units of %d)" % (
                 item.serial, item.pool_rows, self.pool_rows, UNIT))
         for first, x, y in item.uploads:
-            if (x.dtype != np.float32 or y.dtype != np.float32 or x.ndim != 2 or y.ndim != 2 or x.shape[0] != y.shape[0]
+            if is_coded(x) or is_coded(y):
+                # a coded admission (FrameBatchReader(device_decode=True)): kaldi_ark.CodedMatrix pairs, whose constructor has checked the
+                # byte count against kind, rows and cols
+                if not (is_coded(x) and is_coded(y)) or x.rows != y.rows or x.cols != item.input_dim or y.cols != item.label_dim:
+                    raise ValueError("frame draw %d: an upload is not a pair of coded [n, %d] / [n, %d] matrices" % (
+                        item.serial, item.input_dim, item.label_dim))
+            elif (x.dtype != np.float32 or y.dtype != np.float32 or x.ndim != 2 or y.ndim != 2 or x.shape[0] != y.shape[0]
                     or x.shape[1] != item.input_dim or y.shape[1] != item.label_dim):
                 raise ValueError("frame draw %d: an upload is not a pair of float32 [n, %d] / [n, %d] matrices" % (
                     item.serial, item.input_dim, item.label_dim))

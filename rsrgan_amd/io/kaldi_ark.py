@@ -15,6 +15,37 @@ import struct
 import numpy as np
 
 
+KIND_FLOAT, KIND_DOUBLE, KIND_COMPRESSED = 0, 1, 2          # the `kind` of include/rsrgan.h rsrgan_feat_decode
+
+
+def coded_bytes(kind, rows, cols):
+    """bytes of a matrix of `kind` in the archive, its header excluded (None: unknown kind)"""
+    if kind == KIND_FLOAT:
+        return 4 * rows * cols
+    if kind == KIND_DOUBLE:
+        return 8 * rows * cols
+    if kind == KIND_COMPRESSED:
+        return 8 * cols + rows * cols
+    return None
+
+
+class CodedMatrix(object):
+    """One archive matrix as the file holds it (ArkReader.read_coded).  `kind`: KIND_FLOAT ('BFM ', float32 [rows, cols] row-major),
+    KIND_DOUBLE ('BDM ', float64 likewise) or KIND_COMPRESSED ('BCM ' format 1: 8 * cols bytes of per-column uint16 percentiles, then
+    rows * cols payload bytes, column-major); `min`, `range`: the compressed header's float32 pair (0.0 otherwise); `data`: the bytes."""
+    __slots__ = ("kind", "rows", "cols", "min", "range", "data")
+
+    @property
+    def shape(self):
+        return (self.rows, self.cols)
+
+    def __init__(self, kind, rows, cols, min_value, rng, data):
+        self.kind, self.rows, self.cols, self.min, self.range, self.data = int(kind), int(rows), int(cols), float(min_value), float(rng), data
+        if len(data) != coded_bytes(self.kind, self.rows, self.cols):
+            raise ValueError("a %d x %d matrix of kind %d holds %s bytes, the archive gave %d" % (
+                self.rows, self.cols, self.kind, coded_bytes(self.kind, self.rows, self.cols), len(data)))
+
+
 class ArkReader(object):
     """kaldi_io.py:41-235.  Call the instance with an .scp path, then read utterances."""
 
@@ -67,6 +98,32 @@ class ArkReader(object):
             else:
                 raise ValueError("unknown matrix type %r" % (header[1],))
             return np.reshape(mat, (rows, cols))
+
+    def read_coded(self, ark_file, ark_offset=0):
+        """The matrix at `ark_offset` UNDECODED, for the device-side decode (csrc/feat.hip k_feat_decode): the header parsed as read_ark
+        parses it (the same errors), the matrix's bytes as they lie in the file, one read.  -> CodedMatrix."""
+        with open(ark_file, "rb") as buf:
+            buf.seek(int(ark_offset), 0)
+            header = struct.unpack("<xcccc", buf.read(5))
+            if header[0] != b"B":
+                raise ValueError("%s: input .ark file is not binary" % ark_file)
+            if header[1] == b"C":
+                if header[2] == b"M" and header[3] != b"2":
+                    min_value, rng, rows, cols = struct.unpack("<ffii", buf.read(16))
+                    if cols == 0:
+                        raise ValueError("Empty matrix.")
+                    return CodedMatrix(KIND_COMPRESSED, rows, cols, min_value, rng, buf.read(8 * cols + rows * cols))
+                raise ValueError("Unsupport format. Maybe because of the matrices with 8 or fewer rows.")
+            _, rows = struct.unpack("<bi", buf.read(5))
+            _, cols = struct.unpack("<bi", buf.read(5))
+            if header[1] == b"F":
+                return CodedMatrix(KIND_FLOAT, rows, cols, 0.0, 0.0, buf.read(rows * cols * 4))
+            if header[1] == b"D":
+                return CodedMatrix(KIND_DOUBLE, rows, cols, 0.0, 0.0, buf.read(rows * cols * 8))
+            raise ValueError("unknown matrix type %r" % (header[1],))
+
+    def read_coded_from_index(self, index):
+        return self.read_coded(self.scp_data[index][0], self.scp_data[index][1])
 
     def read_shape(self, ark_file, ark_offset=0):
         """(rows, cols) of the matrix at `ark_offset` from its header alone (length bucketing without reading the data)."""

@@ -24,7 +24,7 @@ import numpy as np
 
 from . import dist as rdist
 from .gan import GAN
-from .io import ArkReader, ArkWriter, FrameBatchReader, pack_utterances, splice_feats
+from .io import ArkReader, ArkWriter, FrameBatchReader, pack_coded, pack_utterances, splice_feats
 from .run_gan_rnn import _cmvn, str2bool
 from .train import device_frames
 
@@ -66,13 +66,25 @@ def build_parser():
     p.add_argument("--device_features", type=str2bool, nargs="?", const=True, default=False, help="CMVN and context splice on the device: "
                    "the shuffle queue's utterances stay resident there, normalised once, and one HIP kernel gathers every batch "
                    "(HipEngine.featurize_frames); same batches as the host path, bit for bit")
+    p.add_argument("--device_decode", type=str2bool, nargs="?", const=True, default=False, help="implies --device_features, and the archive "
+                   "is decoded on the device as well (csrc/feat.hip k_feat_decode): every utterance enters the pool as the bytes the file "
+                   "holds -- float, double or Kaldi-compressed -- with no host decode; training, cross-validation and --decode; same "
+                   "batches, bit for bit")
     return p
+
+
+def _device_decode(FLAGS):
+    return bool(getattr(FLAGS, "device_decode", False))
+
+
+def _device_features(FLAGS):
+    return bool(getattr(FLAGS, "device_features", False)) or _device_decode(FLAGS)
 
 
 def _reader(FLAGS, inputs_scp, labels_scp, cmvn, shuffle, seed):
     return FrameBatchReader(inputs_scp, labels_scp, FLAGS.batch_size, FLAGS.left_context, FLAGS.right_context, cmvn=cmvn,
                             num_threads=FLAGS.num_threads, shuffle=shuffle, seed=seed,
-                            device_features=bool(getattr(FLAGS, "device_features", False)))
+                            device_features=_device_features(FLAGS), device_decode=_device_decode(FLAGS))
 
 
 def _one_epoch(model, batches, num_batch, epoch, FLAGS, train, log, report=True):
@@ -215,8 +227,8 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None, moving_aver
         os.remove(write_ark_path)
     writer = ArkWriter(write_scp_path)
     featurize = None
-    if getattr(FLAGS, "device_features", False):
-        # --device_features: the raw utterance travels; CMVN, the splice and the zero rows up to `longest` come from rsrgan_feat_batch
+    if _device_features(FLAGS):
+        # --device_features: the raw utterance travels (--device_decode: its bytes as the archive holds them, decoded on the device); CMVN, the splice and the zero rows up to `longest` come from rsrgan_feat_batch
         # (B = 1, T = longest), the same bits as the host lines below.  De-normalising the output_dim-wide result stays on the host.
         featurize = getattr(getattr(model, "engine", None), "featurize", None)
         if featurize is None:
@@ -224,7 +236,12 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None, moving_aver
         stats = (None, None) if cmvn is None else tuple(np.ascontiguousarray(cmvn[k], np.float64).reshape(-1)
                                                         for k in ("mean_inputs", "stddev_inputs"))
     for i, utt in enumerate(reader.utt_ids):
-        if featurize is not None:
+        if featurize is not None and _device_decode(FLAGS):
+            raw = reader.read_coded_from_index(i)
+            n = raw.rows
+            packed = pack_coded([raw], FLAGS.left_context, FLAGS.right_context, *stats, T=longest, names=[utt])
+            pad = featurize(packed, limit=False)[0][0]
+        elif featurize is not None:
             raw = reader.read_utt_data_from_index(i)
             n = raw.shape[0]
             packed = pack_utterances([raw], FLAGS.left_context, FLAGS.right_context, *stats, T=longest, names=[utt])

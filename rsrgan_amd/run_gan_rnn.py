@@ -21,7 +21,7 @@ import numpy as np
 
 from . import dist as rdist
 from .gan_rnn import GAN_RNN
-from .io import ArkReader, ArkWriter, PaddedBatchReader, pack_utterances, prefetch, splice_feats
+from .io import ArkReader, ArkWriter, PaddedBatchReader, pack_coded, pack_utterances, prefetch, splice_feats
 from .train import eval_one_iteration, exponential_decay, train_one_iteration
 
 
@@ -70,7 +70,19 @@ def build_parser():
     p.add_argument("--device_features", type=str2bool, nargs="?", const=True, default=False, help="CMVN, context splice and padding on the "
                    "device (csrc/feat.hip): the reader ships packed raw frames and an offset table instead of the expanded batch; "
                    "training, cross-validation and --decode; the same numbers bit for bit")
+    p.add_argument("--device_decode", type=str2bool, nargs="?", const=True, default=False, help="implies --device_features, and the archive "
+                   "is decoded on the device as well (csrc/feat.hip k_feat_decode): the reader ships each matrix's bytes as the file holds "
+                   "them -- float, double or Kaldi-compressed -- with no host decode; training, cross-validation and --decode; the same "
+                   "numbers bit for bit")
     return p
+
+
+def _device_decode(FLAGS):
+    return bool(getattr(FLAGS, "device_decode", False))
+
+
+def _device_features(FLAGS):
+    return bool(getattr(FLAGS, "device_features", False)) or _device_decode(FLAGS)
 
 
 def _cmvn(FLAGS):
@@ -84,7 +96,7 @@ def _cmvn(FLAGS):
 
 def _reader(FLAGS, inputs_scp, labels_scp, cmvn, shuffle, seed):
     return PaddedBatchReader(inputs_scp, labels_scp, FLAGS.batch_size * FLAGS.num_gpu, FLAGS.left_context, FLAGS.right_context,
-                             cmvn=cmvn, shuffle=shuffle, seed=seed, device_features=bool(getattr(FLAGS, "device_features", False)))
+                             cmvn=cmvn, shuffle=shuffle, seed=seed, device_features=_device_features(FLAGS), device_decode=_device_decode(FLAGS))
 
 
 def get_num_batch(reader, full):
@@ -224,8 +236,8 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
 
     host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
     finish = None
-    if getattr(FLAGS, "device_features", False):
-        # --device_features: the raw utterance travels, CMVN and the splice run on the device (HipEngine.featurize) and the generator reads
+    if _device_features(FLAGS):
+        # --device_features: the raw utterance travels (--device_decode: its bytes as the archive holds them, decoded on the device), CMVN and the splice run on the device (HipEngine.featurize) and the generator reads
         # the device tensor; the same bits as features() above.  The output is de-normalised on the device as well (HipEngine.denormalize,
         # rsrgan_feat_denorm: the product and the sum rounded separately, NumPy's bits) and comes back as the float64 matrix that is written.
         featurize = getattr(getattr(model, "engine", None), "featurize", None)
@@ -240,6 +252,9 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
                                                         for k in ("mean_inputs", "stddev_inputs"))
 
         def features(i):                                                     # noqa: F811 -- [n, D * (L + 1 + R)] on the device
+            if _device_decode(FLAGS):
+                coded = pack_coded([reader.read_coded_from_index(i)], FLAGS.left_context, FLAGS.right_context, *stats, names=[reader.utt_ids[i]])
+                return featurize(coded, limit=chunk <= 0)[0][0]
             packed = pack_utterances([reader.read_utt_data_from_index(i)], FLAGS.left_context, FLAGS.right_context, *stats,
                                      names=[reader.utt_ids[i]])
             return featurize(packed, limit=chunk <= 0)[0][0]                 # (chunked decode cuts the utterance itself)

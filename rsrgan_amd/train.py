@@ -45,8 +45,9 @@ def _dpipe():
 
 
 def is_packed(a):
-    """an io.PackedBatch: raw frames and offsets, to be normalised, spliced and padded on the device"""
-    return hasattr(a, "offsets") and hasattr(a, "rows") and hasattr(a, "data")
+    """an io.PackedBatch (raw frames and offsets) or an io.CodedBatch (the archive's bytes and offsets): to be normalised, spliced and
+    padded -- the latter decoded first -- on the device"""
+    return hasattr(a, "offsets") and hasattr(a, "rows") and (hasattr(a, "data") or hasattr(a, "blob"))
 
 
 def device_batch(model, inputs, labels, lengths, d_run=True):
