@@ -532,6 +532,36 @@ int rsrgan_feat_denorm(const float* y, const int32_t* lengths, int32_t B, int32_
 int rsrgan_feat_decode(const uint8_t* blob, int64_t blob_bytes, const int64_t* seg, const float* scale, const int32_t* offsets, int32_t B,
                        int32_t D, const double* mean, const double* stddev, float* out, int64_t out_rows, void* stream);
 
+/* ---- TensorBoard histogram summaries on the device (csrc/hist.hip): what tf.summary.histogram's HistogramProto holds,
+ * computed where the tensors are.  No handle.  x: a HOST table of n DEVICE pointers to float32 tensors; dims: a HOST table of n x
+ * (rows, cols, ld), tensor i being the strided 2-D view x[i][r * ld + c] (ld >= cols; ld = cols: dense).  out (DEVICE): n records of
+ * 5 + NL doubles, NL the length of the table rsrgan_hist_limits gives:
+ *   [0] min  [1] max  [2] num  [3] sum  [4] sum_squares  [5 + k] the count of bucket k
+ * Bucket of a value v, widened to double: the first limit greater than v, clamped to the last bucket (rsrgan_amd/summary.py histogram());
+ * -inf counts into the first bucket, +inf and NaN into the last; a NaN makes min, max, sum and sum_squares NaN.  A tensor without
+ * elements (rows or cols 0; its pointer may be NULL) yields the record of the single value 0.0.  min, max, num and the counts are exact;
+ * sum and sum_squares are fp64 sums in a fixed order: the record has the same bits run to run.  Two launches on `stream`; calls on
+ * different streams are ordered against each other by the entry (they share the launches' device memory), so it cannot be captured into
+ * a graph.  RSRGAN_ERR_INVALID before any device work, rsrgan_last_error() naming the argument, for: n below 1 or above 16; a null x,
+ * dims or out; out not 8-byte aligned; for a tensor: a negative rows, cols or ld; ld below cols; rows x cols above 2^31 - 1; ld above
+ * 2^40; a null or not 4-byte aligned pointer where there are elements. */
+int rsrgan_hist(int32_t n, const float* const* x, const int64_t* dims, double* out, void* stream);
+/* The bucket limits the kernel uses (TensorFlow's defaults: +-1e-12 * 1.1^k by repeated multiplication in double, +-DBL_MAX, 0.0),
+ * built once on the host: *n receives their count, out (HOST, may be NULL to ask for the count alone) the limits. */
+int rsrgan_hist_limits(double* out, int32_t* n);
+/* The discriminator logits of the most recent D-run (rsrgan_d_backward / rsrgan_d_step, training or not) as two dense DEVICE tensors
+ * [batch_size][T] float32, batch-major -- the reference's d_rl_logits / d_fk_logits [B, T, 1] (gan_rnn_placeholder.py:219-220): the
+ * caller's batch_size rows only (none of the rows that pad a batch to the kernels' row group), every frame including those past a row's
+ * length, as the reference's histograms see them.  With d_type dnn the values are the clipped ones discriminator_dnn returns
+ * (discriminator_dnn.py:93); a frame-level handle (g_type dnn / rced) has T = 1.  *T receives the frame count; real and fake may both be
+ * NULL to ask for it alone.  A G-run overwrites the logits with D(G(x)): call between the D-run and the G-run, in stream order.
+ * RSRGAN_ERR_INVALID on an inference handle, on a handle without a discriminator (RSRGAN_FLAG_SUPERVISED) and when no D-run's logits
+ * are at hand. */
+int rsrgan_d_logits(rsrgan_handle h, float* real, float* fake, int32_t* T, void* stream);
+/* rsrgan_hist of those two tensors (record 0: real, record 1: fake) straight from the handle's buffer, without the dense copies.
+ * out: DEVICE, 2 x (5 + NL) doubles.  The same refusals. */
+int rsrgan_d_logits_hist(rsrgan_handle h, double* out, void* stream);
+
 /* ---- the SEGAN operators (csrc/segan.hip and the window-GEMM primitives of csrc/segan.cpp).  Unit parity tests only
  * (tests/test_gpu_segan_ops.py, tests/test_op_args.py); no trainer calls them.  Each goes through the host function SeganModel calls
  * and never launches a kernel directly.  One entry per family: op selects the launcher; ptrs is a HOST table of device pointers,

@@ -31,6 +31,7 @@ SYMBOLS = ["rsrgan_default_cfg", "rsrgan_create", "rsrgan_destroy", "rsrgan_last
            "rsrgan_op_bn_forward", "rsrgan_op_bn_backward", "rsrgan_op_bn_commit", "rsrgan_op_bn_last_plan",
            "rsrgan_op_bn_seq_forward", "rsrgan_op_bn_seq_backward", "rsrgan_feat_batch", "rsrgan_feat_frames",
            "rsrgan_feat_stream", "rsrgan_feat_denorm", "rsrgan_feat_decode",
+           "rsrgan_hist", "rsrgan_hist_limits", "rsrgan_d_logits", "rsrgan_d_logits_hist",
            "rsrgan_op_segan_sizes", "rsrgan_op_segan_conv2", "rsrgan_op_segan_conv1", "rsrgan_op_segan_colred", "rsrgan_op_segan_last_plan",
            "rsrgan_op_segan_vbn", "rsrgan_op_segan_elem", "rsrgan_op_segan_dhead",
            "rsrgan_op_chunks", "rsrgan_op_update", "rsrgan_op_step_elem", "rsrgan_op_layout",
@@ -135,6 +136,10 @@ def load():
     lib.rsrgan_feat_stream.argtypes = [p, i64, p, p, i32, i32, i32, i32, i32, i32, p, p, p, p, vp]
     lib.rsrgan_feat_denorm.argtypes = [p, p, i32, i32, i32, p, p, p, vp]
     lib.rsrgan_feat_decode.argtypes = [p, i64, p, p, p, i32, i32, p, p, p, i64, vp]
+    lib.rsrgan_hist.argtypes = [i32, pp, C.POINTER(i64), p, vp]
+    lib.rsrgan_hist_limits.argtypes = [C.POINTER(C.c_double), C.POINTER(i32)]
+    lib.rsrgan_d_logits.argtypes = [vp, p, p, C.POINTER(i32), vp]
+    lib.rsrgan_d_logits_hist.argtypes = [vp, p, vp]
     lib.rsrgan_op_bn_commit.argtypes =[i32, pp, pp, C.POINTER(i32), i32, vp]
     lib.rsrgan_op_bn_last_plan.argtypes = [C.POINTER(i32)]
     lib.rsrgan_op_segan_sizes.argtypes = [i32, C.POINTER(i64), C.POINTER(i64)]
@@ -200,6 +205,24 @@ BN_VARS = ("beta", "gamma", "moving_mean", "moving_variance", "renorm_mean", "re
 def ptr_table(ptrs):
     """a C array of device pointers (None stays NULL) for the batched operator entries"""
     return (C.c_void_p * max(len(ptrs), 1))(*[None if q is None else q for q in ptrs])
+
+
+_hist_limits = None
+
+
+def hist_limits():
+    """the bucket limits of rsrgan_hist (rsrgan_hist_limits: built in C++, on the host) as a float64 array; no device is needed"""
+    global _hist_limits
+    if _hist_limits is None:
+        import numpy as np
+        lib = load()
+        n = C.c_int32()
+        check(lib.rsrgan_hist_limits(None, C.byref(n)))
+        buf = (C.c_double * n.value)()
+        check(lib.rsrgan_hist_limits(buf, C.byref(n)))
+        _hist_limits = np.frombuffer(buf, np.float64).copy()
+        _hist_limits.setflags(write=False)
+    return _hist_limits
 
 
 def check(rc):

@@ -595,4 +595,85 @@ int rsrgan_feat_decode(const uint8_t* blob, int64_t blob_bytes, const int64_t* s
   OP_LAUNCHED("feat_decode");
 }
 
+// ---- TensorBoard histograms on the device (hist.hip): no handle; two launches on the caller's stream
+int rsrgan_hist_limits(double* out, int32_t* n) {
+  OP_REFUSE(!n, "hist_limits: null pointer (n)");
+  return guard("rsrgan_hist_limits", [&]() -> int {
+    const std::vector<double>& t = hist_limits();
+    *n = (int32_t)t.size();
+    if (out) std::memcpy(out, t.data(), t.size() * sizeof(double));
+    return RSRGAN_OK;
+  });
+}
+
+int rsrgan_hist(int32_t n, const float* const* x, const int64_t* dims, double* out, void* stream) {
+  OP_REFUSE(n < 1, "hist: n = %d: at least one tensor is needed", n);
+  OP_REFUSE(n > HIST_MAX_TENSORS, "hist: n = %d above the entry's %d tensors per call", n, HIST_MAX_TENSORS);
+  OP_REFUSE(!x || !dims || !out, "hist: null pointer (x, dims or out)");
+  OP_REFUSE((size_t)out & 7, "hist: out not 8-byte aligned");
+  HistView v[HIST_MAX_TENSORS];
+  for (int i = 0; i < n; ++i) {
+    const int64_t rows = dims[3 * i], cols = dims[3 * i + 1], ld = dims[3 * i + 2];
+    OP_REFUSE(rows < 0 || cols < 0 || ld < 0, "hist: tensor %d: negative size (rows %lld, cols %lld, ld %lld)", i, (long long)rows, (long long)cols,
+              (long long)ld);
+    OP_REFUSE(ld < cols, "hist: tensor %d: leading dimension ld = %lld below its row of %lld", i, (long long)ld, (long long)cols);
+    const int64_t lim = 0x7FFFFFFF;                        // element indices are 32 bits wide (hist.hip)
+    OP_REFUSE(rows > lim || cols > lim || (rows && cols > lim / rows), "hist: tensor %d: rows x cols = %lld x %lld above the entry's 2^31 - 1 elements",
+              i, (long long)rows, (long long)cols);
+    OP_REFUSE(ld > ((int64_t)1 << 40), "hist: tensor %d: ld = %lld above the entry's 2^40", i, (long long)ld);
+    const bool empty = rows == 0 || cols == 0;
+    OP_REFUSE(!x[i] && !empty, "hist: tensor %d: null pointer (x[%d]) with %lld x %lld elements: only a tensor without elements may be null", i, i,
+              (long long)rows, (long long)cols);
+    OP_REFUSE((size_t)x[i] & 3, "hist: tensor %d: x[%d] not 4-byte aligned", i, i);
+    v[i] = HistView{empty ? nullptr : x[i], (long long)ld, 1, empty ? 0u : (unsigned)rows, empty ? 0u : (unsigned)cols, 0};
+  }
+  if (!launch_hist(n, v, 0.f, 0.f, out, (hipStream_t)stream)) { set_error("hist: the launches' device memory or stream order could not be set up"); return RSRGAN_ERR_HIP; }
+  OP_LAUNCHED("hist");
+}
+
+// the D-run's logits: which handles have them, and where they lie (model.h dlog_*)
+static int dlogits_check(rsrgan_handle h, const char* what) {
+  CHECK_H(h);
+  REFUSE_INFER(h, what, RSRGAN_ERR_INVALID);
+  Model& m = h->m;
+  if (m.supervised() || !m.logits) { set_error("%s: the handle has no discriminator (RSRGAN_FLAG_SUPERVISED)", what); return RSRGAN_ERR_INVALID; }
+  if (m.dlog_T <= 0) {
+    set_error("%s: no D-run's logits at hand: call rsrgan_d_backward / rsrgan_d_step first (a G-run overwrites them with D(G(x)) alone)", what);
+    return RSRGAN_ERR_INVALID;
+  }
+  return RSRGAN_OK;
+}
+
+int rsrgan_d_logits(rsrgan_handle h, float* real, float* fake, int32_t* T, void* stream) {
+  if (int rc = dlogits_check(h, "rsrgan_d_logits")) return rc;
+  Model& m = h->m;
+  if (!T) { set_error("rsrgan_d_logits: null pointer (T)"); return RSRGAN_ERR_INVALID; }
+  if ((real == nullptr) != (fake == nullptr)) { set_error("rsrgan_d_logits: real and fake must both be given, or both be null to ask for T alone"); return RSRGAN_ERR_INVALID; }
+  *T = m.dlog_T;
+  if (!real) return RSRGAN_OK;
+  return guard("rsrgan_d_logits", [&]() -> int {
+    StreamScope sc(m, stream);
+    launch_logits_dense(m.logits, m.dlog_rows, m.Bt, m.dlog_T, real, m.d_dnn(), D_CLIP_LO, D_CLIP_HI, sc.work);
+    launch_logits_dense(m.logits + m.dlog_fake0 * 4, m.dlog_rows, m.Bt, m.dlog_T, fake, m.d_dnn(), D_CLIP_LO, D_CLIP_HI, sc.work);
+    if (hipGetLastError() != hipSuccess) { set_error("kernel launch failed in d_logits"); return RSRGAN_ERR_HIP; }
+    return RSRGAN_OK;
+  });
+}
+
+int rsrgan_d_logits_hist(rsrgan_handle h, double* out, void* stream) {
+  if (int rc = dlogits_check(h, "rsrgan_d_logits_hist")) return rc;
+  Model& m = h->m;
+  if (!out || ((size_t)out & 7)) { set_error("rsrgan_d_logits_hist: out is null or not 8-byte aligned"); return RSRGAN_ERR_INVALID; }
+  return guard("rsrgan_d_logits_hist", [&]() -> int {
+    StreamScope sc(m, stream);
+    // frames x the caller's rows of each half, where they lie: row stride one frame, column stride one row of `logits`
+    HistView v[2];
+    for (int k = 0; k < 2; ++k)
+      v[k] = HistView{m.logits + (k ? m.dlog_fake0 * 4 : 0), (long long)m.dlog_rows * 4, 4, (unsigned)m.dlog_T, (unsigned)m.Bt, m.d_dnn() ? 1 : 0};
+    if (!launch_hist(2, v, D_CLIP_LO, D_CLIP_HI, out, sc.work)) { set_error("rsrgan_d_logits_hist: the launches' device memory or stream order could not be set up"); return RSRGAN_ERR_HIP; }
+    if (hipGetLastError() != hipSuccess) { set_error("kernel launch failed in d_logits_hist"); return RSRGAN_ERR_HIP; }
+    return RSRGAN_OK;
+  });
+}
+
 }  // extern "C"

@@ -7,7 +7,7 @@
 
 namespace rsr {
 
-static const float kDClipLo = -0.5f, kDClipHi = 1.5f;     // discriminator_dnn.py:93 tf.clip_by_value(y, -0.5, 1.5)
+static const float kDClipLo = D_CLIP_LO, kDClipHi = D_CLIP_HI;     // discriminator_dnn.py:93 tf.clip_by_value(y, -0.5, 1.5)
 
 BnVars Model::bn_vars(const ParamSet& ps, const int (&tbn)[8]) const {
   BnVars v;
@@ -214,6 +214,7 @@ int Model::dnn_d_backward(const float* x, const float* labels, int T, float* out
   }
   if (out_losses) launch_copy_f(losses, out_losses, 3, s);
   HIPC(hipGetLastError());
+  dlog_T = T; dlog_rows = B; dlog_fake0 = (size_t)R;       // logits rows [0, R) real, [R, 2R) fake, row t * B + b each
   return RSRGAN_OK;
 }
 

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "switches.h"
 
 namespace rsr {
@@ -478,6 +480,24 @@ void launch_feat_denorm(const float* y, const int* lengths, int B, int T, int D,
 // blob and out 16-byte aligned, out_rows * D <= 2^40, mean / stddev [D] double or both null.
 void launch_feat_decode(const uint8_t* blob, long long blob_bytes, const long long* seg, const float* scale, const int* offsets, int B, int D,
                         const double* mean, const double* stddev, float* out, long long out_rows, hipStream_t s);
+// ---- TensorBoard histograms on the device (hist.hip): for each of n <= HIST_MAX_TENSORS strided float32 views (element (r, c) at
+// x[r * ld + c * cs]; rows * cols <= 2^31 - 1; x may be null where rows * cols == 0) one record of HIST_REC doubles in out: min, max, num,
+// sum, sum_squares and the count of each of the HIST_NL buckets of TensorFlow's default limits (hist_limits(), built once on the host).
+// clip: the view's values pass through clamp(clip_lo, clip_hi) first (discriminator_dnn's logits).  Two launches on s; false: the launches'
+// own device memory could not be made (first call), or the stream refused the order against the call before.  Not capturable.
+constexpr int HIST_MAX_TENSORS = 16;
+constexpr int hist_nl() {
+  int k = 0;
+  for (double v = 1e-12; v < 1e20; v *= 1.1) ++k;
+  return 2 * (k + 1) + 1;
+}
+constexpr int HIST_NL = hist_nl();
+constexpr int HIST_REC = 5 + HIST_NL;
+struct HistView { const float* x; long long ld, cs; unsigned rows, cols; int clip; };
+const std::vector<double>& hist_limits();
+bool launch_hist(int n, const HistView* views, float clip_lo, float clip_hi, double* out, hipStream_t s);
+// the discriminator's logits ([rows][4], column 0, frame t's row b at t * frame_rows + b) as a dense batch-major [B][T] tensor
+void launch_logits_dense(const float* logits, int frame_rows, int B, int T, float* out, bool clip, float clip_lo, float clip_hi, hipStream_t s);
 void launch_colsum(const float* a, int lda, const float* b, int ldb, float* out, int rows, int cols,
                    float* scratch /* >= 64*cols floats */, hipStream_t s);
 

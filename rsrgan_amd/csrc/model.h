@@ -211,6 +211,9 @@ struct BnlFold {
 };
 void launch_bnl_fold(const BnlFold& a, hipStream_t s);
 
+// discriminator_dnn.py:93 tf.clip_by_value(y, -0.5, 1.5): `logits` holds the value in front of the clip, every reader applies it
+constexpr float D_CLIP_LO = -0.5f, D_CLIP_HI = 1.5f;
+
 struct Model {
   rsrgan_cfg cfg{};
   const HandleSwitches sw;       // the handle-scope rows of switches.h, read when rsrgan_create constructs the handle; never written
@@ -234,6 +237,11 @@ struct Model {
   float *g_dA = nullptr, *g_dB = nullptr, *g_dC = nullptr;   // ping-pong gradient buffers [T*B][max ld]
   // discriminator activations (N = 2B rows per frame)
   float *xd = nullptr, *logits = nullptr, *dlogits = nullptr;
+  // The logits of the most recent D-run, for rsrgan_d_logits / rsrgan_d_logits_hist: `logits` is [rows][4], column 0; frame t's row b is
+  // row t * dlog_rows + b, the real half from row 0, the fake half from row dlog_fake0 on.  dlog_T = 0: none (no D-run yet, or a G-run
+  // has overwritten them with D(G(x)) alone).
+  int dlog_T = 0, dlog_rows = 0;
+  size_t dlog_fake0 = 0;
   std::vector<LstmStash> d_st;
   float *d_dA = nullptr, *d_dB = nullptr, *last_dx0 = nullptr;
   int *len_dev = nullptr;        // [2B]: lengths duplicated for the real|fake stacked batch

@@ -511,6 +511,7 @@ int Model::d_backward(const float* x, const float* labels, const int32_t* length
     d_run_head_backward(p, s);
     if (p.inl) apply_body(RSRGAN_NET_D, s);
   });
+  dlog_T = T; dlog_rows = 2 * B; dlog_fake0 = (size_t)B;      // logits row t * 2B + n: n < B real, the rest fake
   d_partial_fresh = false;        // (a later rsrgan_apply -- after the caller's all-reduce -- squares the gradients it finds)
   g_fwd_valid = true;
   if (p.inl) apply_inlined |= 2;
@@ -703,6 +704,7 @@ void Model::g_run_tail(const GRunPlan& p, hipStream_t s) {
 int Model::g_backward(const float* x, const float* labels, const int32_t* lengths, int T, const float* nf,
                       float* out_losses, bool want_grads, bool reuse, hipStream_t s) {
   if (!labels) { set_error("labels required"); return RSRGAN_ERR_INVALID; }
+  dlog_T = 0;                                      // the run's discriminator head writes D(G(x)) over the D-run's logits
   if (g_dnn()) return dnn_g_backward(x, labels, T, out_losses, want_grads, reuse, s);
   if (g_bnl()) return bnl_step(x, labels, lengths, T, out_losses, want_grads, s);
   bn_eval_call = !want_grads;                      // (is_training of this fetch)

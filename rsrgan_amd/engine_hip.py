@@ -682,6 +682,25 @@ class HipEngine(OpEntries):      # (the handle-free rsrgan_op_* wrappers and lau
         self._keep2 = (x, lab, ln, nf)
         return out
 
+    # -- the D-run's logits and their histograms (include/rsrgan.h rsrgan_d_logits, rsrgan_d_logits_hist; csrc/hist.hip) -----
+    def d_logits(self):
+        """(real, fake): the discriminator's logits of the most recent d_backward as two [batch_size, T] float32 device tensors (the
+        reference's d_rl_logits / d_fk_logits [B, T, 1]; with d_type dnn the clipped values).  Call before the next g_backward: it
+        writes D(G(x)) over them."""
+        T = C.c_int32()
+        check(self.lib.rsrgan_d_logits(self.h, None, None, C.byref(T), self._stream()))
+        real = torch.empty(self.batch_size, T.value, dtype=torch.float32, device=self.device)
+        fake = torch.empty_like(real)
+        check(self.lib.rsrgan_d_logits(self.h, _ptr(real), _ptr(fake), C.byref(T), self._stream()))
+        return real, fake
+
+    def d_logits_hist(self) -> torch.Tensor:
+        """[2, 5 + NL] float64 device tensor: the histogram records (summary.histogram_stats) of d_logits()' two tensors, read straight
+        from the library's buffer"""
+        out = torch.empty(2, 5 + len(_lib.hist_limits()), dtype=torch.float64, device=self.device)
+        check(self.lib.rsrgan_d_logits_hist(self.h, _ptr(out), self._stream()))
+        return out
+
     def apply(self, net: int):
         self._training_only('apply')
         check(self.lib.rsrgan_apply(self.h, net, self._stream()))

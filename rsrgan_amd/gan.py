@@ -31,6 +31,7 @@ class GAN(Model):
         self.batch_size, self.devices = args.batch_size, devices
         self.num_gpu = getattr(args, "num_gpu", 1)
         self.save_dir = getattr(args, "save_dir", None)
+        self.device_summaries = bool(getattr(args, "device_summaries", False))
         self.l2_scale = getattr(args, "l2_scale", 0.0)
         self.input_dim, self.output_dim = args.input_dim, args.output_dim
         self.left_context, self.right_context = getattr(args, "left_context", 0), getattr(args, "right_context", 0)
@@ -132,6 +133,7 @@ class GAN(Model):
         """collective-free (only the writer's rank calls it): the engine directly, on the batch this rank drew"""
         x, lab = self._frames(inputs), self._frames(labels)
         d = self.engine.d_backward(x, lab, None, train=False, apply=False)
+        self._logit_summaries()
         g = self.engine.g_backward(x, lab, None, train=False, reuse=False, apply=False)
         return d, g, inputs, labels, self.forward(inputs)
 

@@ -79,9 +79,35 @@ class Model(object):
         # on this rank's shard of the fed batch and calls the engine directly (d_step / g_step gather the towers' losses, and the
         # other ranks are already in their next gradient all-reduce).  The summary describes tower 0, as the reference's
         # tf.summary ops do (gan_rnn_placeholder.py:219-223 are built in tower 0's name scope).
-        d, g, x, lab, y = self._summary_fetch(inputs, labels, lengths)
         host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-        return model_summaries([float(v) for v in list(host(d).reshape(-1)) + list(host(g).reshape(-1))], host(x), host(lab), host(y))
+        if not (getattr(self, "device_summaries", False) and hasattr(self.engine, "hist")):
+            d, g, x, lab, y = self._summary_fetch(inputs, labels, lengths)
+            return model_summaries([float(v) for v in list(host(d).reshape(-1)) + list(host(g).reshape(-1))], host(x), host(lab), host(y))
+        # args.device_summaries: the histograms are computed where the tensors are (csrc/hist.hip) and only their records travel.  The
+        # discriminator's logits exist between the fetch's two runs alone (the G-run writes D(G(x)) over them): _logit_summaries takes
+        # their records there, in stream order.  A trainer without a discriminator never calls it and writes three histograms.
+        self._logit_stats, self._want_logit_stats = None, True
+        try:
+            d, g, x, lab, y = self._summary_fetch(inputs, labels, lengths)
+        finally:
+            self._want_logit_stats = False
+        tags = ("real_clean", "real_noise", "g_clean")
+        with (self.on_stream() if hasattr(self, "on_stream") else contextlib.nullcontext()):
+            recs = self.engine.hist([self.engine._f32(a) for a in (x, lab, y)])
+            if self._logit_stats is not None:
+                recs, tags = torch.cat([self._logit_stats, recs]), ("d_real", "d_fake") + tags
+        stats = dict(zip(tags, host(recs)))                  # one copy: five records of 5 + 1551 doubles
+        self._logit_stats = None
+        return model_summaries([float(v) for v in list(host(d).reshape(-1)) + list(host(g).reshape(-1))], stats=stats)
+
+    device_summaries = False         # args.device_summaries (run_*.py --device_summaries): run_summaries' histograms on the device
+    _want_logit_stats = False
+    _logit_stats = None
+
+    def _logit_summaries(self):
+        """called by a _summary_fetch between its D-run and its G-run: on the device route, the histogram records of the D-run's logits"""
+        if self._want_logit_stats and hasattr(self.engine, "d_logits_hist"):
+            self._logit_stats = self.engine.d_logits_hist()
 
     inference_only = False           # GAN_RNN(..., inference_only=True): the generator's variables only, forward calls only
 
@@ -236,6 +262,7 @@ class GAN_RNN(Model):
         self.devices = devices
         self.num_gpu = getattr(args, "num_gpu", 1)
         self.save_dir = getattr(args, "save_dir", None)
+        self.device_summaries = bool(getattr(args, "device_summaries", False))
         self.l2_scale = getattr(args, "l2_scale", 0.0)
         self.input_dim = args.input_dim
         self.output_dim = args.output_dim
@@ -412,6 +439,7 @@ class GAN_RNN(Model):
         x, lab, ln = self._shard(inputs), self._shard(labels), self._shard(lengths)
         with self.on_stream():
             d = self.engine.d_backward(x, lab, ln, self._draw_noise(), self._draw_noise(), train=False, apply=False)
+            self._logit_summaries()
             g = self.engine.g_backward(x, lab, ln, self._draw_noise(), train=False, reuse=False, apply=False)
             y = self.engine.forward_g(x, ln)
         return d, g, x, lab, y

@@ -46,6 +46,40 @@ class OpEntries:
         check(self.lib.rsrgan_op_launch_floor(n, mode, C.byref(us), self._stream()))
         return us.value
 
+    # -- TensorBoard histograms on the device (include/rsrgan.h rsrgan_hist, csrc/hist.hip): a product entry that needs no handle ------
+    HIST_MAX_TENSORS = 16          # csrc/kernels.h: tensors per call of the entry
+
+    def hist_limits(self):
+        """the bucket limits the kernel uses (rsrgan_hist_limits) as a float64 array: summary._LIMITS bit for bit"""
+        return _lib.hist_limits()
+
+    def hist(self, tensors) -> torch.Tensor:
+        """[len(tensors), 5 + NL] float64 device tensor: one histogram record (summary.histogram_stats) per float32 device tensor, on
+        the current stream.  A tensor is read where it lies if it is contiguous, or 2-D with unit column stride (a view with a leading
+        dimension: logits[:, :1] of a [rows, 4] buffer); anything else is made contiguous first."""
+        views, keep = [], []
+        for t in tensors:
+            if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.float32:
+                raise ValueError("hist: float32 tensors on %s are needed" % (self.device,))
+            if t.numel() == 0:
+                views.append((None, 0, 0, 0))
+            elif t.is_contiguous():
+                views.append((t, 1, t.numel(), t.numel()))
+            elif t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+                views.append((t, t.shape[0], t.shape[1], t.stride(0)))
+            else:
+                c = t.contiguous()
+                keep.append(c)
+                views.append((c, 1, c.numel(), c.numel()))
+        nl = len(self.hist_limits())
+        out = torch.empty(len(views), 5 + nl, dtype=torch.float64, device=self.device)
+        for i in range(0, len(views), self.HIST_MAX_TENSORS):
+            part = views[i:i + self.HIST_MAX_TENSORS]
+            dims = (C.c_int64 * (3 * len(part)))(*[int(v) for _, r, c, ld in part for v in (r, c, ld)])
+            check(self.lib.rsrgan_hist(len(part), self._table([v[0] for v in part]), dims, _ptr(out[i:]), self._stream()))
+        self._keep_hist = (tensors, keep)          # borrowed until the stream has consumed them
+        return out
+
     def op_gemm(self, A, a_kc, B, b_kc, C_, M, N, K, bias=None, act=0, alpha=0.3, accumulate=False):
         check(self.lib.rsrgan_op_gemm(_ptr(A), A.stride(0), 1 if a_kc else 0, _ptr(B), B.stride(0), 1 if b_kc else 0,
                                       _ptr(C_), C_.stride(0), M, N, K, _ptr(bias), act, alpha, 1 if accumulate else 0,

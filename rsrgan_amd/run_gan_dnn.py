@@ -66,6 +66,9 @@ def build_parser():
     p.add_argument("--device_features", type=str2bool, nargs="?", const=True, default=False, help="CMVN and context splice on the device: "
                    "the shuffle queue's utterances stay resident there, normalised once, and one HIP kernel gathers every batch "
                    "(HipEngine.featurize_frames); same batches as the host path, bit for bit")
+    p.add_argument("--device_summaries", type=str2bool, nargs="?", const=True, default=False, help="the TensorBoard histograms of the "
+                   "training and cross-validation summaries are computed on the device (csrc/hist.hip) and the discriminator's logits get "
+                   "theirs (d_real, d_fake); off: three histograms computed on the host")
     p.add_argument("--device_decode", type=str2bool, nargs="?", const=True, default=False, help="implies --device_features, and the archive "
                    "is decoded on the device as well (csrc/feat.hip k_feat_decode): every utterance enters the pool as the bytes the file "
                    "holds -- float, double or Kaldi-compressed -- with no host decode; training, cross-validation and --decode; same "

@@ -70,6 +70,9 @@ def build_parser():
     p.add_argument("--device_features", type=str2bool, nargs="?", const=True, default=False, help="CMVN, context splice and padding on the "
                    "device (csrc/feat.hip): the reader ships packed raw frames and an offset table instead of the expanded batch; "
                    "training, cross-validation and --decode; the same numbers bit for bit")
+    p.add_argument("--device_summaries", type=str2bool, nargs="?", const=True, default=False, help="the TensorBoard histograms of the "
+                   "training and cross-validation summaries are computed on the device (csrc/hist.hip) and the discriminator's logits get "
+                   "theirs (d_real, d_fake); off: three histograms computed on the host")
     p.add_argument("--device_decode", type=str2bool, nargs="?", const=True, default=False, help="implies --device_features, and the archive "
                    "is decoded on the device as well (csrc/feat.hip k_feat_decode): the reader ships each matrix's bytes as the file holds "
                    "them -- float, double or Kaldi-compressed -- with no host decode; training, cross-validation and --decode; the same "

@@ -58,6 +58,9 @@ def build_parser():
                    "(run_gan_rnn --decode_push)")
     p.add_argument("--device_features", type=str2bool, nargs="?", const=True, default=False, help="CMVN, context splice and padding on the "
                    "device (run_gan_rnn --device_features)")
+    p.add_argument("--device_summaries", type=str2bool, nargs="?", const=True, default=False, help="the TensorBoard histograms of the "
+                   "training and cross-validation summaries are computed on the device (csrc/hist.hip) and the discriminator's logits get "
+                   "theirs (d_real, d_fake); off: three histograms computed on the host")
     p.add_argument("--device_decode", type=str2bool, nargs="?", const=True, default=False, help="implies --device_features; the archive's "
                    "bytes travel undecoded and the device decodes them (run_gan_rnn --device_decode)")
     return p

@@ -94,14 +94,29 @@ def scalar(tag: str, value) -> bytes:
     return _f_bytes(1, _f_bytes(1, tag.encode()) + _f_float(2, value))
 
 
-def histogram(tag: str, values) -> bytes:
-    """one Summary.Value {tag, histo}: min, max, num, sum, sum_squares, bucket_limit[], bucket[] (histogram.cc EncodeToProto)"""
+STATS_HEAD = 5            # a histogram record: min, max, num, sum, sum_squares, then the count of every bucket of _LIMITS
+
+
+def histogram_stats(values) -> np.ndarray:
+    """the record of one tensor: [min, max, num, sum, sum_squares, count of bucket 0, ...] as float64 -- what csrc/hist.hip computes on
+    the device (include/rsrgan.h rsrgan_hist), here with NumPy.  An empty tensor gives the record of the single value 0.0."""
     x = np.asarray(values, np.float64).ravel()
     if x.size == 0:
         x = np.zeros(1)
     idx = np.searchsorted(_LIMITS, x, side="right")            # upper_bound: the first limit greater than the value
     counts = np.bincount(np.minimum(idx, len(_LIMITS) - 1), minlength=len(_LIMITS)).astype(np.float64)
-    limits, buckets, i, n = [], [], 0, len(_LIMITS)
+    return np.concatenate([np.array([x.min(), x.max(), x.size, x.sum(), np.square(x).sum()], np.float64), counts])
+
+
+def histogram_from_stats(tag: str, stats) -> bytes:
+    """one Summary.Value {tag, histo} from a record (histogram_stats, or a row of HipEngine.hist): min, max, num, sum, sum_squares,
+    bucket_limit[], bucket[] with runs of empty buckets collapsed into one (histogram.cc EncodeToProto)"""
+    stats = np.asarray(stats, np.float64).ravel()
+    n = len(_LIMITS)
+    if stats.size != STATS_HEAD + n:
+        raise ValueError("a histogram record holds %d doubles, got %d" % (STATS_HEAD + n, stats.size))
+    counts = stats[STATS_HEAD:]
+    limits, buckets, i = [], [], 0
     while i < n:
         end, count = _LIMITS[i], counts[i]
         i += 1
@@ -110,9 +125,14 @@ def histogram(tag: str, values) -> bytes:
                 end, count = _LIMITS[i], counts[i]
                 i += 1
         limits.append(end); buckets.append(count)
-    h = (_f_double(1, x.min()) + _f_double(2, x.max()) + _f_double(3, x.size) + _f_double(4, x.sum()) + _f_double(5, np.square(x).sum()) +
+    h = (_f_double(1, stats[0]) + _f_double(2, stats[1]) + _f_double(3, stats[2]) + _f_double(4, stats[3]) + _f_double(5, stats[4]) +
          _f_packed_doubles(6, limits) + _f_packed_doubles(7, buckets))
     return _f_bytes(1, _f_bytes(1, tag.encode()) + _f_bytes(5, h))
+
+
+def histogram(tag: str, values) -> bytes:
+    """one Summary.Value {tag, histo} of a tensor's values"""
+    return histogram_from_stats(tag, histogram_stats(values))
 
 
 def merge(values: Iterable[bytes]) -> bytes:
@@ -152,14 +172,21 @@ class FileWriter:
 LOSS_TAGS = ("d_rl_loss", "d_fk_loss", "d_loss", "g_adv_loss", "g_mse_loss", "g_l2_loss", "g_loss")
 
 
-def model_summaries(losses7, inputs=None, labels=None, g=None) -> bytes:
-    """`model.summaries` of the reference graphs: the seven loss scalars and the histograms of the fed batch and of the
-    generator's output -- with the reference's tags ('real_clean' is fed `inputs` and 'real_noise' `labels`,
-    gan_rnn_placeholder.py:221-222).  The histograms of the discriminator logits ('d_real', 'd_fake') need tensors the C ABI does
-    not hand out and are left out."""
+HIST_TAGS = ("d_real", "d_fake", "real_clean", "real_noise", "g_clean")
+
+
+def model_summaries(losses7, inputs=None, labels=None, g=None, d_real=None, d_fake=None, stats=None) -> bytes:
+    """`model.summaries` of the reference graphs: the seven loss scalars and the histograms of the discriminator's logits, of the fed
+    batch and of the generator's output, in the reference's order and with its tags ('real_clean' is fed `inputs` and 'real_noise'
+    `labels`, gan_rnn_placeholder.py:219-223,285-296).  A histogram is written for every tensor given; `stats` ({tag: record}, what
+    histogram_stats or the device route's HipEngine.hist computes) stands in for the tensor of its tag.  d_real / d_fake are the
+    discriminator's logits (HipEngine.d_logits); a model without a discriminator has none."""
     vals = [scalar(t, v) for t, v in zip(LOSS_TAGS, losses7)]
-    for tag, a in (("real_clean", inputs), ("real_noise", labels), ("g_clean", g)):
-        if a is not None:
+    stats = stats or {}
+    for tag, a in zip(HIST_TAGS, (d_real, d_fake, inputs, labels, g)):
+        if tag in stats:
+            vals.append(histogram_from_stats(tag, stats[tag]))
+        elif a is not None:
             vals.append(histogram(tag, a))
     return merge(vals)
 
