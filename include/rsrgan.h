@@ -531,6 +531,39 @@ int rsrgan_feat_denorm(const float* y, const int32_t* lengths, int32_t B, int32_
  * 4-byte aligned; B, D, blob_bytes or out_rows below 1; out_rows * D above 2^40. */
 int rsrgan_feat_decode(const uint8_t* blob, int64_t blob_bytes, const int64_t* seg, const float* scale, const int32_t* offsets, int32_t B,
                        int32_t D, const double* mean, const double* stddev, float* out, int64_t out_rows, void* stream);
+/* The waveform side (csrc/wave.hip): PCM samples -> the RAW log-power-spectrum (LPS) rows every other entry starts from,
+ * out [out_rows][P / 2 + 1] float32, one launch, no handle.  The definition is Kaldi's compute-spectrogram-feats --dither=0
+ * --window-type=hamming with its other defaults, stated here in full.  Constants of the recipes: N = 400 samples per frame (25 ms at
+ * 16 kHz), shift S = 160, padded length P = 512, NB = P / 2 + 1 = 257 bins, eps = FLT_EPSILON.
+ *   samples      pcm, kind 0: int16, widened to float without scaling (as Kaldi's wave reader does); kind 1: float32, taken as already
+ *                on that scale.  Utterance b is samples seg[b] = (first sample, sample count), n = the count.
+ *   frame count  F_b = n < N ? 0 : 1 + (n - N) / S  (snip-edges); frame f is samples [f * S, f * S + N) of the utterance.
+ *   per frame, on v[0 .. N):
+ *     1. v -= (sum v) / N
+ *     2. E = log(max(sum v^2, eps))                       the raw energy: before pre-emphasis and before the window
+ *     3. v'[i] = v[i] - preemph * v[i - 1] for i >= 1,  v'[0] = v[0] - preemph * v[0]         (the old values on the right)
+ *     4. v'[i] *= window[i]
+ *     5. zero-pad to P;  X = DFT_P(v');  p_k = |X_k|^2                                         k = 0 .. P / 2
+ *     6. out[k] = log(max(p_k, eps)) for k = 1 .. P / 2,  out[0] = E
+ *   rows         frame f of utterance b goes to row offsets[b] + f, for f < min(F_b, offsets[b + 1] - offsets[b]); rows that belong to no
+ *                utterance are not written.
+ * window [N] float32 is the caller's table, so the kernel is window-agnostic (rsrgan_amd/io/wave.py builds Hamming,
+ * 0.54 - 0.46 cos(2 pi i / (N - 1)), and Povey, (0.5 - 0.5 cos)^0.85, in fp64 and rounds once).  twiddle [P / 2][2] float32 =
+ * (cos, -sin)(2 pi j / P), j < P / 2, built the same way: the kernel calls no sincosf and sums in a fixed order, so a frame has the same
+ * bits run to run, whatever its utterance's place in the batch.  Arithmetic: fp32 throughout; the real FFT is a P / 2-point complex FFT
+ * (radix 4) and a split pass.  out is then an ordinary `raw` for rsrgan_feat_batch, or `fresh` for rsrgan_feat_stream.  The segment is
+ * clamped into [0, n_samples), every sample index too, and every destination row into [0, out_rows): the kernel reads and writes nothing
+ * outside its buffers, whatever the device-resident tables hold.  An utterance starts at any sample: pcm is only asked to be aligned
+ * to its element.  All pointers are DEVICE pointers.  RSRGAN_ERR_INVALID before the first HIP call, rsrgan_last_error() naming the
+ * argument, for: a null pcm, seg, offsets, out, window or twiddle; a kind other than 0 or 1; pcm not aligned to its element size (2 or
+ * 4 bytes); out not 16-byte, seg not 8-byte, offsets, window or twiddle not 4-byte aligned; B, n_samples or out_rows below 1; P no
+ * power of two in [64, 2048]; not 1 <= S <= N <= P; preemph outside [0, 1] (or NaN); out_rows * (P / 2 + 1) above 2^40. */
+int rsrgan_feat_wave(const void* pcm, int32_t kind, int64_t n_samples, const int64_t* seg, const int32_t* offsets, int32_t B, int32_t N,
+                     int32_t S, int32_t P, float preemph, const float* window, const float* twiddle, float* out, int64_t out_rows,
+                     void* stream);
+/* The frames one workgroup of rsrgan_feat_wave takes (consecutive frames of one utterance, whose overlapping samples it reads once);
+ * 0 for a P the entry refuses.  Tests place their utterance lengths around it. */
+int rsrgan_feat_wave_frames(int32_t P);
 
 /* ---- TensorBoard histogram summaries on the device (csrc/hist.hip): what tf.summary.histogram's HistogramProto holds,
  * computed where the tensors are.  No handle.  x: a HOST table of n DEVICE pointers to float32 tensors; dims: a HOST table of n x

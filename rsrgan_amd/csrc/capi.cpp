@@ -595,6 +595,30 @@ int rsrgan_feat_decode(const uint8_t* blob, int64_t blob_bytes, const int64_t* s
   OP_LAUNCHED("feat_decode");
 }
 
+// ---- the waveform front end (wave.hip): no handle, one launch on the caller's stream
+int rsrgan_feat_wave(const void* pcm, int32_t kind, int64_t n_samples, const int64_t* seg, const int32_t* offsets, int32_t B, int32_t N, int32_t S,
+                     int32_t P, float preemph, const float* window, const float* twiddle, float* out, int64_t out_rows, void* stream) {
+  OP_REFUSE(!pcm || !seg || !offsets || !out, "feat_wave: null pointer (pcm, seg, offsets or out)");
+  OP_REFUSE(!window || !twiddle, "feat_wave: null pointer (window or twiddle)");
+  OP_REFUSE(kind != 0 && kind != 1, "feat_wave: kind = %d is neither 0 (int16) nor 1 (float32)", kind);
+  OP_REFUSE((size_t)pcm & (kind ? 3 : 1), "feat_wave: pcm not aligned to its %d-byte samples", kind ? 4 : 2);
+  OP_REFUSE((size_t)out & 15, "feat_wave: out not 16-byte aligned");
+  OP_REFUSE((size_t)seg & 7, "feat_wave: seg not 8-byte aligned");
+  OP_REFUSE(((size_t)offsets & 3) || ((size_t)window & 3) || ((size_t)twiddle & 3), "feat_wave: offsets, window or twiddle not 4-byte aligned");
+  OP_REFUSE(B < 1 || n_samples < 1 || out_rows < 1, "feat_wave: B, n_samples, out_rows must be positive (got %d, %lld, %lld)", B,
+            (long long)n_samples, (long long)out_rows);
+  OP_REFUSE(P < 64 || P > 2048 || (P & (P - 1)), "feat_wave: P = %d is no power of two in [64, 2048]", P);
+  OP_REFUSE(S < 1 || N < S || P < N, "feat_wave: N = %d, S = %d, P = %d outside 1 <= S <= N <= P", N, S, P);
+  OP_REFUSE(!(preemph >= 0.f && preemph <= 1.f), "feat_wave: preemph = %g outside [0, 1]", (double)preemph);
+  OP_REFUSE((unsigned long long)out_rows > ((1ull << 40) / (unsigned long long)(P / 2 + 1)), "feat_wave: out_rows x (P / 2 + 1) = %lld x %d above the entry's 2^40",
+            (long long)out_rows, P / 2 + 1);
+  launch_feat_wave(pcm, kind, (long long)n_samples, reinterpret_cast<const long long*>(seg), offsets, B, N, S, P, preemph, window, twiddle, out,
+                   (long long)out_rows, (hipStream_t)stream);
+  OP_LAUNCHED("feat_wave");
+}
+
+int rsrgan_feat_wave_frames(int32_t P) { return (P >= 64 && P <= 2048 && !(P & (P - 1))) ? wave_frames(P) : 0; }
+
 // ---- TensorBoard histograms on the device (hist.hip): no handle; two launches on the caller's stream
 int rsrgan_hist_limits(double* out, int32_t* n) {
   OP_REFUSE(!n, "hist_limits: null pointer (n)");

@@ -480,6 +480,13 @@ void launch_feat_denorm(const float* y, const int* lengths, int B, int T, int D,
 // blob and out 16-byte aligned, out_rows * D <= 2^40, mean / stddev [D] double or both null.
 void launch_feat_decode(const uint8_t* blob, long long blob_bytes, const long long* seg, const float* scale, const int* offsets, int B, int D,
                         const double* mean, const double* stddev, float* out, long long out_rows, hipStream_t s);
+// ---- the waveform front end (wave.hip): PCM samples (kind 0: int16, 1: float32 on the int16 scale) -> raw log-power-spectrum rows
+// out [out_rows][P / 2 + 1], utterance b = samples seg[b] = (first, count), its frame 0 at row offsets[b], at most offsets[b + 1] - offsets[b]
+// rows.  window [N] and twiddle [P / 2][2] = exp(-2 pi i j / P) are device tables.  P a power of two in [64, 2048], 1 <= S <= N <= P.
+// wave_frames(P): the frames a workgroup takes (consecutive frames of one utterance).
+int wave_frames(int P);
+void launch_feat_wave(const void* pcm, int kind, long long n_samples, const long long* seg, const int* offsets, int B, int N, int S, int P,
+                      float preemph, const float* window, const float* twiddle, float* out, long long out_rows, hipStream_t s);
 // ---- TensorBoard histograms on the device (hist.hip): for each of n <= HIST_MAX_TENSORS strided float32 views (element (r, c) at
 // x[r * ld + c * cs]; rows * cols <= 2^31 - 1; x may be null where rows * cols == 0) one record of HIST_REC doubles in out: min, max, num,
 // sum, sum_squares and the count of each of the HIST_NL buckets of TensorFlow's default limits (hist_limits(), built once on the host).

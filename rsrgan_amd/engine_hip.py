@@ -234,7 +234,8 @@ class HipEngine(OpEntries):      # (the handle-free rsrgan_op_* wrappers and lau
         a D-run under RSRGAN_DPIPE=1); ready=False hands them over by event, as upload_async does.  ValueError before any device work
         if an utterance is longer than max_frames (limit=False: the caller cuts the result into chunks itself, as the chunked decode
         does).  An io.CodedBatch (the archive's bytes: float, double or Kaldi-compressed matrices) is decoded on the device first
-        (_featurize_coded); everything else is the same."""
+        (_featurize_coded), an io.WaveBatch (audio samples) becomes log-power-spectrum frames there first (_featurize_wave); everything
+        else is the same."""
         left = packed.left if left is None else int(left)
         right = packed.right if right is None else int(right)
         if mean is None and stddev is None:
@@ -243,6 +244,8 @@ class HipEngine(OpEntries):      # (the handle-free rsrgan_op_* wrappers and lau
             raise ValueError("featurize: mean and stddev must both be given or both be None")
         if hasattr(packed, "blob"):
             return self._featurize_coded(packed, left, right, mean, stddev, ready, limit)
+        if hasattr(packed, "samples"):
+            return self._featurize_wave(packed, left, right, mean, stddev, ready, limit)
         data, offsets = packed.data, packed.offsets
         if not isinstance(data, np.ndarray) or data.dtype != np.float32 or data.ndim != 2:
             raise ValueError("featurize: packed.data must be a float32 [rows, D] array")
@@ -314,6 +317,83 @@ class HipEngine(OpEntries):      # (the handle-free rsrgan_op_* wrappers and lau
             ln = torch.empty(B, dtype=torch.int32, device=self.device)
             self.op_feat_decode(dblob, dseg, dscale, off, B, D, dm, ds, raw, stream=us)
             self.op_feat_batch(raw, off, B, T, D, left, right, None, None, out, ln, stream=us)
+            if not ready:
+                ev = torch.cuda.Event()
+                ev.record(us)
+        cur = torch.cuda.current_stream(self.device)
+        if ready:
+            us.synchronize()
+            self._vouch(out); self._vouch(ln)
+        else:
+            cur.wait_event(ev)
+        out.record_stream(cur); ln.record_stream(cur)
+        return out, ln
+
+    # -- the waveform side (include/rsrgan.h rsrgan_feat_wave, csrc/wave.hip k_feat_wave) -------------------------------------------
+    def wave_frames_per_workgroup(self, P=512):
+        """the consecutive frames of one utterance a workgroup of k_feat_wave takes (rsrgan_feat_wave_frames)"""
+        return int(self.lib.rsrgan_feat_wave_frames(P))
+
+    def op_feat_wave(self, pcm, seg, offsets, B, window, twiddle, out, N=400, S=160, P=512, preemph=0.97, kind=None, n_samples=None,
+                     out_rows=None, stream=None):
+        """rsrgan_feat_wave on caller-owned device tensors (pcm int16 or float32 [n], seg [B, 2] i64 = (first sample, count), offsets
+        [B + 1] i32, window [N] f32, twiddle [P / 2, 2] f32, out [rows, P / 2 + 1] f32), on `stream` (default: the current one).  kind
+        defaults to what pcm's dtype says."""
+        if kind is None:
+            if pcm.dtype not in (torch.int16, torch.float32):
+                raise ValueError("op_feat_wave: pcm must be int16 or float32, got %s" % pcm.dtype)
+            kind = 0 if pcm.dtype == torch.int16 else 1
+        check(self.lib.rsrgan_feat_wave(_ptr(pcm), kind, pcm.numel() if n_samples is None else n_samples, _ptr(seg), _ptr(offsets), B, N, S, P,
+                                        preemph, _ptr(window), _ptr(twiddle), _ptr(out), out.shape[0] if out_rows is None else out_rows,
+                                        self._stream() if stream is None else C.c_void_p(stream.cuda_stream)))
+
+    def _wave_tables(self, spec, us):
+        """the window and the twiddles of a framing as fp32 device tensors: built on the host in float64, rounded once, uploaded at first use
+        and kept per engine (as _cmvn_device keeps the statistics)"""
+        from .io.wave import twiddle_table, window_table
+        cache = self.__dict__.setdefault("_wave_cache", {})
+        ent = cache.get(spec.key())
+        if ent is None:
+            win = np.ascontiguousarray(window_table(spec.window, spec.frame_length).astype(np.float32))
+            with torch.cuda.stream(us):
+                ent = (torch.from_numpy(win).to(self.device), torch.from_numpy(twiddle_table(spec.padded)).to(self.device))
+            if len(cache) > 16:
+                cache.clear()
+            cache[spec.key()] = ent
+        return ent
+
+    def wave_lps(self, samples, seg, offsets, rows, spec, us):
+        """host samples and tables -> (raw LPS rows [rows, bins], the offset table) on the device: the uploads and the launch are queued on
+        `us` (the caller is inside `with torch.cuda.stream(us)`)"""
+        win, tw = self._wave_tables(spec, us)
+        pcm = torch.from_numpy(np.ascontiguousarray(samples)).to(self.device, non_blocking=True)
+        dseg = torch.from_numpy(np.ascontiguousarray(seg)).to(self.device, non_blocking=True)
+        off = torch.from_numpy(np.ascontiguousarray(offsets)).to(self.device, non_blocking=True)
+        raw = torch.empty(rows, spec.bins, dtype=torch.float32, device=self.device)
+        self.op_feat_wave(pcm, dseg, off, int(seg.shape[0]), win, tw, raw, spec.frame_length, spec.frame_shift, spec.padded, spec.preemph,
+                          stream=us)
+        return raw, off
+
+    def _featurize_wave(self, wb, left, right, mean, stddev, ready, limit):
+        """featurize for an io.WaveBatch: the samples and the two tables travel on the upload stream, rsrgan_feat_wave writes the raw LPS
+        rows [frames, bins] and rsrgan_feat_batch normalises, splices and pads those; the hand-off is _featurize_coded's."""
+        offsets, spec = wb.offsets, wb.spec
+        B, T, D = int(wb.shape[0]), int(wb.shape[1]), int(wb.dim)
+        rows = int(offsets[-1]) if offsets.shape[0] else 0
+        if B < 1 or T < 1 or rows < 1 or offsets.shape != (B + 1,):
+            raise ValueError("featurize: B = %d, T = %d, %d rows, %d offsets" % (B, T, rows, offsets.shape[0]))
+        n = np.diff(offsets.astype(np.int64))
+        if limit and max(int(n.max()), T) > self.max_frames:
+            raise ValueError("featurize: an utterance of %d frames (T = %d) is longer than max_frames = %d" % (int(n.max()), T, self.max_frames))
+        if mean is not None and (np.size(mean) != D or np.size(stddev) != D):
+            raise ValueError("featurize: mean / stddev must hold D = %d entries, got %d / %d" % (D, np.size(mean), np.size(stddev)))
+        us = self.upload_stream()
+        dm, ds = self._cmvn_device(mean, stddev, us) if mean is not None else (None, None)
+        with torch.cuda.stream(us):
+            raw, off = self.wave_lps(wb.samples, wb.seg, offsets, rows, spec, us)
+            out = torch.empty(B, T, D * (left + 1 + right), dtype=torch.float32, device=self.device)
+            ln = torch.empty(B, dtype=torch.int32, device=self.device)
+            self.op_feat_batch(raw, off, B, T, D, left, right, dm, ds, out, ln, stream=us)
             if not ready:
                 ev = torch.cuda.Event()
                 ev.record(us)

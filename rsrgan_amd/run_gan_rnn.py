@@ -21,7 +21,7 @@ import numpy as np
 
 from . import dist as rdist
 from .gan_rnn import GAN_RNN
-from .io import ArkReader, ArkWriter, PaddedBatchReader, pack_coded, pack_utterances, prefetch, splice_feats
+from .io import ArkReader, ArkWriter, PaddedBatchReader, pack_coded, pack_utterances, pack_wave, prefetch, splice_feats
 from .train import eval_one_iteration, exponential_decay, train_one_iteration
 
 
@@ -77,7 +77,40 @@ def build_parser():
                    "is decoded on the device as well (csrc/feat.hip k_feat_decode): the reader ships each matrix's bytes as the file holds "
                    "them -- float, double or Kaldi-compressed -- with no host decode; training, cross-validation and --decode; the same "
                    "numbers bit for bit")
+    p.add_argument("--wav_scp", type=str, default=None, help="decode: read AUDIO instead of --test_inputs_scp -- lines `utt path` naming "
+                   "16-bit PCM wav files at 16 kHz; the log-power-spectrum frames (io/wave.py: 400 samples every 160, Hamming, 257 bins) are "
+                   "computed on the host, or with --device_features on the device (csrc/wave.hip); with --decode_push K the live path is "
+                   "driven by pushes of K x 160 samples")
     return p
+
+
+class _WavSource(object):
+    """--wav_scp: the utterances of a wav.scp behind the two members decode uses of an ArkReader (utt_ids, read_utt_data_from_index: here
+    the host route's frames), and the samples themselves for the device route and the live path"""
+
+    def __init__(self, path, input_dim):
+        from .io import wave as W
+        self.W, self.spec = W, W.DEFAULT
+        if int(input_dim) != self.spec.bins:
+            raise SystemExit("--wav_scp makes frames of %d bins; --input_dim is %d" % (self.spec.bins, int(input_dim)))
+        try:
+            self.items = W.read_wav_scp(path)
+        except (OSError, ValueError) as e:
+            raise SystemExit("--wav_scp: %s" % e)
+        self.utt_ids = [u for u, _ in self.items]
+
+    def read_samples(self, i):
+        utt, path = self.items[i]
+        try:
+            x = self.W.read_wav(path, sample_rate=self.spec.sample_rate)
+        except (OSError, EOFError, ValueError, self.W._wave.Error) as e:
+            raise SystemExit("--wav_scp: %s: %s" % (utt, e))
+        if self.W.num_frames(x.shape[0], self.spec) < 1:
+            raise SystemExit("--wav_scp: %s: %d samples make no frame of %d" % (utt, x.shape[0], self.spec.frame_length))
+        return x
+
+    def read_utt_data_from_index(self, i):
+        return self.W.lps_from_wave(self.read_samples(i), spec=self.spec)
 
 
 def _device_decode(FLAGS):
@@ -206,8 +239,15 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
     if os.path.exists(write_ark_path):
         os.remove(write_ark_path)
     writer = ArkWriter(write_scp_path)
-    reader = ArkReader()
-    reader(FLAGS.test_inputs_scp)
+    wav = getattr(FLAGS, "wav_scp", None)
+    if wav:
+        # --wav_scp: audio instead of an archive of frames.  Training from audio is out of scope: the labels are another feature type
+        if _device_decode(FLAGS):
+            raise SystemExit("--wav_scp reads audio, --device_decode decodes archives: use --device_features for the device route")
+        reader = _WavSource(wav, FLAGS.input_dim)
+    else:
+        reader = ArkReader()
+        reader(FLAGS.test_inputs_scp)
     start = datetime.datetime.now()
     denorm = lambda a: a * cmvn["stddev_labels"] + cmvn["mean_labels"] if cmvn is not None else a
 
@@ -229,6 +269,10 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
                               device_features=bool(getattr(FLAGS, "device_features", False)))
         except ValueError as e:
             raise SystemExit("--decode_push: %s" % e)
+        if wav:                                                              # pushes of N frames' worth of new samples
+            from .stream import decode_live_audio
+            return write_all(decode_live_audio(bank, (reader.read_samples(i) for i in range(len(reader.utt_ids))),
+                                               push * reader.spec.frame_shift), lambda a: a)
         return write_all(decode_live(bank, (reader.read_utt_data_from_index(i) for i in range(len(reader.utt_ids))), push), lambda a: a)
 
     def features(i):
@@ -255,6 +299,9 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
                                                         for k in ("mean_inputs", "stddev_inputs"))
 
         def features(i):                                                     # noqa: F811 -- [n, D * (L + 1 + R)] on the device
+            if wav:                                                          # the samples travel; the frames are made on the device
+                return featurize(pack_wave([reader.read_samples(i)], None, FLAGS.left_context, FLAGS.right_context, *stats,
+                                           spec=reader.spec, names=[reader.utt_ids[i]]), limit=chunk <= 0)[0][0]
             if _device_decode(FLAGS):
                 coded = pack_coded([reader.read_coded_from_index(i)], FLAGS.left_context, FLAGS.right_context, *stats, names=[reader.utt_ids[i]])
                 return featurize(coded, limit=chunk <= 0)[0][0]

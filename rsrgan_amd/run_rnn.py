@@ -63,6 +63,8 @@ def build_parser():
                    "theirs (d_real, d_fake); off: three histograms computed on the host")
     p.add_argument("--device_decode", type=str2bool, nargs="?", const=True, default=False, help="implies --device_features; the archive's "
                    "bytes travel undecoded and the device decodes them (run_gan_rnn --device_decode)")
+    p.add_argument("--wav_scp", type=str, default=None, help="decode: read audio (lines `utt path`, 16-bit PCM wav at 16 kHz) instead of "
+                   "--test_inputs_scp (run_gan_rnn --wav_scp)")
     return p
 
 

@@ -1,6 +1,7 @@
 """Decoding with the generator's carried state (GAN_RNN.forward_stream): one live stream enhanced while it arrives
 (StreamEnhancer), many utterances decoded side by side in the rows of one handle (decode_streams), and many live streams enhanced side
-by side, with the splice and the de-normalising on the device if asked (StreamBank, decode_live).
+by side, with the splice and the de-normalising on the device if asked (StreamBank, decode_live).  The live classes take audio as well
+(push_audio, decode_live_audio): samples become log-power-spectrum frames on the host (io/wave.py) or on the device (csrc/wave.hip).
 
 All are host logic around `model.forward_stream(inputs, lengths, reset)`: the model keeps, per batch row, the recurrent
 state of every generator layer between calls, so an utterance is a sequence of chunks of at most the handle's max_frames
@@ -26,6 +27,30 @@ def _on_device(a):
     return hasattr(a, "new_zeros") and hasattr(a, "detach")
 
 
+def _wave_spec(wave):
+    from .io.wave import DEFAULT
+    return DEFAULT if wave is None else wave
+
+
+def _take_frames(pending, samples, spec):
+    """(buf, keep): `pending` followed by the new `samples`, and the tail of it that belongs to no complete frame yet -- what stays on the
+    host for the next push, at most frame_length - 1 samples.  int16 stays int16; anything else makes the row float32."""
+    from .io.wave import as_pcm, num_frames
+    x = as_pcm(samples)
+    if pending is not None and pending.shape[0]:
+        x = np.concatenate([pending, x]) if pending.dtype == x.dtype else np.concatenate([pending.astype(np.float32), x.astype(np.float32)])
+    F = num_frames(x.shape[0], spec)
+    return x, (x[F * spec.frame_shift:] if F else x)
+
+
+class _DeviceRows(object):
+    """`count` consecutive rows, from `start`, of a frame tensor that is already on the device (StreamBank.push_audio): what a round
+    appends for a row in place of host frames"""
+
+    def __init__(self, start, count):
+        self.start, self.shape = int(start), (int(count),)
+
+
 class StreamEnhancer(object):
     """One live stream on batch row 0 of `model`.
 
@@ -42,9 +67,10 @@ class StreamEnhancer(object):
     max_frames, the default).  `device_features=True`: the splice and the de-normalising run on the device; the enhancer is then a
     one-row StreamBank (raw frames are shipped as float32)."""
 
-    def __init__(self, model, cmvn=None, left_context=0, right_context=0, chunk=None, device_features=False):
+    def __init__(self, model, cmvn=None, left_context=0, right_context=0, chunk=None, device_features=False, wave=None):
         # device_features: the splice and the de-normalising run on the device -- a one-row StreamBank serves push, flush and reset
-        self._bank = StreamBank(model, cmvn, left_context, right_context, chunk, streams=1, device_features=True) if device_features else None
+        self._bank = StreamBank(model, cmvn, left_context, right_context, chunk, streams=1, device_features=True, wave=wave) if device_features else None
+        self.wave = _wave_spec(wave)                # the framing push_audio turns samples into frames with
         self.model, self.cmvn = model, cmvn
         self.left, self.right = int(left_context), int(right_context)
         if self.left < 0 or self.right < 0:
@@ -64,6 +90,7 @@ class StreamEnhancer(object):
         self._n = 0                  # frames received
         self._next = 0               # next frame to enhance
         self._fresh = True           # the carried state of row 0 is zeroed with the next forward call
+        self._pcm = None             # push_audio: the samples that belong to no complete frame yet
 
     # -- pieces -------------------------------------------------------------------------
     def _normalise(self, frames):
@@ -123,6 +150,17 @@ class StreamEnhancer(object):
         outs = self._enhance(self._n - self.right) if self._n - self.right > self._next else []
         return np.concatenate(outs, 0) if outs else self._empty()
 
+    def push_audio(self, samples):
+        """push for audio: `samples` [n] (int16 PCM, or floats on that scale) of the utterance, any n >= 0.  The frames the samples
+        received so far complete (io.wave: 400 samples every 160) are pushed; the samples that belong to no complete frame yet -- at most
+        frame_length - 1 -- wait for the next call.  flush() and reset() drop them: a frame is never made of fewer samples."""
+        if self._bank is not None:
+            return self._bank.push_audio({0: samples})[0]
+        from .io.wave import lps_from_wave
+        buf, keep = _take_frames(self._pcm, samples, self.wave)
+        self._pcm = keep
+        return self.push(lps_from_wave(buf, spec=self.wave))
+
     def flush(self):
         """the end of the utterance: the held-back frames, their right context filled with the last frame"""
         if self._bank is not None:
@@ -174,8 +212,9 @@ class StreamBank(object):
     nothing is normalised or de-normalised and the output is float32.  ValueError before any device work: a row outside [0, streams),
     frames that are not [n, input_dim], device_features=True on a model whose engine has no op_feat_stream."""
 
-    def __init__(self, model, cmvn=None, left_context=0, right_context=0, chunk=None, streams=None, device_features=False):
+    def __init__(self, model, cmvn=None, left_context=0, right_context=0, chunk=None, streams=None, device_features=False, wave=None):
         self.model, self.cmvn = model, cmvn
+        self.wave = _wave_spec(wave)                                       # the framing push_audio turns samples into frames with
         self.left, self.right = int(left_context), int(right_context)
         if self.left < 0 or self.right < 0:
             raise ValueError("contexts must be >= 0")
@@ -199,6 +238,7 @@ class StreamBank(object):
         self._hist = [None] * self.streams                                 # host path: normalised frames [base, n) (float64)
         self._base = np.zeros(self.streams, np.int64)
         self._ring, self._pinned = None, {}                                # device path
+        self._pcm = [None] * self.streams                                  # push_audio: the samples that belong to no complete frame yet
         self.counters = {"rounds": 0, "calls": 0, "bytes_up": 0, "bytes_down": 0}      # bytes: host <-> device, both paths
 
     # -- the interface --------------------------------------------------------------------
@@ -208,6 +248,7 @@ class StreamBank(object):
             self._n[r] = self._next[r] = self._base[r] = 0
             self._fresh[r] = True
             self._hist[r] = None
+            self._pcm[r] = None
 
     def push(self, frames_by_row):
         work = {}
@@ -224,22 +265,73 @@ class StreamBank(object):
             self.dim = dims.pop()
         # (the device path ships raw float32 frames; the host path normalises in float64 whatever arrives, as StreamEnhancer does)
         work = {r: np.ascontiguousarray(x, np.float32 if self.device_features else np.float64) for r, x in work.items()}
-        outs, pos = {r: [] for r in work}, {r: 0 for r in work}
+        return self._rounds({r: x.shape[0] for r, x in work.items()}, lambda r, lo, n: work[r][lo:lo + n])
+
+    def _rounds(self, count, piece, dev=None):
+        """a push cut into rounds: row r has count[r] new frames, piece(r, lo, n) are frames [lo, lo + n) of them as a round appends
+        them -- host frames, or _DeviceRows of the frame tensor `dev`"""
+        outs, pos = {r: [] for r in count}, {r: 0 for r in count}
         while True:
             app, emit = {}, {}
-            for r, x in work.items():
-                a = min(self.chunk, x.shape[0] - pos[r])
+            for r, total in count.items():
+                a = min(self.chunk, total - pos[r])
                 k = min(self.chunk, int(self._n[r]) + a - self.right - int(self._next[r]))
                 if a > 0:
-                    app[r] = x[pos[r]:pos[r] + a]
+                    app[r] = piece(r, pos[r], a)
                     pos[r] += a
                 if k > 0:
                     emit[r] = k
             if not app and not emit:
                 break
-            for r, y in self._round(app, emit).items():
+            for r, y in self._round(app, emit, dev).items():
                 outs[r].append(y)
         return {r: np.concatenate(o, 0) if o else self._empty() for r, o in outs.items()}
+
+    def push_audio(self, samples_by_row):
+        """push for audio: {row: samples [n]} (int16 PCM, or floats on that scale), any n >= 0.  Per row the host keeps only the samples
+        that belong to no complete frame yet (at most frame_length - 1); the frames this call completes are enhanced as push enhances
+        them.  device_features=False: io.wave.lps_from_wave on the host, then push.  device_features=True: the samples of the completed
+        frames go up once, ONE rsrgan_feat_wave launch writes every row's new log-power-spectrum frames into one device tensor, and the
+        rounds' table entries (`src`) point into it: no frame visits the host.  flush() and reset() drop a row's pending samples."""
+        from .io.wave import lps_from_wave, num_frames
+        spec = self.wave
+        if self.dim is not None and self.dim != spec.bins:
+            raise ValueError("push_audio makes frames of %d bins, the bank's frames have %d" % (spec.bins, self.dim))
+        if self.device_features and not hasattr(self.model.engine, "wave_lps"):
+            raise ValueError("push_audio with device_features=True needs an engine with a device-side waveform front end (HipEngine.op_feat_wave)")
+        taken = {}
+        for r, x in samples_by_row.items():
+            r = self._rows([r])[0]
+            taken[r] = _take_frames(self._pcm[r], x, spec)                 # (raises before any row's state changes)
+        for r, (_, keep) in taken.items():
+            self._pcm[r] = keep
+        if not self.device_features:
+            return self.push({r: lps_from_wave(buf, spec=spec) for r, (buf, _) in taken.items()})
+        if self.dim is None and taken:
+            self.dim = spec.bins
+        N, S = spec.frame_length, spec.frame_shift
+        count = {r: num_frames(buf.shape[0], spec) for r, (buf, _) in taken.items()}
+        rows = [r for r in sorted(count) if count[r] > 0]
+        if not rows:
+            return self._rounds(count, None)
+        # one blob, one launch: row r's frames are rows base[r] .. base[r] + count[r] - 1 of `lps`
+        spans = [taken[r][0][:(count[r] - 1) * S + N] for r in rows]
+        if len({s.dtype for s in spans}) > 1:
+            spans = [s.astype(np.float32) for s in spans]
+        seg = np.zeros((len(rows), 2), np.int64)
+        seg[:, 1] = [s.shape[0] for s in spans]
+        seg[1:, 0] = np.cumsum(seg[:-1, 1])
+        offsets = np.zeros(len(rows) + 1, np.int32)
+        offsets[1:] = np.cumsum([count[r] for r in rows])
+        base = {r: int(offsets[i]) for i, r in enumerate(rows)}
+        blob = np.concatenate(spans)
+        import torch
+        eng = self.model.engine
+        us = eng.upload_stream()
+        with torch.cuda.stream(us):                                        # (the rounds read `lps` on this stream too: no other order is needed)
+            lps, _ = eng.wave_lps(blob, seg, offsets, int(offsets[-1]), spec, us)
+        self.counters["bytes_up"] += blob.nbytes + seg.nbytes + offsets.nbytes
+        return self._rounds(count, lambda r, lo, n: _DeviceRows(base[r] + lo, n), dev=lps)
 
     def flush(self, rows=None):
         """the end of the utterances on `rows` (default: every row with an utterance in flight): the held-back frames, their right
@@ -272,22 +364,26 @@ class StreamBank(object):
         on = getattr(getattr(self.model, "engine", None), "on_stream", None)
         return on() if on is not None else contextlib.nullcontext()
 
-    def _round(self, app, emit):
+    def _round(self, app, emit, dev=None):
         """one round: `app` {row: new frames (at most chunk)} are taken in, `emit` {row: k} frames [next, next + k) are enhanced in one
-        forward_stream call.  Returns {row: [k, output_dim]}."""
+        forward_stream call.  Returns {row: [k, output_dim]}.  `dev` (push_audio's device path): the new frames are rows of this device
+        tensor, `app` {row: _DeviceRows}, and the table's `src` entries point into it instead of into a packed upload."""
         table = np.zeros((self.batch, 6), np.int32)                        # (src, app0, napp, emit0, nemit, last) of rsrgan_feat_stream
         table[:, 5] = -1
         src, H = 0, self.ring_frames
         for r in range(self.streams):
             a = app[r].shape[0] if r in app else 0
-            table[r] = (src, self._n[r], a, self._next[r], emit.get(r, 0), self._n[r] + a - 1)
+            table[r] = (app[r].start if dev is not None and r in app else src, self._n[r], a, self._next[r], emit.get(r, 0), self._n[r] + a - 1)
             src += a
         for r in set(app) | set(emit):
             _, app0, napp, emit0, nemit, last = (int(v) for v in table[r])
             if last - (emit0 - self.left) + 1 > H or emit0 - self.left > app0 or app0 + napp - 1 > last or emit0 + nemit - 1 > last:
                 raise AssertionError("row %d: frames %d .. %d do not fit a ring of %d (the window invariant of rsrgan_feat_stream)"
                                      % (r, emit0 - self.left, last, H))
-        fresh = np.concatenate([app[r] for r in sorted(app)], 0) if app else np.zeros((0, self.dim), np.float32 if self.device_features else np.float64)
+        if dev is not None:
+            fresh = dev if app else dev[:0]
+        else:
+            fresh = np.concatenate([app[r] for r in sorted(app)], 0) if app else np.zeros((0, self.dim), np.float32 if self.device_features else np.float64)
         T = max(1, max(emit.values()) if emit else 0)
         outs = {}
         with self._on_stream():
@@ -353,7 +449,10 @@ class StreamBank(object):
         with torch.cuda.stream(us):
             if self._ring is None:
                 self._ring = torch.zeros(B, H, D, dtype=torch.float32, device=eng.device)
-            fr = torch.from_numpy(fresh).to(eng.device, non_blocking=True) if fresh.shape[0] else None
+            if _on_device(fresh):                                          # (push_audio: the frames were made on the device, on this stream)
+                fr, up = (fresh if fresh.shape[0] else None), 0
+            else:
+                fr, up = (torch.from_numpy(fresh).to(eng.device, non_blocking=True) if fresh.shape[0] else None), fresh.nbytes
             tb = torch.from_numpy(table).to(eng.device, non_blocking=True)
             out = torch.empty(B, T, D * (self.left + 1 + self.right), dtype=torch.float32, device=eng.device)
             ln = torch.empty(B, dtype=torch.int32, device=eng.device)
@@ -363,7 +462,7 @@ class StreamBank(object):
         cur = torch.cuda.current_stream(eng.device)
         cur.wait_event(ev)
         out.record_stream(cur); ln.record_stream(cur)
-        self.counters["bytes_up"] += fresh.nbytes + table.nbytes
+        self.counters["bytes_up"] += up + table.nbytes
         return out, ln
 
     def _collect_device(self, y, ln, emit):
@@ -409,6 +508,47 @@ def decode_live(bank: StreamBank, utterances: Iterable[np.ndarray], push: int) -
         busy = [r for r in range(bank.streams) if rows[r] is not None]
         if busy:
             for r, y in bank.push({r: rows[r][1][rows[r][2]:rows[r][2] + push] for r in busy}).items():
+                rows[r][3].append(y)
+                rows[r][2] += push
+            ended = [r for r in busy if rows[r][2] >= rows[r][1].shape[0]]
+            for r, y in (bank.flush(ended) if ended else {}).items():
+                done[rows[r][0]] = np.concatenate(rows[r][3] + [y], 0)
+                rows[r] = None
+        while next_out in done:
+            yield done.pop(next_out)
+            next_out += 1
+        if not busy and exhausted:
+            return
+
+
+def decode_live_audio(bank: StreamBank, utterances: Iterable[np.ndarray], push_samples: int) -> Iterator[np.ndarray]:
+    """decode_live from audio: every utterance (SAMPLES [n_i], int16 PCM or floats on that scale) arrives as pushes of `push_samples`
+    samples on one row of `bank` (StreamBank.push_audio) and ends with a flush.  Yields the enhanced utterances [F_i, output_dim], F_i the
+    frames the samples make (io.wave.num_frames), in input order."""
+    push = int(push_samples)
+    if push <= 0:
+        raise ValueError("push_samples=%d must be positive" % push)
+    source = enumerate(utterances)
+    rows = [None] * bank.streams                 # per row: [index, samples, position, outputs]
+    done, next_out, exhausted = {}, 0, False
+    while True:
+        for r in range(bank.streams):
+            while rows[r] is None and not exhausted:
+                try:
+                    i, x = next(source)
+                except StopIteration:
+                    exhausted = True
+                    break
+                x = np.asarray(x)
+                if x.ndim != 1:
+                    raise ValueError("utterance %d must be a 1-D array of samples, got %s" % (i, x.shape))
+                if x.shape[0] == 0:
+                    done[i] = bank._empty()
+                    continue
+                rows[r] = [i, x, 0, []]
+        busy = [r for r in range(bank.streams) if rows[r] is not None]
+        if busy:
+            for r, y in bank.push_audio({r: rows[r][1][rows[r][2]:rows[r][2] + push] for r in busy}).items():
                 rows[r][3].append(y)
                 rows[r][2] += push
             ended = [r for r in busy if rows[r][2] >= rows[r][1].shape[0]]
