@@ -561,8 +561,41 @@ int rsrgan_feat_decode(const uint8_t* blob, int64_t blob_bytes, const int64_t* s
 int rsrgan_feat_wave(const void* pcm, int32_t kind, int64_t n_samples, const int64_t* seg, const int32_t* offsets, int32_t B, int32_t N,
                      int32_t S, int32_t P, float preemph, const float* window, const float* twiddle, float* out, int64_t out_rows,
                      void* stream);
-/* The frames one workgroup of rsrgan_feat_wave takes (consecutive frames of one utterance, whose overlapping samples it reads once);
- * 0 for a P the entry refuses.  Tests place their utterance lengths around it. */
+/* The labels' side of the waveform front end (csrc/wave.hip k_feat_mfcc): PCM samples -> RAW MFCC or log-mel rows,
+ * out [out_rows][C ? C : M] float32, one launch, no handle.  The definition is Kaldi's compute-mfcc-feats --dither=0 with the WSJ
+ * conf/mfcc_hires.conf (--use-energy=false --num-mel-bins=40 --num-ceps=40 --low-freq=20 --high-freq=-400) and its other defaults: Povey
+ * window, pre-emphasis 0.97, DC removal, snip-edges, 25 ms / 10 ms frames, padding to a power of two, cepstral lifter 22.  Samples,
+ * frame count and rows are rsrgan_feat_wave's.  Per frame, steps 1, 3, 4 and 5 of rsrgan_feat_wave run unchanged (mean removal,
+ * pre-emphasis with the old values, the caller's window, zero padding to P, p_k = |X_k|^2 for k = 0 .. P / 2); the raw energy of step 2 is
+ * no part of the output.  Then, with eps = FLT_EPSILON:
+ *     6'. m_j = sum_t w_j[t] * p[a_j + t], t = 0 .. n_j - 1 ascending, j < M         the mel energies; filter j covers the contiguous bins
+ *                                                                                   [a_j, a_j + n_j) inside [0, P / 2): the Nyquist bin
+ *                                                                                   never enters (Kaldi's MelBanks); n_j = 0 gives m_j = 0
+ *     7'. l_j = log(max(m_j, eps))
+ *     8'. c_i = sum_j dct[i][j] * l_j, j ascending, i < C                            the cepstra.  C = 0 (dct == NULL): the row is l itself,
+ *                                                                                   the M log-mel energies (compute-fbank-feats)
+ * The filterbank and the DCT are the caller's device tables, as the window and the twiddles are, so the kernel is filterbank-agnostic:
+ *   mel_seg [M][3] int32 = (a_j, n_j, the index of w_j[0] in mel_w);  mel_w [nnz] float32;  dct [C][M] float32 row-major, the lifter
+ *   multiplied in.
+ * rsrgan_amd/io/wave.py builds them in fp64 and rounds once: Mel(f) = 1127 ln(1 + f / 700); M + 2 points equally spaced in mel between
+ * Mel(low) and Mel(high) (a high <= 0 is an offset from Nyquist); bin i has frequency i * rate / P and belongs to filter j where
+ * left_j < Mel < right_j strictly, with weight (Mel - left) / (centre - left) up to the centre and (right - Mel) / (right - centre) after
+ * it; dct row 0 = sqrt(1 / M), row k = sqrt(2 / M) cos(pi / M (n + 1/2) k) (Kaldi's ComputeDctMatrix), row i scaled by the lifter
+ * 1 + (Q / 2) sin(pi i / Q), Q = 22 (Q = 0: none).  Kaldi computes its tables in float32 and sums in another order: bit parity with a
+ * Kaldi binary is NOT pinned (none was available to compare against); the tests pin the definition above against float64.
+ * Arithmetic: fp32 throughout, fixed summation orders, so a frame's bits depend on nothing but its samples and the tables.  Every a_j is
+ * clamped into [0, P / 2), n_j into [0, P / 2 - a_j], every weight index into [0, nnz), besides the clamps of rsrgan_feat_wave: the kernel
+ * reads and writes nothing outside its buffers, whatever the device-resident tables hold.  Limits: 1 <= M <= 128, 0 <= C <= M,
+ * 1 <= nnz <= 8192, and the launch's dynamic LDS -- 4 (P / 2 + nz P / 2) x 2 + 4 (2 N + (F - 1) S) + 4 (nz P / 2 + nz M + M C + 3 M + nnz)
+ * bytes with F = rsrgan_feat_wave_frames(P), nz = min(4, F) -- at most 65536 (30.7 KB for 400 / 160 / 512 / 40 / 40 / 468).  All pointers
+ * are DEVICE pointers.  RSRGAN_ERR_INVALID before the first HIP call, rsrgan_last_error() naming the argument, for everything
+ * rsrgan_feat_wave refuses, and: a null mel_seg or mel_w; dct null with C != 0 or given with C = 0; mel_seg, mel_w or dct not 4-byte
+ * aligned; M, C or nnz outside the limits; an LDS need above 65536 bytes (the message holds the count); out_rows * (C ? C : M) above 2^40. */
+int rsrgan_feat_mfcc(const void* pcm, int32_t kind, int64_t n_samples, const int64_t* seg, const int32_t* offsets, int32_t B, int32_t N,
+                     int32_t S, int32_t P, float preemph, const float* window, const float* twiddle, const int32_t* mel_seg,
+                     const float* mel_w, int32_t nnz, int32_t M, const float* dct, int32_t C, float* out, int64_t out_rows, void* stream);
+/* The frames one workgroup of rsrgan_feat_wave or rsrgan_feat_mfcc takes (consecutive frames of one utterance, whose overlapping samples
+ * it reads once); 0 for a P the entries refuse.  Tests place their utterance lengths around it. */
 int rsrgan_feat_wave_frames(int32_t P);
 
 /* ---- TensorBoard histogram summaries on the device (csrc/hist.hip): what tf.summary.histogram's HistogramProto holds,

@@ -617,6 +617,38 @@ int rsrgan_feat_wave(const void* pcm, int32_t kind, int64_t n_samples, const int
   OP_LAUNCHED("feat_wave");
 }
 
+int rsrgan_feat_mfcc(const void* pcm, int32_t kind, int64_t n_samples, const int64_t* seg, const int32_t* offsets, int32_t B, int32_t N, int32_t S,
+                     int32_t P, float preemph, const float* window, const float* twiddle, const int32_t* mel_seg, const float* mel_w, int32_t nnz,
+                     int32_t M, const float* dct, int32_t C, float* out, int64_t out_rows, void* stream) {
+  OP_REFUSE(!pcm || !seg || !offsets || !out, "feat_mfcc: null pointer (pcm, seg, offsets or out)");
+  OP_REFUSE(!window || !twiddle, "feat_mfcc: null pointer (window or twiddle)");
+  OP_REFUSE(!mel_seg || !mel_w, "feat_mfcc: null pointer (mel_seg or mel_w)");
+  OP_REFUSE(kind != 0 && kind != 1, "feat_mfcc: kind = %d is neither 0 (int16) nor 1 (float32)", kind);
+  OP_REFUSE((size_t)pcm & (kind ? 3 : 1), "feat_mfcc: pcm not aligned to its %d-byte samples", kind ? 4 : 2);
+  OP_REFUSE((size_t)out & 15, "feat_mfcc: out not 16-byte aligned");
+  OP_REFUSE((size_t)seg & 7, "feat_mfcc: seg not 8-byte aligned");
+  OP_REFUSE(((size_t)offsets & 3) || ((size_t)window & 3) || ((size_t)twiddle & 3), "feat_mfcc: offsets, window or twiddle not 4-byte aligned");
+  OP_REFUSE(((size_t)mel_seg & 3) || ((size_t)mel_w & 3) || ((size_t)dct & 3), "feat_mfcc: mel_seg, mel_w or dct not 4-byte aligned");
+  OP_REFUSE(B < 1 || n_samples < 1 || out_rows < 1, "feat_mfcc: B, n_samples, out_rows must be positive (got %d, %lld, %lld)", B,
+            (long long)n_samples, (long long)out_rows);
+  OP_REFUSE(P < 64 || P > 2048 || (P & (P - 1)), "feat_mfcc: P = %d is no power of two in [64, 2048]", P);
+  OP_REFUSE(S < 1 || N < S || P < N, "feat_mfcc: N = %d, S = %d, P = %d outside 1 <= S <= N <= P", N, S, P);
+  OP_REFUSE(!(preemph >= 0.f && preemph <= 1.f), "feat_mfcc: preemph = %g outside [0, 1]", (double)preemph);
+  OP_REFUSE(M < 1 || M > 128, "feat_mfcc: M = %d outside [1, 128]", M);
+  OP_REFUSE(C < 0 || C > M, "feat_mfcc: C = %d outside [0, M = %d]", C, M);
+  OP_REFUSE(nnz < 1 || nnz > 8192, "feat_mfcc: nnz = %d outside [1, 8192]", nnz);
+  OP_REFUSE(C != 0 && !dct, "feat_mfcc: null pointer (dct) with C = %d: only C = 0 (log-mel output) takes none", C);
+  OP_REFUSE(C == 0 && dct, "feat_mfcc: dct given with C = 0: the log-mel output takes no DCT table");
+  const size_t lds = mfcc_lds_bytes(N, S, P, M, C, nnz);
+  OP_REFUSE(lds > 65536, "feat_mfcc: N = %d, S = %d, P = %d, M = %d, C = %d, nnz = %d need %zu bytes of LDS, above the entry's 65536", N, S, P, M, C,
+            nnz, lds);
+  OP_REFUSE((unsigned long long)out_rows > ((1ull << 40) / (unsigned long long)(C ? C : M)), "feat_mfcc: out_rows x width = %lld x %d above the entry's 2^40",
+            (long long)out_rows, C ? C : M);
+  launch_feat_mfcc(pcm, kind, (long long)n_samples, reinterpret_cast<const long long*>(seg), offsets, B, N, S, P, preemph, window, twiddle, mel_seg,
+                   mel_w, nnz, M, dct, C, out, (long long)out_rows, (hipStream_t)stream);
+  OP_LAUNCHED("feat_mfcc");
+}
+
 int rsrgan_feat_wave_frames(int32_t P) { return (P >= 64 && P <= 2048 && !(P & (P - 1))) ? wave_frames(P) : 0; }
 
 // ---- TensorBoard histograms on the device (hist.hip): no handle; two launches on the caller's stream

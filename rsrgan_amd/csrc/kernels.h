@@ -487,6 +487,13 @@ void launch_feat_decode(const uint8_t* blob, long long blob_bytes, const long lo
 int wave_frames(int P);
 void launch_feat_wave(const void* pcm, int kind, long long n_samples, const long long* seg, const int* offsets, int B, int N, int S, int P,
                       float preemph, const float* window, const float* twiddle, float* out, long long out_rows, hipStream_t s);
+// the same pipeline with the mel / cepstral epilogue (k_feat_mfcc): out [out_rows][C ? C : M] = the C cepstra, or with C = 0 (dct null) the M
+// log-mel energies.  mel_seg [M][3] = (first bin, bins, index of the first weight), mel_w [nnz], dct [C][M] are device tables; 1 <= M <= 128,
+// 0 <= C <= M, 1 <= nnz <= 8192.  mfcc_lds_bytes: the dynamic LDS the launch asks for, which the caller holds to 64 KB.
+size_t mfcc_lds_bytes(int N, int S, int P, int M, int C, int nnz);
+void launch_feat_mfcc(const void* pcm, int kind, long long n_samples, const long long* seg, const int* offsets, int B, int N, int S, int P,
+                      float preemph, const float* window, const float* twiddle, const int* mel_seg, const float* mel_w, int nnz, int M,
+                      const float* dct, int C, float* out, long long out_rows, hipStream_t s);
 // ---- TensorBoard histograms on the device (hist.hip): for each of n <= HIST_MAX_TENSORS strided float32 views (element (r, c) at
 // x[r * ld + c * cs]; rows * cols <= 2^31 - 1; x may be null where rows * cols == 0) one record of HIST_REC doubles in out: min, max, num,
 // sum, sum_squares and the count of each of the HIST_NL buckets of TensorFlow's default limits (hist_limits(), built once on the host).

@@ -1,6 +1,7 @@
 // wave.hip -- the waveform front end on the device: PCM samples -> log-power-spectrum frames (the 257-dim LPS every entry point of the
-// library starts from; the reference's README names Kaldi's compute-spectrogram-feats with a Hamming window as their source).  The
-// definition is the one stated at rsrgan_feat_wave in include/rsrgan.h: snip-edges framing (N samples every S), per frame the mean is
+// library starts from; the reference's README names Kaldi's compute-spectrogram-feats with a Hamming window as their source), and
+// PCM samples -> MFCC / log-mel frames (the 40-dim labels: compute-mfcc-feats with mfcc_hires.conf).  The definitions are the ones stated
+// at rsrgan_feat_wave and rsrgan_feat_mfcc in include/rsrgan.h: snip-edges framing (N samples every S), per frame the mean is
 // removed, E = log(max(sum v^2, eps)) is taken, then pre-emphasis, the caller's window table, zero padding to P, |DFT_P|^2, log; bin 0
 // carries E.  fp32 throughout.
 // Work: a workgroup (256 threads, four wavefronts) takes a run of F consecutive frames of ONE utterance (F = wave_frames(P): 8 up to
@@ -24,6 +25,8 @@
 // every output row into [0, out_rows); an utterance writes min(F_b, offsets[b + 1] - offsets[b], out_rows) rows and rows of no utterance
 // are not written.  The int16 samples are read one by one (an utterance starts at any sample).  No atomics, no traffic between
 // workgroups, no scratch memory.
+// The two kernels share the frame pipeline as __device__ functions (wave_find_run, wave_stage_run, wave_mean, wave_load_frame, wave_fft,
+// wave_power); k_feat_wave adds the raw energy and the log, k_feat_mfcc the mel / cepstral epilogue described in front of it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -64,6 +67,117 @@ __device__ __forceinline__ float wave_sample(const void* __restrict__ pcm, long 
   return F32 ? reinterpret_cast<const float*>(pcm)[i] : (float)reinterpret_cast<const short*>(pcm)[i];
 }
 
+// run w of the launch: which utterance it belongs to, where its samples and rows start (uniform over the workgroup)
+struct WaveRun {
+  long long s0, off, f0;       // the utterance's first sample (clamped), its first row, the run's first frame
+  uint32_t nf;                 // frames of the run, 1 .. F
+};
+
+// false: run w does not exist (w grows: no later run of this workgroup exists either)
+__device__ __forceinline__ bool wave_find_run(unsigned long long w, const long long* __restrict__ seg, const int* __restrict__ offsets, int B,
+                                              long long n_samples, uint32_t N, uint32_t S, long long out_rows, uint32_t F, WaveRun& r) {
+  int b = 0;
+  unsigned long long first = 0;
+  long long rows = 0, s0 = 0, cnt = 0;
+  for (; b < B; ++b) {
+    s0 = min(max(seg[2 * (size_t)b], 0ll), n_samples);
+    cnt = min(max(seg[2 * (size_t)b + 1], 0ll), n_samples - s0);
+    const long long frames = cnt < (long long)N ? 0ll : 1 + (cnt - (long long)N) / (long long)S;
+    rows = min(min(frames, max((long long)offsets[b + 1] - (long long)offsets[b], 0ll)), out_rows);
+    const unsigned long long t = ((unsigned long long)rows + F - 1) / F;
+    if (w < first + t) break;
+    first += t;
+  }
+  if (b == B) return false;
+  r.s0 = s0;
+  r.f0 = (long long)(w - first) * F;
+  r.off = offsets[b];
+  r.nf = (uint32_t)min((long long)F, rows - r.f0);
+  return true;
+}
+
+// the samples of a run, widened to float, into smp; a workgroup barrier on either side
+template <bool F32>
+__device__ __forceinline__ void wave_stage_run(float* smp, const void* __restrict__ pcm, long long n_samples, const WaveRun& r, uint32_t N,
+                                               uint32_t S, uint32_t tid) {
+  __syncthreads();                                                    // (the run before is done with smp; the staged tables are complete)
+  const long long g0 = r.s0 + r.f0 * (long long)S;
+  const uint32_t span = (r.nf - 1) * S + N;
+  for (uint32_t i = tid; i < span; i += 256) smp[i] = wave_sample<F32>(pcm, min(max(g0 + (long long)i, 0ll), n_samples - 1));
+  __syncthreads();
+}
+
+// 1: the mean of a frame
+__device__ __forceinline__ float wave_mean(const float* x, uint32_t N, uint32_t lane) {
+  float s = 0.f;
+  for (uint32_t i = lane; i < N; i += 64) s += x[i];
+  return wave_sum(s) / (float)N;
+}
+
+// 3, 4, 5: pre-emphasis, window, zero padding; two real samples are one complex element.  Ends in a workgroup barrier.
+__device__ __forceinline__ void wave_load_frame(float2* z, const float* x, float mean, float preemph, const float* win, uint32_t N, uint32_t H,
+                                                uint32_t lane, bool live) {
+  for (uint32_t j = lane; j < H; j += 64) {
+    float v[2];
+#pragma unroll
+    for (uint32_t h = 0; h < 2; ++h) {
+      const uint32_t i = 2 * j + h;
+      v[h] = 0.f;
+      if (i < N) {
+        const float cur = x[i] - mean, prev = x[i ? i - 1 : 0u] - mean;
+        v[h] = (cur - preemph * prev) * win[i];
+      }
+    }
+    if (live) z[fft_sw(j)] = make_float2(v[0], v[1]);
+  }
+  __syncthreads();
+}
+
+// the H-point complex FFT in place (digit-reversed result); a workgroup barrier after every stage
+__device__ __forceinline__ void wave_fft(float2* z, const float2* tw, uint32_t P, uint32_t H, uint32_t lane, bool live) {
+  uint32_t L = H;
+  for (; L >= 4; L >>= 2) {
+    const uint32_t q = L >> 2, step = P / L;
+    if (live) {
+      for (uint32_t t = lane; t < (H >> 2); t += 64) {
+        const uint32_t k = t & (q - 1), base = (t - k) * 4 + k;       // block * L + k
+        const float2 a0 = z[fft_sw(base)], a1 = z[fft_sw(base + q)], a2 = z[fft_sw(base + 2 * q)], a3 = z[fft_sw(base + 3 * q)];
+        const float2 t0 = make_float2(a0.x + a2.x, a0.y + a2.y), t1 = make_float2(a0.x - a2.x, a0.y - a2.y);
+        const float2 t2 = make_float2(a1.x + a3.x, a1.y + a3.y), t3 = make_float2(a1.x - a3.x, a1.y - a3.y);
+        float2 y0 = make_float2(t0.x + t2.x, t0.y + t2.y), y2 = make_float2(t0.x - t2.x, t0.y - t2.y);
+        float2 y1 = make_float2(t1.x + t3.y, t1.y - t3.x), y3 = make_float2(t1.x - t3.y, t1.y + t3.x);
+        if (q > 1) {
+          y1 = cmul(y1, tw_at(tw, k * step, H));
+          y2 = cmul(y2, tw_at(tw, 2 * k * step, H));
+          y3 = cmul(y3, tw_at(tw, 3 * k * step, H));
+        }
+        z[fft_sw(base)] = y0; z[fft_sw(base + q)] = y1; z[fft_sw(base + 2 * q)] = y2; z[fft_sw(base + 3 * q)] = y3;
+      }
+    }
+    __syncthreads();
+  }
+  if (L == 2) {
+    if (live) {
+      for (uint32_t t = lane; t < (H >> 1); t += 64) {
+        const float2 a0 = z[fft_sw(2 * t)], a1 = z[fft_sw(2 * t + 1)];
+        z[fft_sw(2 * t)] = make_float2(a0.x + a1.x, a0.y + a1.y);
+        z[fft_sw(2 * t + 1)] = make_float2(a0.x - a1.x, a0.y - a1.y);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// the split pass for bin k <= H: p_k = |X_k|^2
+__device__ __forceinline__ float wave_power(const float2* z, const float2* tw, uint32_t k, uint32_t H) {
+  const float2 a = z[fft_sw(fft_pos(k & (H - 1), H))], c = z[fft_sw(fft_pos((H - k) & (H - 1), H))];
+  const float2 ev = make_float2(0.5f * (a.x + c.x), 0.5f * (a.y - c.y));         // (Z_k + conj Z_{H-k}) / 2
+  const float2 od = make_float2(0.5f * (a.y + c.y), -0.5f * (a.x - c.x));        // -i (Z_k - conj Z_{H-k}) / 2
+  const float2 r = cmul(od, tw_at(tw, k, H));
+  const float re = ev.x + r.x, im = ev.y + r.y;
+  return re * re + im * im;
+}
+
 // PT: the padded length at compile time (the fast path, 512), or 0: P is the argument
 template <int PT, bool F32>
 __global__ __launch_bounds__(256) void k_feat_wave(const void* __restrict__ pcm, long long n_samples, const long long* __restrict__ seg,
@@ -82,119 +196,158 @@ __global__ __launch_bounds__(256) void k_feat_wave(const void* __restrict__ pcm,
   for (uint32_t i = tid; i < N; i += 256) win[i] = window[i];
   float2* z = zall + (size_t)min(wave, nz - 1) * H;
   for (unsigned long long w = blockIdx.x; w < runs; w += gridDim.x) {
-    // which utterance run w belongs to (uniform over the workgroup)
-    int b = 0;
-    unsigned long long first = 0;
-    long long rows = 0, s0 = 0, cnt = 0;
-    for (; b < B; ++b) {
-      s0 = min(max(seg[2 * (size_t)b], 0ll), n_samples);
-      cnt = min(max(seg[2 * (size_t)b + 1], 0ll), n_samples - s0);
-      const long long frames = cnt < (long long)N ? 0ll : 1 + (cnt - (long long)N) / (long long)S;
-      rows = min(min(frames, max((long long)offsets[b + 1] - (long long)offsets[b], 0ll)), out_rows);
-      const unsigned long long t = ((unsigned long long)rows + F - 1) / F;
-      if (w < first + t) break;
-      first += t;
-    }
-    if (b == B) break;                                                // (w grows: no later run of this workgroup exists either)
-    const long long f0 = (long long)(w - first) * F, off = offsets[b];
-    const uint32_t nf = (uint32_t)min((long long)F, rows - f0);
-    __syncthreads();                                                  // (the run before is done with smp; tw and win are complete)
-    {
-      const long long g0 = s0 + f0 * (long long)S;
-      const uint32_t span = (nf - 1) * S + N;
-      for (uint32_t i = tid; i < span; i += 256) smp[i] = wave_sample<F32>(pcm, min(max(g0 + (long long)i, 0ll), n_samples - 1));
-    }
-    __syncthreads();
+    WaveRun r;
+    if (!wave_find_run(w, seg, offsets, B, n_samples, N, S, out_rows, F, r)) break;
+    wave_stage_run<F32>(smp, pcm, n_samples, r, N, S, tid);
     for (uint32_t it = 0; it < F; it += nz) {
       const uint32_t fl = it + wave;
-      const bool live = wave < nz && fl < nf;
+      const bool live = wave < nz && fl < r.nf;
       const float* x = smp + (live ? fl * S : 0u);
       // 1, 2: the mean and the raw energy
-      float s = 0.f;
-      for (uint32_t i = lane; i < N; i += 64) s += x[i];
-      const float mean = wave_sum(s) / (float)N;
+      const float mean = wave_mean(x, N, lane);
       float e = 0.f;
       for (uint32_t i = lane; i < N; i += 64) { const float v = x[i] - mean; e += v * v; }
       const float energy = logf(fmaxf(wave_sum(e), FLT_EPSILON));
-      // 3, 4, 5: pre-emphasis, window, zero padding; two real samples are one complex element
-      for (uint32_t j = lane; j < H; j += 64) {
-        float v[2];
-#pragma unroll
-        for (uint32_t h = 0; h < 2; ++h) {
-          const uint32_t i = 2 * j + h;
-          v[h] = 0.f;
-          if (i < N) {
-            const float cur = x[i] - mean, prev = x[i ? i - 1 : 0u] - mean;
-            v[h] = (cur - preemph * prev) * win[i];
-          }
-        }
-        if (live) z[fft_sw(j)] = make_float2(v[0], v[1]);
-      }
-      __syncthreads();
-      uint32_t L = H;
-      for (; L >= 4; L >>= 2) {
-        const uint32_t q = L >> 2, step = P / L;
-        if (live) {
-          for (uint32_t t = lane; t < (H >> 2); t += 64) {
-            const uint32_t k = t & (q - 1), base = (t - k) * 4 + k;   // block * L + k
-            const float2 a0 = z[fft_sw(base)], a1 = z[fft_sw(base + q)], a2 = z[fft_sw(base + 2 * q)], a3 = z[fft_sw(base + 3 * q)];
-            const float2 t0 = make_float2(a0.x + a2.x, a0.y + a2.y), t1 = make_float2(a0.x - a2.x, a0.y - a2.y);
-            const float2 t2 = make_float2(a1.x + a3.x, a1.y + a3.y), t3 = make_float2(a1.x - a3.x, a1.y - a3.y);
-            float2 y0 = make_float2(t0.x + t2.x, t0.y + t2.y), y2 = make_float2(t0.x - t2.x, t0.y - t2.y);
-            float2 y1 = make_float2(t1.x + t3.y, t1.y - t3.x), y3 = make_float2(t1.x - t3.y, t1.y + t3.x);
-            if (q > 1) {
-              y1 = cmul(y1, tw_at(tw, k * step, H));
-              y2 = cmul(y2, tw_at(tw, 2 * k * step, H));
-              y3 = cmul(y3, tw_at(tw, 3 * k * step, H));
-            }
-            z[fft_sw(base)] = y0; z[fft_sw(base + q)] = y1; z[fft_sw(base + 2 * q)] = y2; z[fft_sw(base + 3 * q)] = y3;
-          }
-        }
-        __syncthreads();
-      }
-      if (L == 2) {
-        if (live) {
-          for (uint32_t t = lane; t < (H >> 1); t += 64) {
-            const float2 a0 = z[fft_sw(2 * t)], a1 = z[fft_sw(2 * t + 1)];
-            z[fft_sw(2 * t)] = make_float2(a0.x + a1.x, a0.y + a1.y);
-            z[fft_sw(2 * t + 1)] = make_float2(a0.x - a1.x, a0.y - a1.y);
-          }
-        }
-        __syncthreads();
-      }
+      wave_load_frame(z, x, mean, preemph, win, N, H, lane, live);
+      wave_fft(z, tw, P, H, lane, live);
       // the split pass, |X_k|^2 and the log; consecutive lanes write consecutive bins of the row
       if (live) {
-        const long long row = min(max(off + f0 + (long long)fl, 0ll), out_rows - 1);
+        const long long row = min(max(r.off + r.f0 + (long long)fl, 0ll), out_rows - 1);
         float* o = out + (size_t)row * NB;
-        for (uint32_t k = lane; k <= H; k += 64) {
-          const float2 a = z[fft_sw(fft_pos(k & (H - 1), H))], c = z[fft_sw(fft_pos((H - k) & (H - 1), H))];
-          const float2 ev = make_float2(0.5f * (a.x + c.x), 0.5f * (a.y - c.y));         // (Z_k + conj Z_{H-k}) / 2
-          const float2 od = make_float2(0.5f * (a.y + c.y), -0.5f * (a.x - c.x));        // -i (Z_k - conj Z_{H-k}) / 2
-          const float2 r = cmul(od, tw_at(tw, k, H));
-          const float re = ev.x + r.x, im = ev.y + r.y;
-          o[k] = k == 0 ? energy : logf(fmaxf(re * re + im * im, FLT_EPSILON));
-        }
+        for (uint32_t k = lane; k <= H; k += 64) o[k] = k == 0 ? energy : logf(fmaxf(wave_power(z, tw, k, H), FLT_EPSILON));
       }
       __syncthreads();                                                // (z is rewritten by this wavefront's next frame)
     }
   }
 }
 
+// ---- MFCC / log-mel (include/rsrgan.h rsrgan_feat_mfcc): the same pipeline up to p_k, then per frame, by the wavefront that owns it,
+//   p     the split pass writes p_k, k < H, into the wavefront's OWN row prow [H] (not over z: the pass reads z[k] and z[H - k], which other
+//         lanes of the wavefront still need); the Nyquist bin is not formed
+//   mel   lane j (stride 64 for M > 64) sums filter j, t ascending: m_j = sum_t w[w0_j + t] * p[a_j + t]; l_j = log(max(m_j, eps)) -> lrow [M]
+//   dct   lane i (stride 64) forms c_i = sum_j dct[i][j] * l_j, j ascending, from dctT [M][C], the table staged TRANSPOSED once per
+//         workgroup: lanes i, i + 1, .. read consecutive dwords (no conflict) and l_j is one address for all lanes (a broadcast)
+// A workgroup barrier separates the three steps (the loop is uniform over the workgroup, as the FFT stages' barriers already demand).
+// LDS banks of the mel sums (ds_read_b32: per 32-lane half, bank = dword index mod 32): at step t lane j reads p[a_j + t].  The filters'
+// first bins a_j ascend with j but not evenly, so two lanes of a half can meet on a bank with different bins.  ENUMERATED for the
+// recipe's table (400 / 160 / 512, 40 filters of 3 .. 30 bins; tools/mfcc_bench.py --banks prints the count), not measured: lanes 0 - 31
+// are active for 19 steps, lanes 32 - 39 for 30, no step is worse than 2-way, and the 49 half-wave reads take 78 LDS cycles where 49 would
+// be conflict-free -- 29 cycles per frame beside the 128 of the four FFT stages' 8-byte reads and stores (4 x (4 x 2 + 4 x 6)), so the row is left unpadded.  The weights
+// w[w0_j + t] take 77 cycles for the same 49 reads (worst step 4-way: the short low filters' w0_j lie close together).
+// Memory safety: a_j is clamped into [0, H), n_j into [0, H - a_j], every weight index into [0, nnz): the tables are device-resident, the
+// host cannot see them, and the kernel reads and writes nothing outside its buffers whatever they hold.
+template <int PT, bool F32>
+__global__ __launch_bounds__(256) void k_feat_mfcc(const void* __restrict__ pcm, long long n_samples, const long long* __restrict__ seg,
+                                                    const int* __restrict__ offsets, int B, uint32_t N, uint32_t S, uint32_t Prt, float preemph,
+                                                    const float* __restrict__ window, const float* __restrict__ twiddle,
+                                                    const int* __restrict__ mel_seg, const float* __restrict__ mel_w, uint32_t nnz, uint32_t M,
+                                                    const float* __restrict__ dct, uint32_t C, float* __restrict__ out, long long out_rows,
+                                                    unsigned long long runs, uint32_t F) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const uint32_t P = PT ? (uint32_t)PT : Prt, H = P >> 1, NC = C ? C : M;
+  const uint32_t nz = min((uint32_t)WAVE_WAVES, F);
+  float2* tw = reinterpret_cast<float2*>(lds_raw);                   // [H]
+  float2* zall = tw + H;                                             // [nz][H]
+  float* win = reinterpret_cast<float*>(zall + (size_t)nz * H);      // [N]
+  float* smp = win + N;                                              // [(F - 1) * S + N]
+  float* pall = smp + (F - 1) * S + N;                               // [nz][H]
+  float* lall = pall + (size_t)nz * H;                               // [nz][M]
+  float* dctT = lall + (size_t)nz * M;                               // [M][C]
+  int* mseg = reinterpret_cast<int*>(dctT + (size_t)M * C);          // [M][3]
+  float* mw = reinterpret_cast<float*>(mseg + 3 * M);                // [nnz]
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  for (uint32_t i = tid; i < H; i += 256) tw[i] = make_float2(twiddle[2 * i], twiddle[2 * i + 1]);
+  for (uint32_t i = tid; i < N; i += 256) win[i] = window[i];
+  for (uint32_t i = tid; i < M * C; i += 256) { const uint32_t c = i / M, j = i - c * M; dctT[j * C + c] = dct[i]; }
+  for (uint32_t i = tid; i < 3 * M; i += 256) mseg[i] = mel_seg[i];
+  for (uint32_t i = tid; i < nnz; i += 256) mw[i] = mel_w[i];
+  float2* z = zall + (size_t)min(wave, nz - 1) * H;
+  float* prow = pall + (size_t)min(wave, nz - 1) * H;
+  float* lrow = lall + (size_t)min(wave, nz - 1) * M;
+  for (unsigned long long w = blockIdx.x; w < runs; w += gridDim.x) {
+    WaveRun r;
+    if (!wave_find_run(w, seg, offsets, B, n_samples, N, S, out_rows, F, r)) break;
+    wave_stage_run<F32>(smp, pcm, n_samples, r, N, S, tid);
+    for (uint32_t it = 0; it < F; it += nz) {
+      const uint32_t fl = it + wave;
+      const bool live = wave < nz && fl < r.nf;
+      const float* x = smp + (live ? fl * S : 0u);
+      const float mean = wave_mean(x, N, lane);
+      wave_load_frame(z, x, mean, preemph, win, N, H, lane, live);
+      wave_fft(z, tw, P, H, lane, live);
+      if (live)
+        for (uint32_t k = lane; k < H; k += 64) prow[k] = wave_power(z, tw, k, H);
+      __syncthreads();
+      const long long row = min(max(r.off + r.f0 + (long long)fl, 0ll), out_rows - 1);
+      float* o = out + (size_t)row * NC;
+      if (live) {
+        for (uint32_t j = lane; j < M; j += 64) {
+          const uint32_t a = (uint32_t)min(max(mseg[3 * j], 0), (int)H - 1);
+          const uint32_t n = (uint32_t)min(max(mseg[3 * j + 1], 0), (int)(H - a));
+          const uint32_t w0 = (uint32_t)min(max(mseg[3 * j + 2], 0), (int)nnz - 1);
+          float m = 0.f;
+          for (uint32_t t = 0; t < n; ++t) m += mw[min(w0 + t, nnz - 1)] * prow[a + t];
+          const float l = logf(fmaxf(m, FLT_EPSILON));
+          if (C) lrow[j] = l; else o[j] = l;
+        }
+      }
+      if (C) {
+        __syncthreads();
+        if (live) {
+          for (uint32_t i = lane; i < C; i += 64) {
+            float c = 0.f;
+            for (uint32_t j = 0; j < M; ++j) c += dctT[j * C + i] * lrow[j];
+            o[i] = c;
+          }
+        }
+      }
+      __syncthreads();                                                // (z, prow and lrow are rewritten by this wavefront's next frame)
+    }
+  }
+}
+
 int wave_frames(int P) { return P <= 1024 ? 8 : 2; }
+
+// twiddles, the wavefronts' buffers, the window, the samples of a run: 16.4 KB for 400 / 160 / 512, at most 56 KB (P = 1024, N = S = P)
+static size_t wave_lds(int N, int S, int P) {
+  const int F = wave_frames(P), H = P / 2, nz = std::min(WAVE_WAVES, F);
+  return (size_t)(H + nz * H) * sizeof(float2) + (size_t)(N + (F - 1) * S + N) * sizeof(float);
+}
 
 void launch_feat_wave(const void* pcm, int kind, long long n_samples, const long long* seg, const int* offsets, int B, int N, int S, int P,
                       float preemph, const float* window, const float* twiddle, float* out, long long out_rows, hipStream_t s) {
-  const int F = wave_frames(P), H = P / 2, nz = std::min(WAVE_WAVES, F);
+  const int F = wave_frames(P);
   const unsigned long long runs = ((unsigned long long)out_rows + F - 1) / F + (unsigned long long)B;
   const int grid = (int)std::min<unsigned long long>(16384, runs);
-  // twiddles, the wavefronts' buffers, the window, the samples of a run: 16.4 KB for 400 / 160 / 512, at most 56 KB (P = 1024, N = S = P)
-  const size_t lds = (size_t)(H + nz * H) * sizeof(float2) + (size_t)(N + (F - 1) * S + N) * sizeof(float);
+  const size_t lds = wave_lds(N, S, P);
 #define RSR_WAVE_LAUNCH(PT, F32) \
   hipLaunchKernelGGL((k_feat_wave<PT, F32>), dim3(grid), dim3(256), lds, s, pcm, n_samples, seg, offsets, B, (uint32_t)N, (uint32_t)S, (uint32_t)P, \
                      preemph, window, twiddle, out, out_rows, runs, (uint32_t)F)
   if (P == 512) { if (kind) RSR_WAVE_LAUNCH(512, true); else RSR_WAVE_LAUNCH(512, false); }
   else { if (kind) RSR_WAVE_LAUNCH(0, true); else RSR_WAVE_LAUNCH(0, false); }
 #undef RSR_WAVE_LAUNCH
+}
+
+// k_feat_wave's need plus the power rows, the log-mel rows, the transposed DCT and the two mel tables: 30.7 KB for 400 / 160 / 512 with
+// 40 filters, 40 cepstra and the recipe's 468 weights
+size_t mfcc_lds_bytes(int N, int S, int P, int M, int C, int nnz) {
+  const int F = wave_frames(P), H = P / 2, nz = std::min(WAVE_WAVES, F);
+  return wave_lds(N, S, P) + ((size_t)nz * H + (size_t)nz * M + (size_t)M * C + 3 * (size_t)M + (size_t)nnz) * sizeof(float);
+}
+
+void launch_feat_mfcc(const void* pcm, int kind, long long n_samples, const long long* seg, const int* offsets, int B, int N, int S, int P,
+                      float preemph, const float* window, const float* twiddle, const int* mel_seg, const float* mel_w, int nnz, int M,
+                      const float* dct, int C, float* out, long long out_rows, hipStream_t s) {
+  const int F = wave_frames(P);
+  const unsigned long long runs = ((unsigned long long)out_rows + F - 1) / F + (unsigned long long)B;
+  const int grid = (int)std::min<unsigned long long>(16384, runs);
+  const size_t lds = mfcc_lds_bytes(N, S, P, M, C, nnz);
+#define RSR_MFCC_LAUNCH(PT, F32) \
+  hipLaunchKernelGGL((k_feat_mfcc<PT, F32>), dim3(grid), dim3(256), lds, s, pcm, n_samples, seg, offsets, B, (uint32_t)N, (uint32_t)S, (uint32_t)P, \
+                     preemph, window, twiddle, mel_seg, mel_w, (uint32_t)nnz, (uint32_t)M, dct, (uint32_t)C, out, out_rows, runs, (uint32_t)F)
+  if (P == 512) { if (kind) RSR_MFCC_LAUNCH(512, true); else RSR_MFCC_LAUNCH(512, false); }
+  else { if (kind) RSR_MFCC_LAUNCH(0, true); else RSR_MFCC_LAUNCH(0, false); }
+#undef RSR_MFCC_LAUNCH
 }
 
 }  // namespace rsr

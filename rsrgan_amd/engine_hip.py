@@ -27,7 +27,97 @@ class _RawDeviceBuffer:
                                          "version": 2, "strides": None}
 
 
-class HipEngine(OpEntries):      # (the handle-free rsrgan_op_* wrappers and launch_floor: ops.py)
+class WaveFrontEnd(OpEntries):
+    """The waveform front end on the handle-free entries (rsrgan_feat_wave, rsrgan_feat_mfcc): the op wrappers, the per-spec table cache
+    and wave_features, on the upload stream.  HipEngine is one; so is a bare WaveFrontEnd(), for callers without a model (io.wave_cmvn,
+    tools/mfcc_bench.py)."""
+
+    def upload_stream(self):
+        """the stream the feature front end uploads and runs on (featurize, featurize_frames, StreamBank)"""
+        us = getattr(self, "_upload_stream", None)
+        if us is None:
+            us = self._upload_stream = torch.cuda.Stream(self.device)
+        return us
+
+    # -- the waveform side (include/rsrgan.h rsrgan_feat_wave, csrc/wave.hip k_feat_wave) -------------------------------------------
+    def wave_frames_per_workgroup(self, P=512):
+        """the consecutive frames of one utterance a workgroup of k_feat_wave takes (rsrgan_feat_wave_frames)"""
+        return int(self.lib.rsrgan_feat_wave_frames(P))
+
+    def op_feat_wave(self, pcm, seg, offsets, B, window, twiddle, out, N=400, S=160, P=512, preemph=0.97, kind=None, n_samples=None,
+                     out_rows=None, stream=None):
+        """rsrgan_feat_wave on caller-owned device tensors (pcm int16 or float32 [n], seg [B, 2] i64 = (first sample, count), offsets
+        [B + 1] i32, window [N] f32, twiddle [P / 2, 2] f32, out [rows, P / 2 + 1] f32), on `stream` (default: the current one).  kind
+        defaults to what pcm's dtype says."""
+        if kind is None:
+            if pcm.dtype not in (torch.int16, torch.float32):
+                raise ValueError("op_feat_wave: pcm must be int16 or float32, got %s" % pcm.dtype)
+            kind = 0 if pcm.dtype == torch.int16 else 1
+        check(self.lib.rsrgan_feat_wave(_ptr(pcm), kind, pcm.numel() if n_samples is None else n_samples, _ptr(seg), _ptr(offsets), B, N, S, P,
+                                        preemph, _ptr(window), _ptr(twiddle), _ptr(out), out.shape[0] if out_rows is None else out_rows,
+                                        self._stream() if stream is None else C.c_void_p(stream.cuda_stream)))
+
+    def op_feat_mfcc(self, pcm, seg, offsets, B, window, twiddle, mel_seg, mel_w, dct, out, N=400, S=160, P=512, preemph=0.97, M=None, ceps=None,
+                     nnz=None, kind=None, n_samples=None, out_rows=None, stream=None):
+        """rsrgan_feat_mfcc on caller-owned device tensors (pcm, seg, offsets, window, twiddle as op_feat_wave takes them; mel_seg [M, 3]
+        i32, mel_w [nnz] f32, dct [C, M] f32 or None for log-mel output; out [rows, C or M] f32), on `stream` (default: the current one).
+        M, ceps (the entry's C) and nnz default to what the tables' shapes say."""
+        if kind is None:
+            if pcm.dtype not in (torch.int16, torch.float32):
+                raise ValueError("op_feat_mfcc: pcm must be int16 or float32, got %s" % pcm.dtype)
+            kind = 0 if pcm.dtype == torch.int16 else 1
+        M = int(mel_seg.shape[0]) if M is None else M
+        ceps = (0 if dct is None else int(dct.shape[0])) if ceps is None else ceps
+        check(self.lib.rsrgan_feat_mfcc(_ptr(pcm), kind, pcm.numel() if n_samples is None else n_samples, _ptr(seg), _ptr(offsets), B, N, S, P,
+                                        preemph, _ptr(window), _ptr(twiddle), _ptr(mel_seg), _ptr(mel_w), mel_w.numel() if nnz is None else nnz,
+                                        M, _ptr(dct), ceps, _ptr(out), out.shape[0] if out_rows is None else out_rows,
+                                        self._stream() if stream is None else C.c_void_p(stream.cuda_stream)))
+
+    def _wave_tables(self, spec, us):
+        """the window and the twiddles of a framing as fp32 device tensors: built on the host in float64, rounded once, uploaded at first use
+        and kept per engine (as _cmvn_device keeps the statistics).  For an io.wave.MfccSpec three more follow: mel_seg, mel_w and the DCT
+        (None for log-mel output)."""
+        from .io.wave import dct_table, mel_table, twiddle_table, window_table
+        cache = self.__dict__.setdefault("_wave_cache", {})
+        ent = cache.get(spec.key())
+        if ent is None:
+            win = np.ascontiguousarray(window_table(spec.window, spec.frame_length).astype(np.float32))
+            with torch.cuda.stream(us):
+                ent = (torch.from_numpy(win).to(self.device), torch.from_numpy(twiddle_table(spec.padded)).to(self.device))
+                if hasattr(spec, "num_mel_bins"):
+                    mseg, mw = mel_table(spec)
+                    ent += (torch.from_numpy(mseg).to(self.device), torch.from_numpy(mw).to(self.device),
+                            torch.from_numpy(dct_table(spec)).to(self.device) if spec.num_ceps else None)
+            if len(cache) > 16:
+                cache.clear()
+            cache[spec.key()] = ent
+        return ent
+
+    def wave_features(self, samples, seg, offsets, rows, spec, us):
+        """host samples and tables -> (raw feature rows [rows, spec.bins], the offset table) on the device: LPS for a WaveSpec
+        (rsrgan_feat_wave), MFCC or log-mel for an MfccSpec (rsrgan_feat_mfcc).  The uploads and the launch are queued on `us` (the caller is
+        inside `with torch.cuda.stream(us)`)"""
+        tabs = self._wave_tables(spec, us)
+        pcm = torch.from_numpy(np.ascontiguousarray(samples)).to(self.device, non_blocking=True)
+        dseg = torch.from_numpy(np.ascontiguousarray(seg)).to(self.device, non_blocking=True)
+        off = torch.from_numpy(np.ascontiguousarray(offsets)).to(self.device, non_blocking=True)
+        raw = torch.empty(rows, spec.bins, dtype=torch.float32, device=self.device)
+        if hasattr(spec, "num_mel_bins"):
+            win, tw, mseg, mw, dct = tabs
+            self.op_feat_mfcc(pcm, dseg, off, int(seg.shape[0]), win, tw, mseg, mw, dct, raw, spec.frame_length, spec.frame_shift, spec.padded,
+                              spec.preemph, stream=us)
+        else:
+            win, tw = tabs
+            self.op_feat_wave(pcm, dseg, off, int(seg.shape[0]), win, tw, raw, spec.frame_length, spec.frame_shift, spec.padded, spec.preemph,
+                              stream=us)
+        return raw, off
+
+    def wave_lps(self, samples, seg, offsets, rows, spec, us):
+        """wave_features under its first name: the spec's type says which features come out"""
+        return self.wave_features(samples, seg, offsets, rows, spec, us)
+
+
+class HipEngine(WaveFrontEnd):      # (the handle-free rsrgan_op_* wrappers and launch_floor: ops.py)
     def __init__(self, *, batch_size: int, max_frames: int, input_dim: int = 257, output_dim: int = 40,
                  g_type: str = "lstm", g_layers: Optional[int] = None, g_cells: Optional[int] = None,
                  g_proj: Optional[int] = None, d_layers: Optional[int] = None, d_cells: Optional[int] = None,
@@ -329,54 +419,10 @@ class HipEngine(OpEntries):      # (the handle-free rsrgan_op_* wrappers and lau
         out.record_stream(cur); ln.record_stream(cur)
         return out, ln
 
-    # -- the waveform side (include/rsrgan.h rsrgan_feat_wave, csrc/wave.hip k_feat_wave) -------------------------------------------
-    def wave_frames_per_workgroup(self, P=512):
-        """the consecutive frames of one utterance a workgroup of k_feat_wave takes (rsrgan_feat_wave_frames)"""
-        return int(self.lib.rsrgan_feat_wave_frames(P))
-
-    def op_feat_wave(self, pcm, seg, offsets, B, window, twiddle, out, N=400, S=160, P=512, preemph=0.97, kind=None, n_samples=None,
-                     out_rows=None, stream=None):
-        """rsrgan_feat_wave on caller-owned device tensors (pcm int16 or float32 [n], seg [B, 2] i64 = (first sample, count), offsets
-        [B + 1] i32, window [N] f32, twiddle [P / 2, 2] f32, out [rows, P / 2 + 1] f32), on `stream` (default: the current one).  kind
-        defaults to what pcm's dtype says."""
-        if kind is None:
-            if pcm.dtype not in (torch.int16, torch.float32):
-                raise ValueError("op_feat_wave: pcm must be int16 or float32, got %s" % pcm.dtype)
-            kind = 0 if pcm.dtype == torch.int16 else 1
-        check(self.lib.rsrgan_feat_wave(_ptr(pcm), kind, pcm.numel() if n_samples is None else n_samples, _ptr(seg), _ptr(offsets), B, N, S, P,
-                                        preemph, _ptr(window), _ptr(twiddle), _ptr(out), out.shape[0] if out_rows is None else out_rows,
-                                        self._stream() if stream is None else C.c_void_p(stream.cuda_stream)))
-
-    def _wave_tables(self, spec, us):
-        """the window and the twiddles of a framing as fp32 device tensors: built on the host in float64, rounded once, uploaded at first use
-        and kept per engine (as _cmvn_device keeps the statistics)"""
-        from .io.wave import twiddle_table, window_table
-        cache = self.__dict__.setdefault("_wave_cache", {})
-        ent = cache.get(spec.key())
-        if ent is None:
-            win = np.ascontiguousarray(window_table(spec.window, spec.frame_length).astype(np.float32))
-            with torch.cuda.stream(us):
-                ent = (torch.from_numpy(win).to(self.device), torch.from_numpy(twiddle_table(spec.padded)).to(self.device))
-            if len(cache) > 16:
-                cache.clear()
-            cache[spec.key()] = ent
-        return ent
-
-    def wave_lps(self, samples, seg, offsets, rows, spec, us):
-        """host samples and tables -> (raw LPS rows [rows, bins], the offset table) on the device: the uploads and the launch are queued on
-        `us` (the caller is inside `with torch.cuda.stream(us)`)"""
-        win, tw = self._wave_tables(spec, us)
-        pcm = torch.from_numpy(np.ascontiguousarray(samples)).to(self.device, non_blocking=True)
-        dseg = torch.from_numpy(np.ascontiguousarray(seg)).to(self.device, non_blocking=True)
-        off = torch.from_numpy(np.ascontiguousarray(offsets)).to(self.device, non_blocking=True)
-        raw = torch.empty(rows, spec.bins, dtype=torch.float32, device=self.device)
-        self.op_feat_wave(pcm, dseg, off, int(seg.shape[0]), win, tw, raw, spec.frame_length, spec.frame_shift, spec.padded, spec.preemph,
-                          stream=us)
-        return raw, off
-
     def _featurize_wave(self, wb, left, right, mean, stddev, ready, limit):
-        """featurize for an io.WaveBatch: the samples and the two tables travel on the upload stream, rsrgan_feat_wave writes the raw LPS
-        rows [frames, bins] and rsrgan_feat_batch normalises, splices and pads those; the hand-off is _featurize_coded's."""
+        """featurize for an io.WaveBatch: the samples and the two tables travel on the upload stream, wave_features writes the raw rows
+        [frames, bins] the batch's spec asks for (rsrgan_feat_wave: LPS; rsrgan_feat_mfcc: MFCC or log-mel) and rsrgan_feat_batch
+        normalises, splices and pads those; the hand-off is _featurize_coded's."""
         offsets, spec = wb.offsets, wb.spec
         B, T, D = int(wb.shape[0]), int(wb.shape[1]), int(wb.dim)
         rows = int(offsets[-1]) if offsets.shape[0] else 0
@@ -390,7 +436,7 @@ class HipEngine(OpEntries):      # (the handle-free rsrgan_op_* wrappers and lau
         us = self.upload_stream()
         dm, ds = self._cmvn_device(mean, stddev, us) if mean is not None else (None, None)
         with torch.cuda.stream(us):
-            raw, off = self.wave_lps(wb.samples, wb.seg, offsets, rows, spec, us)
+            raw, off = self.wave_features(wb.samples, wb.seg, offsets, rows, spec, us)
             out = torch.empty(B, T, D * (left + 1 + right), dtype=torch.float32, device=self.device)
             ln = torch.empty(B, dtype=torch.int32, device=self.device)
             self.op_feat_batch(raw, off, B, T, D, left, right, dm, ds, out, ln, stream=us)
@@ -527,13 +573,6 @@ class HipEngine(OpEntries):      # (the handle-free rsrgan_op_* wrappers and lau
         f64), on `stream` (default: the current one)"""
         check(self.lib.rsrgan_feat_denorm(_ptr(y), _ptr(lengths), B, T, D, _ptr(mean), _ptr(stddev), _ptr(out),
                                           self._stream() if stream is None else C.c_void_p(stream.cuda_stream)))
-
-    def upload_stream(self):
-        """the stream the feature front end uploads and runs on (featurize, featurize_frames, StreamBank)"""
-        us = getattr(self, "_upload_stream", None)
-        if us is None:
-            us = self._upload_stream = torch.cuda.Stream(self.device)
-        return us
 
     def denormalize(self, y, mean, stddev, lengths=None):
         """G(x) y [B, T, D] f32 on the device -> y * stddev + mean as [B, T, D] f64 on the device (rows from lengths[b] on are zero), on the

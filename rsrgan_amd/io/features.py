@@ -180,6 +180,44 @@ def pack_coded(mats, left=0, right=0, mean=None, stddev=None, T=None, names=None
                       right, mean, stddev)
 
 
+def plan_batches(nframes, batch_size, num_buckets, shuffle, rng) -> Iterator[List[int]]:
+    """The batching rule of get_padded_batch (tfrecords_dataset.py:139-175) on frame counts alone: the utterance indices of every batch,
+    in order -- windows of batch_size per length bucket (start 200 frames, width 50, ids clipped at num_buckets), partial windows at
+    the end.  Shared by PaddedBatchReader and io.wave_reader.WaveBatchReader."""
+    order = list(range(len(nframes)))
+    if shuffle:
+        rng.shuffle(order)
+    windows = {}
+    for i in order:
+        if num_buckets > 1:
+            key = min(num_buckets, (nframes[i] - 200) // 50)      # :157-165
+        else:
+            key = 0
+        w = windows.setdefault(key, [])
+        w.append(i)
+        if len(w) == batch_size:
+            yield w
+            windows[key] = []
+    for key in sorted(windows):
+        if windows[key]:
+            yield windows[key]
+
+
+def pad_items(items):
+    """(utt, x [n, D], y [n, Dl]) triples -> [ids, X [B, T, D], Y [B, T, Dl], lengths]: zero padding to the longest utterance"""
+    T = max(x.shape[0] for _, x, _ in items)
+    ids = [u for u, _, _ in items]
+    X = np.empty((len(items), T, items[0][1].shape[1]), np.float32)       # every element is written exactly once below
+    Y = np.empty((len(items), T, items[0][2].shape[1]), np.float32)
+    L = np.zeros(len(items), np.int32)
+    for b, (_, x, y) in enumerate(items):
+        n = x.shape[0]
+        X[b, :n] = x; X[b, n:] = 0.0
+        Y[b, :n] = y; Y[b, n:] = 0.0
+        L[b] = n
+    return [ids, X, Y, L]
+
+
 class PaddedBatchReader(object):
     """get_padded_batch (tfrecords_dataset.py:53-180) without TFRecords: reads (inputs, labels)
     utterance pairs from two scp files, applies CMVN and splicing, groups utterances into windows of
@@ -225,40 +263,14 @@ class PaddedBatchReader(object):
         return self.inputs.utt_ids[i], splice_feats(x, self.left, self.right).astype(np.float32), y.astype(np.float32)
 
     def _pad(self, items):
-        T = max(x.shape[0] for _, x, _ in items)
-        ids = [u for u, _, _ in items]
-        X = np.empty((len(items), T, items[0][1].shape[1]), np.float32)       # every element is written exactly once below
-        Y = np.empty((len(items), T, items[0][2].shape[1]), np.float32)
-        L = np.zeros(len(items), np.int32)
-        for b, (_, x, y) in enumerate(items):
-            n = x.shape[0]
-            X[b, :n] = x; X[b, n:] = 0.0
-            Y[b, :n] = y; Y[b, n:] = 0.0
-            L[b] = n
-        return [ids, X, Y, L]
+        return pad_items(items)
 
     def plan(self) -> Iterator[List[int]]:
         """The utterance indices of every batch, in the order __iter__ yields them -- from the matrix headers alone, so the
         expensive part (materialize) can run on several threads (io.prefetch)."""
         if self._nframes is None:
             self._nframes = [self.inputs.utt_shape_from_index(i)[0] for i in range(len(self))]
-        order = list(range(len(self)))
-        if self.shuffle:
-            self.rng.shuffle(order)
-        windows = {}
-        for i in order:
-            if self.num_buckets > 1:
-                key = min(self.num_buckets, (self._nframes[i] - 200) // 50)      # :157-165
-            else:
-                key = 0
-            w = windows.setdefault(key, [])
-            w.append(i)
-            if len(w) == self.batch_size:
-                yield w
-                windows[key] = []
-        for key in sorted(windows):
-            if windows[key]:
-                yield windows[key]
+        return plan_batches(self._nframes, self.batch_size, self.num_buckets, self.shuffle, self.rng)
 
     def _packed(self, indices):
         ids = [self.inputs.utt_ids[i] for i in indices]

@@ -9,7 +9,12 @@ rsrgan_feat_wave in include/rsrgan.h -- is compute-spectrogram-feats --dither=0 
 
 with N = 400, S = 160, P = 512, eps = FLT_EPSILON (WaveSpec holds them).  lps_from_wave is the HOST route (float64 NumPy, one rounding
 to float32); the device route is HipEngine.op_feat_wave / featurize(WaveBatch) / StreamBank.push_audio (csrc/wave.hip), which take the
-window and the twiddles as tables built here in float64 and rounded once."""
+window and the twiddles as tables built here in float64 and rounded once.
+
+The labels of the recipes are another feature of the same audio: 40-dim MFCC (Kaldi's compute-mfcc-feats with the WSJ mfcc_hires.conf),
+stated at rsrgan_feat_mfcc in include/rsrgan.h.  MfccSpec holds its parameters, mel_table / dct_table build the filterbank and the
+liftered DCT the kernel takes as tables, mfcc_from_wave is the host route; the device route is HipEngine.op_feat_mfcc /
+featurize(WaveBatch with an MfccSpec) (csrc/wave.hip k_feat_mfcc).  io/wave_reader.py reads training batches from two wav.scp files."""
 from __future__ import annotations
 
 import wave as _wave
@@ -48,6 +53,159 @@ class WaveSpec(object):
 
 
 DEFAULT = WaveSpec()
+
+
+def _frames_per_workgroup(P):
+    """csrc/wave.hip wave_frames: the frames a workgroup takes"""
+    return 8 if P <= 1024 else 2
+
+
+class MfccSpec(WaveSpec):
+    """the labels' front end (include/rsrgan.h rsrgan_feat_mfcc): WaveSpec's framing, Povey window by default, then num_mel_bins M
+    triangular mel filters between low_freq and high_freq (a high_freq <= 0 is an offset from Nyquist), the log, and num_ceps C rows of
+    the DCT with the cepstral lifter Q multiplied in (Q = 0: none).  num_ceps = 0 means log-mel output (Kaldi's fbank features).  The
+    defaults are compute-mfcc-feats with the WSJ conf/mfcc_hires.conf.  Refused: M outside [1, 128], C outside [0, M], not
+    0 <= low < high <= Nyquist, a negative lifter, a table of no or more than 8192 weights, a launch above 64 KB of LDS."""
+
+    def __init__(self, frame_length=400, frame_shift=160, padded=512, preemph=0.97, window="povey", sample_rate=16000, num_mel_bins=40,
+                 num_ceps=40, low_freq=20.0, high_freq=-400.0, cepstral_lifter=22.0):
+        WaveSpec.__init__(self, frame_length, frame_shift, padded, preemph, window, sample_rate)
+        self.num_mel_bins, self.num_ceps = int(num_mel_bins), int(num_ceps)
+        self.low_freq, self.high_freq, self.cepstral_lifter = float(low_freq), float(high_freq), float(cepstral_lifter)
+        M, C = self.num_mel_bins, self.num_ceps
+        if not 1 <= M <= 128:
+            raise ValueError("num_mel_bins = %d outside [1, 128]" % M)
+        if not 0 <= C <= M:
+            raise ValueError("num_ceps = %d outside [0, num_mel_bins = %d]" % (C, M))
+        if self.sample_rate < 1:
+            raise ValueError("sample_rate = %d must be positive" % self.sample_rate)
+        lo, hi = self.band()
+        if not 0.0 <= lo < hi <= 0.5 * self.sample_rate:
+            raise ValueError("low_freq = %r, high_freq = %r: the band [%g, %g] Hz is not inside 0 <= low < high <= Nyquist = %g" % (
+                low_freq, high_freq, lo, hi, 0.5 * self.sample_rate))
+        if not self.cepstral_lifter >= 0.0:
+            raise ValueError("cepstral_lifter = %r must be 0 (none) or positive" % cepstral_lifter)
+        nnz = sum(w.shape[0] for _, w in _mel_filters(self))
+        if not 1 <= nnz <= 8192:
+            raise ValueError("the mel table holds %d weights, outside [1, 8192]" % nnz)
+        self.nnz = nnz
+        if self.lds_bytes() > 65536:
+            raise ValueError("frame_length = %d, frame_shift = %d, padded = %d, num_mel_bins = %d, num_ceps = %d, %d weights need %d bytes of "
+                             "LDS, above the kernel's 65536" % (self.frame_length, self.frame_shift, self.padded, M, C, nnz, self.lds_bytes()))
+
+    def band(self):
+        """(low, high) in Hz after the offset rule"""
+        return self.low_freq, self.high_freq if self.high_freq > 0.0 else 0.5 * self.sample_rate + self.high_freq
+
+    def lds_bytes(self):
+        """the dynamic LDS of the launch (include/rsrgan.h rsrgan_feat_mfcc states the formula)"""
+        N, S, P, M, C = self.frame_length, self.frame_shift, self.padded, self.num_mel_bins, self.num_ceps
+        F, H = _frames_per_workgroup(P), P // 2
+        nz = min(4, F)
+        return 8 * (H + nz * H) + 4 * (2 * N + (F - 1) * S) + 4 * (nz * H + nz * M + M * C + 3 * M + self.nnz)
+
+    @property
+    def bins(self):
+        return self.num_ceps if self.num_ceps else self.num_mel_bins
+
+    def key(self):
+        return WaveSpec.key(self) + ("mfcc", self.sample_rate, self.num_mel_bins, self.num_ceps, self.low_freq, self.high_freq,
+                                     self.cepstral_lifter)
+
+
+_FILTERS, _DCTS = {}, {}          # the float64 tables of the host route, kept per (the fields they depend on): built once, read-only
+
+
+def _mel(f):
+    return 1127.0 * np.log(1.0 + np.asarray(f, np.float64) / 700.0)
+
+
+def _mel_filters(spec):
+    """[(first bin a_j, float64 weights [n_j])] of the M filters over the bins [0, P / 2) (Kaldi's MelBanks: the Nyquist bin never enters)"""
+    M, P = spec.num_mel_bins, spec.padded
+    lo, hi = spec.band()
+    ck = (P, spec.sample_rate, M, lo, hi)
+    if ck in _FILTERS:
+        return _FILTERS[ck]
+    mlo, mhi = float(_mel(lo)), float(_mel(hi))
+    delta = (mhi - mlo) / (M + 1)
+    mel = _mel(np.arange(P // 2, dtype=np.float64) * spec.sample_rate / P)
+    out = []
+    for j in range(M):
+        left, centre, right = mlo + j * delta, mlo + (j + 1) * delta, mlo + (j + 2) * delta
+        idx = np.flatnonzero((mel > left) & (mel < right))
+        if idx.shape[0] == 0:
+            out.append((0, np.zeros(0, np.float64)))
+            continue
+        a, n = int(idx[0]), int(idx.shape[0])
+        assert int(idx[-1]) == a + n - 1                              # (mel ascends with the bin: a filter is contiguous)
+        m = mel[a:a + n]
+        out.append((a, np.where(m <= centre, (m - left) / (centre - left), (right - m) / (right - centre))))
+    for _, w in out:
+        w.setflags(write=False)
+    if len(_FILTERS) > 16:
+        _FILTERS.clear()
+    _FILTERS[ck] = out
+    return out
+
+
+def mel_table(spec):
+    """(mel_seg int32 [M, 3] = (first bin, bins, index of the first weight in mel_w), mel_w float32 [nnz]): built in float64, rounded once"""
+    filt = _mel_filters(spec)
+    seg, at = np.zeros((len(filt), 3), np.int32), 0
+    for j, (a, w) in enumerate(filt):
+        seg[j] = (a, w.shape[0], at)
+        at += w.shape[0]
+    return seg, np.ascontiguousarray(np.concatenate([w for _, w in filt]).astype(np.float32))
+
+
+def _dct64(spec):
+    """float64 [C, M]: Kaldi's ComputeDctMatrix (row 0 sqrt(1 / M), row k sqrt(2 / M) cos(pi / M (n + 1/2) k)), row i times the lifter
+    1 + (Q / 2) sin(pi i / Q)"""
+    M, C, Q = spec.num_mel_bins, spec.num_ceps, spec.cepstral_lifter
+    if (M, C, Q) in _DCTS:
+        return _DCTS[M, C, Q]
+    k, n = np.arange(C, dtype=np.float64)[:, None], np.arange(M, dtype=np.float64)[None, :]
+    d = np.sqrt(2.0 / M) * np.cos(np.pi / M * (n + 0.5) * k)
+    d[:1] = np.sqrt(1.0 / M)
+    if Q > 0.0:
+        d *= 1.0 + 0.5 * Q * np.sin(np.pi * k / Q)
+    d.setflags(write=False)
+    if len(_DCTS) > 16:
+        _DCTS.clear()
+    _DCTS[M, C, Q] = d
+    return d
+
+
+def dct_table(spec):
+    """float32 [C, M] row-major, the lifter multiplied in: built in float64, rounded once ([0, M] for log-mel output)"""
+    return np.ascontiguousarray(_dct64(spec).astype(np.float32))
+
+
+MFCC_DEFAULT = MfccSpec()
+
+
+def mfcc_from_wave(x, spec=MFCC_DEFAULT):
+    """the host route of the labels: samples [n] -> MFCC [F, C] (or log-mel [F, M] with num_ceps = 0) float32, the definition of
+    rsrgan_feat_mfcc in float64 (np.fft.rfft, float64 tables), rounded once"""
+    N, S, P = spec.frame_length, spec.frame_shift, spec.padded
+    x = np.asarray(x)
+    if x.ndim != 1:
+        raise ValueError("samples must be a 1-D array, got shape %s" % (x.shape,))
+    F = num_frames(x.shape[0], spec)
+    if F == 0:
+        return np.zeros((0, spec.bins), np.float32)
+    v = x[np.arange(F)[:, None] * S + np.arange(N)[None, :]].astype(np.float64)
+    v -= v.sum(1, keepdims=True) / N
+    v = v - spec.preemph * np.concatenate([v[:, :1], v[:, :-1]], 1)
+    v *= window_table(spec.window, N)
+    X = np.fft.rfft(v, n=P, axis=1)
+    p = X.real ** 2 + X.imag ** 2
+    m = np.stack([p[:, a:a + w.shape[0]] @ w for a, w in _mel_filters(spec)], 1)
+    out = np.log(np.maximum(m, EPS))
+    if spec.num_ceps:
+        out = out @ _dct64(spec).T
+    return out.astype(np.float32)
 
 
 def window_table(name="hamming", N=400):

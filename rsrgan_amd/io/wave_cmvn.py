@@ -1,0 +1,95 @@
+"""The global CMVN statistics of a training set given as AUDIO: the train_cmvn.npz the recipes load, from two wav.scp files.
+
+    python -m rsrgan_amd.io.wave_cmvn --inputs_wav_scp tr/inputs_wav.scp --labels_wav_scp tr/labels_wav.scp --out data/train/train_cmvn.npz [--device]
+
+Inputs become log-power-spectrum frames (io.wave.DEFAULT), labels MFCC frames (io.wave.MFCC_DEFAULT).  Per dimension, sum x and sum x^2
+over all frames are accumulated in float64; mean = sum x / n, stddev = sqrt(sum x^2 / n - mean^2), as the reference's
+convert_cmvn_to_numpy.py computes them from Kaldi's statistics.  --device: the frames come from the two kernels of csrc/wave.hip and are
+summed with float64 torch reductions on the device.  A dimension with zero variance is an error here, not a division by zero later."""
+from __future__ import annotations
+
+import argparse
+
+import numpy as np
+
+from . import wave as W
+
+
+def _finish(name, sx, sxx, n):
+    if n < 1:
+        raise ValueError("%s: no frames" % name)
+    mean = sx / n
+    var = sxx / n - mean * mean
+    bad = np.flatnonzero(~(var > 0.0))
+    if bad.shape[0]:
+        raise ValueError("%s: dimension %d has no variance over the %d frames (sum x^2 / n - mean^2 = %g)" % (name, int(bad[0]), n, var[bad[0]]))
+    return mean, np.sqrt(var)
+
+
+def _host_sums(items, spec, featurize):
+    sx, sxx, n = np.zeros(spec.bins), np.zeros(spec.bins), 0
+    for _, path in items:
+        f = featurize(W.read_wav(path, sample_rate=spec.sample_rate)).astype(np.float64)
+        sx += f.sum(0); sxx += (f * f).sum(0); n += f.shape[0]
+    return sx, sxx, n
+
+
+def _device_sums(items, spec, engine, batch=64):
+    import torch
+    sx = sxx = None
+    n = 0
+    us = engine.upload_stream()
+    for lo in range(0, len(items), batch):
+        wb = W.pack_wave([W.read_wav(p, sample_rate=spec.sample_rate) for _, p in items[lo:lo + batch]], spec=spec)
+        rows = int(wb.offsets[-1])
+        if rows < 1:
+            continue
+        with torch.cuda.stream(us):
+            f = engine.wave_features(wb.samples, wb.seg, wb.offsets, rows, spec, us)[0].double()
+            a, b = f.sum(0), (f * f).sum(0)
+            sx, sxx = (a, b) if sx is None else (sx + a, sxx + b)
+        n += rows
+    if sx is None:
+        return np.zeros(spec.bins), np.zeros(spec.bins), 0
+    us.synchronize()
+    return sx.cpu().numpy(), sxx.cpu().numpy(), n
+
+
+def wave_ops():
+    """the waveform front end without a model: the handle-free entries on the current device (HipEngine's base class)"""
+    from ..engine_hip import WaveFrontEnd
+    return WaveFrontEnd()
+
+
+def wave_cmvn(inputs_wav_scp, labels_wav_scp, engine=None, input_spec=W.DEFAULT, label_spec=W.MFCC_DEFAULT):
+    """{mean_inputs, stddev_inputs, mean_labels, stddev_labels} (float64) over all frames of the two wav.scp files; engine: a HipEngine for
+    the device route, None for the host route"""
+    xs, ys = W.read_wav_scp(inputs_wav_scp), W.read_wav_scp(labels_wav_scp)
+    if engine is None:
+        si = _host_sums(xs, input_spec, lambda s: W.lps_from_wave(s, spec=input_spec))
+        sl = _host_sums(ys, label_spec, lambda s: W.mfcc_from_wave(s, label_spec))
+    else:
+        si, sl = _device_sums(xs, input_spec, engine), _device_sums(ys, label_spec, engine)
+    mi, di = _finish("inputs", *si)
+    ml, dl = _finish("labels", *sl)
+    return {"mean_inputs": mi, "stddev_inputs": di, "mean_labels": ml, "stddev_labels": dl}
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    p.add_argument("--inputs_wav_scp", required=True)
+    p.add_argument("--labels_wav_scp", required=True)
+    p.add_argument("--out", required=True, help="the .npz to write (the recipes read <data_dir>/train_cmvn.npz)")
+    p.add_argument("--device", default=False, action="store_true", help="make and sum the frames on the device")
+    a = p.parse_args(argv)
+    engine = wave_ops() if a.device else None
+    try:
+        stats = wave_cmvn(a.inputs_wav_scp, a.labels_wav_scp, engine)
+    except (OSError, EOFError, ValueError) as e:
+        raise SystemExit("wave_cmvn: %s" % e)
+    np.savez(a.out, **stats)
+    return stats
+
+
+if __name__ == "__main__":
+    main()

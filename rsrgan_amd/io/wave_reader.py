@@ -1,0 +1,95 @@
+"""Training batches from audio: PaddedBatchReader's sibling over two wav.scp files (reverberant inputs, clean labels) instead of two feature
+archives.  Inputs become log-power-spectrum frames (io.wave.WaveSpec), labels MFCC frames (io.wave.MfccSpec: compute-mfcc-feats with
+mfcc_hires.conf), on the host or on the device."""
+from __future__ import annotations
+
+import random
+import wave as _wave
+from typing import Iterator, List
+
+import numpy as np
+
+from .features import apply_cmvn, pad_items, plan_batches, splice_feats
+from .wave import DEFAULT, MFCC_DEFAULT, lps_from_wave, mfcc_from_wave, num_frames, pack_wave, read_wav, read_wav_scp
+
+
+class WaveBatchReader(object):
+    """Reads (inputs, labels) utterance pairs from two wav.scp files (lines `utt path`, 16-bit PCM; the utterance ids of the two files
+    equal and in the same order) and yields PaddedBatchReader's items with its plan() rules: windows of `batch_size` by length bucket
+    (start 200 frames, width 50, ids clipped at num_buckets), partial windows at the end.  The frame counts come from the wav headers
+    alone (no sample is read before materialize), so io.prefetch can run materialize on several threads.
+
+    Default route: lps_from_wave / mfcc_from_wave on the host (float64, one rounding), then PaddedBatchReader's float64 CMVN, splice and
+    zero padding: the items are ordinary padded batches [utt_ids, inputs [B, T, bins * (L + 1 + R)] f32, labels [B, T, label bins] f32,
+    lengths [B] i32].
+    device_features=True: the samples travel; the items are [utt_ids, WaveBatch(inputs), WaveBatch(labels), lengths] and the device makes
+    the frames (csrc/wave.hip k_feat_wave / k_feat_mfcc), normalises, splices and pads them (HipEngine.featurize).
+
+    ValueError at construction, naming the utterance: a pair whose two files make different frame counts, an utterance that makes no
+    frame, ids that differ between the two files."""
+
+    def __init__(self, inputs_wav_scp, labels_wav_scp, batch_size, left_context=0, right_context=0, cmvn=None, num_buckets=20, shuffle=True,
+                 seed=None, device_features=False, input_spec=DEFAULT, label_spec=MFCC_DEFAULT):
+        self.device_features = bool(device_features)
+        self.input_spec, self.label_spec = input_spec, label_spec
+        self._stats = None
+        if self.device_features and cmvn is not None:
+            self._stats = tuple(np.ascontiguousarray(cmvn[k], np.float64).reshape(-1)
+                                for k in ("mean_inputs", "stddev_inputs", "mean_labels", "stddev_labels"))
+        self.inputs, self.labels = read_wav_scp(inputs_wav_scp), read_wav_scp(labels_wav_scp)
+        self.utt_ids = [u for u, _ in self.inputs]
+        if self.utt_ids != [u for u, _ in self.labels]:
+            raise ValueError("%s and %s do not list the same utterance ids in the same order" % (inputs_wav_scp, labels_wav_scp))
+        self.batch_size, self.left, self.right = batch_size, left_context, right_context
+        self.cmvn, self.num_buckets, self.shuffle = cmvn, num_buckets, shuffle
+        self.rng = random.Random(seed)
+        self._nframes = []
+        for (u, px), (_, py) in zip(self.inputs, self.labels):
+            fx, fy = num_frames(_header_samples(px), input_spec), num_frames(_header_samples(py), label_spec)
+            if fx != fy:
+                raise ValueError("utterance %s: %d input frames (%s), %d label frames (%s)" % (u, fx, px, fy, py))
+            if fx == 0:
+                raise ValueError("utterance %s: %s makes no frame (fewer than %d samples)" % (u, px, input_spec.frame_length))
+            self._nframes.append(fx)
+
+    def __len__(self):
+        return len(self.utt_ids)
+
+    def plan(self) -> Iterator[List[int]]:
+        """the utterance indices of every batch, in the order __iter__ yields them: PaddedBatchReader's rule on the headers' frame counts"""
+        return plan_batches(self._nframes, self.batch_size, self.num_buckets, self.shuffle, self.rng)
+
+    def __iter__(self) -> Iterator[List]:
+        for indices in self.plan():
+            yield self.materialize(indices)
+
+    def _samples(self, i):
+        return (read_wav(self.inputs[i][1], sample_rate=self.input_spec.sample_rate),
+                read_wav(self.labels[i][1], sample_rate=self.label_spec.sample_rate))
+
+    def _utt(self, i):
+        sx, sy = self._samples(i)
+        x = lps_from_wave(sx, spec=self.input_spec).astype(np.float64)
+        y = mfcc_from_wave(sy, self.label_spec).astype(np.float64)
+        if self.cmvn is not None:
+            x, y = apply_cmvn(x, y, self.cmvn)
+        return self.utt_ids[i], splice_feats(x, self.left, self.right).astype(np.float32), y.astype(np.float32)
+
+    def _waves(self, indices):
+        ids = [self.utt_ids[i] for i in indices]
+        pairs = [self._samples(i) for i in indices]
+        mi, si, ml, sl = self._stats if self._stats is not None else (None,) * 4
+        X = pack_wave([p[0] for p in pairs], None, self.left, self.right, mi, si, self.input_spec, names=ids)
+        Y = pack_wave([p[1] for p in pairs], None, 0, 0, ml, sl, self.label_spec, names=ids)
+        return [ids, X, Y, X.lengths()]
+
+    def materialize(self, indices: List[int]) -> List:
+        if self.device_features:
+            return self._waves(indices)
+        return pad_items([self._utt(i) for i in indices])
+
+
+def _header_samples(path):
+    """samples per channel of a RIFF file, from its header alone"""
+    with _wave.open(str(path), "rb") as f:
+        return f.getnframes()

@@ -81,6 +81,11 @@ def build_parser():
                    "16-bit PCM wav files at 16 kHz; the log-power-spectrum frames (io/wave.py: 400 samples every 160, Hamming, 257 bins) are "
                    "computed on the host, or with --device_features on the device (csrc/wave.hip); with --decode_push K the live path is "
                    "driven by pushes of K x 160 samples")
+    for n in ("tr_inputs_wav_scp", "tr_labels_wav_scp", "cv_inputs_wav_scp", "cv_labels_wav_scp"):
+        p.add_argument("--" + n, type=str, default=None, help="train from AUDIO: a wav.scp (lines `utt path`, 16-bit PCM at 16 kHz) in place "
+                       "of the split's *_scp archive; inputs become 257-bin log-power-spectrum frames, labels 40-dim MFCC frames "
+                       "(io/wave.py MfccSpec: compute-mfcc-feats with mfcc_hires.conf), on the host, or with --device_features on the "
+                       "device (csrc/wave.hip); given in pairs")
     return p
 
 
@@ -130,6 +135,39 @@ def _cmvn(FLAGS):
     return np.load(path)
 
 
+def check_wav_flags(FLAGS):
+    """the *_wav_scp flags come in pairs, replace the split's archive flags and do not go with --device_decode; the two dims are the
+    specs' bins.  SystemExit with a message otherwise."""
+    from .io import wave as W
+    any_wav = False
+    for split in ("tr", "cv"):
+        a, b = (getattr(FLAGS, "%s_%s_wav_scp" % (split, k), None) for k in ("inputs", "labels"))
+        if bool(a) != bool(b):
+            raise SystemExit("--%s_inputs_wav_scp and --%s_labels_wav_scp are given together or not at all" % (split, split))
+        if a and (getattr(FLAGS, split + "_inputs_scp", None) or getattr(FLAGS, split + "_labels_scp", None)):
+            raise SystemExit("--%s_*_wav_scp reads audio in place of --%s_inputs_scp / --%s_labels_scp: give one kind per split" % (
+                split, split, split))
+        any_wav = any_wav or bool(a)
+    if any_wav and _device_decode(FLAGS):
+        raise SystemExit("--*_wav_scp reads audio, --device_decode decodes archives: use --device_features for the device route")
+    if any_wav and (int(FLAGS.input_dim) != W.DEFAULT.bins or int(FLAGS.output_dim) != W.MFCC_DEFAULT.bins):
+        raise SystemExit("--*_wav_scp makes input frames of %d bins and label frames of %d; --input_dim is %d, --output_dim is %d" % (
+            W.DEFAULT.bins, W.MFCC_DEFAULT.bins, int(FLAGS.input_dim), int(FLAGS.output_dim)))
+
+
+def split_reader(FLAGS, split, cmvn, shuffle, seed):
+    """the reader of a split ("tr" / "cv"): over its two wav.scp files if they are given, over its two archives otherwise"""
+    wav = getattr(FLAGS, split + "_inputs_wav_scp", None)
+    if wav:
+        from .io.wave_reader import WaveBatchReader
+        try:
+            return WaveBatchReader(wav, getattr(FLAGS, split + "_labels_wav_scp"), FLAGS.batch_size * FLAGS.num_gpu, FLAGS.left_context,
+                                   FLAGS.right_context, cmvn=cmvn, shuffle=shuffle, seed=seed, device_features=_device_features(FLAGS))
+        except (OSError, EOFError, ValueError) as e:
+            raise SystemExit("--%s_*_wav_scp: %s" % (split, e))
+    return _reader(FLAGS, getattr(FLAGS, split + "_inputs_scp"), getattr(FLAGS, split + "_labels_scp"), cmvn, shuffle, seed)
+
+
 def _reader(FLAGS, inputs_scp, labels_scp, cmvn, shuffle, seed):
     return PaddedBatchReader(inputs_scp, labels_scp, FLAGS.batch_size * FLAGS.num_gpu, FLAGS.left_context, FLAGS.right_context,
                              cmvn=cmvn, shuffle=shuffle, seed=seed, device_features=_device_features(FLAGS), device_decode=_device_decode(FLAGS))
@@ -143,6 +181,7 @@ def get_num_batch(reader, full):
 
 def train(FLAGS, model_factory=None, log=print, net_overrides=None):
     """train (:388-584) + the batch counting of main (:305-343).  Returns the list of per-iteration CV g_loss."""
+    check_wav_flags(FLAGS)
     cmvn = _cmvn(FLAGS)
     mk = model_factory or (lambda cv, share: GAN_RNN(None, FLAGS, ["gpu:%d" % rdist.rank()], cross_validation=cv,
                                                       max_frames=FLAGS.max_frames, share_engine_from=share,
@@ -154,10 +193,10 @@ def train(FLAGS, model_factory=None, log=print, net_overrides=None):
     else:
         log("[!] Begin a new model.")
     full = FLAGS.batch_size * FLAGS.num_gpu
-    tr_reader = _reader(FLAGS, FLAGS.tr_inputs_scp, FLAGS.tr_labels_scp, cmvn, True, 1234)
-    cv_reader = _reader(FLAGS, FLAGS.cv_inputs_scp, FLAGS.cv_labels_scp, cmvn, False, None)
-    tr_num_batch = get_num_batch(_reader(FLAGS, FLAGS.tr_inputs_scp, FLAGS.tr_labels_scp, None, False, None), full)
-    cv_num_batch = get_num_batch(_reader(FLAGS, FLAGS.cv_inputs_scp, FLAGS.cv_labels_scp, None, False, None), full)
+    tr_reader = split_reader(FLAGS, "tr", cmvn, True, 1234)
+    cv_reader = split_reader(FLAGS, "cv", cmvn, False, None)
+    tr_num_batch = get_num_batch(split_reader(FLAGS, "tr", None, False, None), full)
+    cv_num_batch = get_num_batch(split_reader(FLAGS, "cv", None, False, None), full)
     train_batch_per_iter, valdi_batch_per_iter = tr_num_batch, cv_num_batch
     min_iters = int(FLAGS.min_epoches * tr_num_batch / train_batch_per_iter)
     max_iters = int(FLAGS.max_epoches * tr_num_batch / train_batch_per_iter)
@@ -241,7 +280,7 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
     writer = ArkWriter(write_scp_path)
     wav = getattr(FLAGS, "wav_scp", None)
     if wav:
-        # --wav_scp: audio instead of an archive of frames.  Training from audio is out of scope: the labels are another feature type
+        # --wav_scp: audio instead of an archive of frames (training from audio: the --tr_*_wav_scp / --cv_*_wav_scp flags)
         if _device_decode(FLAGS):
             raise SystemExit("--wav_scp reads audio, --device_decode decodes archives: use --device_features for the device route")
         reader = _WavSource(wav, FLAGS.input_dim)

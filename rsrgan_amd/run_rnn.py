@@ -21,7 +21,7 @@ import numpy as np
 from . import dist as rdist
 from . import run_gan_rnn as gan_loop
 from .io import prefetch
-from .run_gan_rnn import _cmvn, _reader, get_num_batch, str2bool
+from .run_gan_rnn import _cmvn, check_wav_flags, get_num_batch, split_reader, str2bool
 from .train import _batches, _check_device, _on_stream, device_batch, exponential_decay
 from .trainer import RNNTrainer
 
@@ -65,6 +65,9 @@ def build_parser():
                    "bytes travel undecoded and the device decodes them (run_gan_rnn --device_decode)")
     p.add_argument("--wav_scp", type=str, default=None, help="decode: read audio (lines `utt path`, 16-bit PCM wav at 16 kHz) instead of "
                    "--test_inputs_scp (run_gan_rnn --wav_scp)")
+    for n in ("tr_inputs_wav_scp", "tr_labels_wav_scp", "cv_inputs_wav_scp", "cv_labels_wav_scp"):
+        p.add_argument("--" + n, type=str, default=None, help="train from audio: a wav.scp in place of the split's *_scp archive "
+                       "(run_gan_rnn --%s)" % n)
     return p
 
 
@@ -114,6 +117,7 @@ def _model(FLAGS, cv, share, net_overrides, **kw):
 
 def train(FLAGS, model_factory=None, log=print, net_overrides=None):
     """train (:270-430) + the batch counting of main (:196-221).  Returns the list of per-iteration CV g_loss."""
+    check_wav_flags(FLAGS)
     cmvn = _cmvn(FLAGS)
     mk = model_factory or (lambda cv, share: _model(FLAGS, cv, share, net_overrides, max_frames=FLAGS.max_frames))
     tr_model = mk(False, None)
@@ -123,10 +127,10 @@ def train(FLAGS, model_factory=None, log=print, net_overrides=None):
     else:
         log("[!] Begin a new model.")
     full = FLAGS.batch_size * FLAGS.num_gpu
-    tr_reader = _reader(FLAGS, FLAGS.tr_inputs_scp, FLAGS.tr_labels_scp, cmvn, True, 1234)
-    cv_reader = _reader(FLAGS, FLAGS.cv_inputs_scp, FLAGS.cv_labels_scp, cmvn, False, None)
-    tr_num_batch = get_num_batch(_reader(FLAGS, FLAGS.tr_inputs_scp, FLAGS.tr_labels_scp, None, False, None), full)
-    cv_num_batch = get_num_batch(_reader(FLAGS, FLAGS.cv_inputs_scp, FLAGS.cv_labels_scp, None, False, None), full)
+    tr_reader = split_reader(FLAGS, "tr", cmvn, True, 1234)
+    cv_reader = split_reader(FLAGS, "cv", cmvn, False, None)
+    tr_num_batch = get_num_batch(split_reader(FLAGS, "tr", None, False, None), full)
+    cv_num_batch = get_num_batch(split_reader(FLAGS, "cv", None, False, None), full)
     train_batch_per_iter, valdi_batch_per_iter = tr_num_batch, cv_num_batch                  # :204-205
     min_iters = int(FLAGS.min_epochs * tr_num_batch / train_batch_per_iter)
     max_iters = int(FLAGS.max_epochs * tr_num_batch / train_batch_per_iter)

@@ -45,9 +45,9 @@ def _dpipe():
 
 
 def is_packed(a):
-    """an io.PackedBatch (raw frames and offsets) or an io.CodedBatch (the archive's bytes and offsets): to be normalised, spliced and
-    padded -- the latter decoded first -- on the device"""
-    return hasattr(a, "offsets") and hasattr(a, "rows") and (hasattr(a, "data") or hasattr(a, "blob"))
+    """an io.PackedBatch (raw frames and offsets), an io.CodedBatch (the archive's bytes and offsets) or an io.WaveBatch (audio samples and
+    offsets): to be normalised, spliced and padded -- the second decoded, the third turned into LPS or MFCC frames first -- on the device"""
+    return hasattr(a, "offsets") and hasattr(a, "rows") and (hasattr(a, "data") or hasattr(a, "blob") or hasattr(a, "samples"))
 
 
 def device_batch(model, inputs, labels, lengths, d_run=True):
