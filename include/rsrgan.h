@@ -597,6 +597,48 @@ int rsrgan_feat_mfcc(const void* pcm, int32_t kind, int64_t n_samples, const int
 /* The frames one workgroup of rsrgan_feat_wave or rsrgan_feat_mfcc takes (consecutive frames of one utterance, whose overlapping samples
  * it reads once); 0 for a P the entries refuse.  Tests place their utterance lengths around it. */
 int rsrgan_feat_wave_frames(int32_t P);
+/* Reverberate clean audio on the device (csrc/reverb.hip): what Kaldi's wav-reverberate --impulse-response=..
+ * --shift-output --normalize-output [--additive-signals .. --snrs .. --start-times ..] does, as its documentation and the reference's
+ * reverberate/ scripts describe it, stated here in full.  No Kaldi source or binary was available to compare against: bit parity with
+ * Kaldi is NOT pinned; the tests pin the definition below against float64.
+ * Per utterance b: x[0 .. n) its samples seg[b] = (first sample, count) of pcm (kind 0: int16 widened without scaling, kind 1: float32 on
+ * that scale); sel[b] = (rir index, noise index, s, m).  RIR r is taps rir_seg[r] = (first tap, L, q, e0, e1) of rir (float32): q the index
+ * of the FIRST maximum of h (Kaldi's Vector::Max), [e0, e1) = [max(q - floor(0.001 fs), 0), min(q + floor(0.05 fs), L)) the early part;
+ * the host fills them (rsrgan_amd/io/reverb.py rir_table), the kernels take them as given and clamp them.  Noise v is samples
+ * noise_seg[v] = (first, nv) of noise (float32) with its power P_v = noise_pow[v] (computed on the host in fp64).
+ *   1. P_in = (1 / n) sum x^2
+ *   2. y = x * h, full length len = n + L - 1.  rir index -1 (or outside [0, R)): y = x, len = n, q = 0
+ *   3. E = (1 / (n + (e1 - e0) - 1)) sum (x * h[e0 .. e1))^2, the early-reverberation energy (e1 = e0: E = 0); without an RIR E = P_in.
+ *      It is formed only when a noise is selected
+ *   4. noise index -1 (or outside [0, V), or nv = 0): none, g = 0.  Else y[s + i] += g v[i mod nv] for 0 <= i < m, s + i < len, with
+ *      g = sqrt(10^(-snr[b] / 10) E / P_v); g = 0 if E = 0 or P_v = 0 (or P_v, g not finite)
+ *   5. flags & 2 (normalize): c = sqrt(P_in / P_out), P_out = (1 / len) sum y^2 after the noise; c = 1 if P_out = 0.  Else c = 1
+ *   6. out[first_b + i] = c y[i + (flags & 1 ? q : 0)] for i < min(n_out, capacity_b), out_seg[b] = (first, capacity); n_out = n with
+ *      flags & 1 (shift), else len.  float32 on the int16 scale, not quantised.  gains[b] = (c, g) if gains is given.
+ * Arithmetic: uniformly partitioned overlap-save in fp32.  C is the complex FFT length, a block C / 2 samples; the RIR is cut into
+ * ceil(L / (C / 2)) partitions whose spectra are formed per call, per utterance, in `work`; output block k is the inverse transform of
+ * sum_p X[k - p] H[p], p ascending; two real blocks ride one complex transform.  twiddle [C][2] float32 = (cos, -sin)(2 pi j / 2 C), j < C
+ * (rsrgan_amd/io/wave.py twiddle_table(2 C)): no sincosf.  The sums of squares and the cross term sum y v are fp32 per block in a fixed
+ * order and are finished per utterance in fp64 in block order, P_out as sum y^2 + 2 g sum y v + g^2 sum v^2; no atomics: an utterance's
+ * output bits depend on its samples, its tables and C only, not on its place in the batch or on B.
+ * Clamps: every segment into its buffer, n to 2^28, L to 2^24, q into [0, L), e0 <= e1 into [0, L], s into [0, len], m into
+ * [0, len - s], the capacity into out: the kernels read and write nothing outside their buffers, whatever the device-resident tables
+ * hold, and utterance b writes min(n_out, capacity_b) samples of out and nothing else there.  work: utterance b owns
+ * work + b * (work_bytes / B rounded down to 16); an utterance that needs more than its slot (longer than the n_max, L_max the caller
+ * sized for) writes nothing and has gains (1, 0); so does an empty one.  rsrgan_wave_reverb_work(B, n_max, L_max, C): the bytes for B
+ * utterances of at most n_max samples against at most L_max taps; 0 for B outside [1, 65535], n_max outside [1, 2^28], L_max outside
+ * [0, 2^24] or a C the entry refuses.  No handle, no allocation, nothing synchronises with the host; four launches on `stream`.  All
+ * pointers are DEVICE pointers.  RSRGAN_ERR_INVALID before the first HIP call, rsrgan_last_error() naming the argument, for: a null pcm,
+ * seg, sel, snr, out, out_seg, twiddle or work; a null rir or rir_seg with R > 0; a null noise, noise_seg or noise_pow with V > 0; B
+ * outside [1, 65535]; R or V outside [0, 2^20]; a kind other than 0 or 1; pcm not aligned to its element; work not 16-byte, seg,
+ * rir_seg, noise_seg or out_seg not 8-byte, any other pointer not 4-byte aligned; n_samples or out_samples outside [1, 2^40]; n_taps
+ * (n_noise) outside [R > 0, 2^40] ([V > 0, 2^40]); C no power of two in [64, 2048]; flags outside [0, 3]; work_bytes below
+ * rsrgan_wave_reverb_work(B, 1, 1, C). */
+int rsrgan_wave_reverb(const void* pcm, int32_t kind, int64_t n_samples, const int64_t* seg, const float* rir, int64_t n_taps,
+                       const int64_t* rir_seg, const float* noise, int64_t n_noise, const int64_t* noise_seg, const float* noise_pow,
+                       const int32_t* sel, const float* snr, int32_t B, int32_t R, int32_t V, int32_t C, const float* twiddle, int32_t flags,
+                       float* out, int64_t out_samples, const int64_t* out_seg, float* gains, void* work, int64_t work_bytes, void* stream);
+int64_t rsrgan_wave_reverb_work(int32_t B, int64_t n_max, int64_t L_max, int32_t C);
 
 /* ---- TensorBoard histogram summaries on the device (csrc/hist.hip): what tf.summary.histogram's HistogramProto holds,
  * computed where the tensors are.  No handle.  x: a HOST table of n DEVICE pointers to float32 tensors; dims: a HOST table of n x

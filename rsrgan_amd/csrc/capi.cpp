@@ -651,6 +651,54 @@ int rsrgan_feat_mfcc(const void* pcm, int32_t kind, int64_t n_samples, const int
 
 int rsrgan_feat_wave_frames(int32_t P) { return (P >= 64 && P <= 2048 && !(P & (P - 1))) ? wave_frames(P) : 0; }
 
+// ---- reverberation on the device (reverb.hip): no handle, no allocation; four launches on the caller's stream
+static bool reverb_sizes_ok(int32_t B, int64_t n_max, int64_t L_max, int32_t C) {
+  return B >= 1 && B <= 65535 && n_max >= 1 && n_max <= ((int64_t)1 << 28) && L_max >= 0 && L_max <= ((int64_t)1 << 24) && C >= 64 && C <= 2048 &&
+         !(C & (C - 1));
+}
+
+int64_t rsrgan_wave_reverb_work(int32_t B, int64_t n_max, int64_t L_max, int32_t C) {
+  return reverb_sizes_ok(B, n_max, L_max, C) ? (int64_t)reverb_work_bytes(B, (long long)n_max, (long long)L_max, C) : 0;
+}
+
+int rsrgan_wave_reverb(const void* pcm, int32_t kind, int64_t n_samples, const int64_t* seg, const float* rir, int64_t n_taps, const int64_t* rir_seg,
+                       const float* noise, int64_t n_noise, const int64_t* noise_seg, const float* noise_pow, const int32_t* sel, const float* snr,
+                       int32_t B, int32_t R, int32_t V, int32_t C, const float* twiddle, int32_t flags, float* out, int64_t out_samples,
+                       const int64_t* out_seg, float* gains, void* work, int64_t work_bytes, void* stream) {
+  OP_REFUSE(!pcm || !seg || !sel || !snr, "wave_reverb: null pointer (pcm, seg, sel or snr)");
+  OP_REFUSE(!out || !out_seg, "wave_reverb: null pointer (out or out_seg)");
+  OP_REFUSE(!twiddle || !work, "wave_reverb: null pointer (twiddle or work)");
+  OP_REFUSE(B < 1 || B > 65535, "wave_reverb: B = %d outside [1, 65535]", B);
+  OP_REFUSE(R < 0 || R > (1 << 20), "wave_reverb: R = %d outside [0, 2^20]", R);
+  OP_REFUSE(V < 0 || V > (1 << 20), "wave_reverb: V = %d outside [0, 2^20]", V);
+  OP_REFUSE(R > 0 && (!rir || !rir_seg), "wave_reverb: null pointer (rir or rir_seg) with R = %d: only R = 0 takes none", R);
+  OP_REFUSE(V > 0 && (!noise || !noise_seg || !noise_pow), "wave_reverb: null pointer (noise, noise_seg or noise_pow) with V = %d: only V = 0 takes none", V);
+  OP_REFUSE(kind != 0 && kind != 1, "wave_reverb: kind = %d is neither 0 (int16) nor 1 (float32)", kind);
+  OP_REFUSE((size_t)pcm & (kind ? 3 : 1), "wave_reverb: pcm not aligned to its %d-byte samples", kind ? 4 : 2);
+  OP_REFUSE((size_t)work & 15, "wave_reverb: work not 16-byte aligned");
+  OP_REFUSE(((size_t)seg & 7) || ((size_t)rir_seg & 7) || ((size_t)noise_seg & 7) || ((size_t)out_seg & 7),
+            "wave_reverb: seg, rir_seg, noise_seg or out_seg not 8-byte aligned");
+  OP_REFUSE(((size_t)rir & 3) || ((size_t)noise & 3) || ((size_t)noise_pow & 3), "wave_reverb: rir, noise or noise_pow not 4-byte aligned");
+  OP_REFUSE(((size_t)sel & 3) || ((size_t)snr & 3) || ((size_t)twiddle & 3), "wave_reverb: sel, snr or twiddle not 4-byte aligned");
+  OP_REFUSE(((size_t)out & 3) || ((size_t)gains & 3), "wave_reverb: out or gains not 4-byte aligned");
+  OP_REFUSE(n_samples < 1 || out_samples < 1, "wave_reverb: n_samples, out_samples must be positive (got %lld, %lld)", (long long)n_samples,
+            (long long)out_samples);
+  OP_REFUSE(n_samples > ((int64_t)1 << 40) || out_samples > ((int64_t)1 << 40), "wave_reverb: n_samples or out_samples above the entry's 2^40 (got %lld, %lld)",
+            (long long)n_samples, (long long)out_samples);
+  OP_REFUSE(n_taps < (R > 0) || n_taps > ((int64_t)1 << 40), "wave_reverb: n_taps = %lld outside [%d, 2^40] with R = %d", (long long)n_taps, R > 0, R);
+  OP_REFUSE(n_noise < (V > 0) || n_noise > ((int64_t)1 << 40), "wave_reverb: n_noise = %lld outside [%d, 2^40] with V = %d", (long long)n_noise, V > 0, V);
+  OP_REFUSE(C < 64 || C > 2048 || (C & (C - 1)), "wave_reverb: C = %d is no power of two in [64, 2048]", C);
+  OP_REFUSE(flags < 0 || flags > 3, "wave_reverb: flags = %d holds bits other than 1 (shift) and 2 (normalize)", flags);
+  const int64_t least = (int64_t)reverb_work_bytes(B, 1, 1, C);
+  OP_REFUSE(work_bytes < least, "wave_reverb: work_bytes = %lld below the %lld bytes B = %d utterances of one sample need at C = %d", (long long)work_bytes,
+            (long long)least, B, C);
+  RevArgs a{pcm, kind, (long long)n_samples, reinterpret_cast<const long long*>(seg), rir, (long long)n_taps, reinterpret_cast<const long long*>(rir_seg),
+            noise, (long long)n_noise, reinterpret_cast<const long long*>(noise_seg), noise_pow, sel, snr, B, R, V, (uint32_t)C, twiddle, flags, out,
+            (long long)out_samples, reinterpret_cast<const long long*>(out_seg), gains, static_cast<unsigned char*>(work), 0ull};
+  launch_wave_reverb(a, (size_t)work_bytes, (hipStream_t)stream);
+  OP_LAUNCHED("wave_reverb");
+}
+
 // ---- TensorBoard histograms on the device (hist.hip): no handle; two launches on the caller's stream
 int rsrgan_hist_limits(double* out, int32_t* n) {
   OP_REFUSE(!n, "hist_limits: null pointer (n)");

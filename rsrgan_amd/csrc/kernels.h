@@ -494,6 +494,18 @@ size_t mfcc_lds_bytes(int N, int S, int P, int M, int C, int nnz);
 void launch_feat_mfcc(const void* pcm, int kind, long long n_samples, const long long* seg, const int* offsets, int B, int N, int S, int P,
                       float preemph, const float* window, const float* twiddle, const int* mel_seg, const float* mel_w, int nnz, int M,
                       const float* dct, int C, float* out, long long out_rows, hipStream_t s);
+// ---- reverberation on the device (reverb.hip): the arguments of rsrgan_wave_reverb (include/rsrgan.h) as the four kernels take them; slot
+// is filled by the launch (work_bytes / B, rounded down to 16).  reverb_work_bytes: B slots for n_max samples against L_max taps.
+struct RevArgs {
+  const void* pcm; int kind; long long n_samples; const long long* seg;
+  const float* rir; long long n_taps; const long long* rir_seg;
+  const float* noise; long long n_noise; const long long* noise_seg; const float* noise_pow;
+  const int* sel; const float* snr; int B, R, V; uint32_t C; const float* twiddle; int flags;
+  float* out; long long out_samples; const long long* out_seg; float* gains;
+  unsigned char* work; unsigned long long slot;
+};
+size_t reverb_work_bytes(int B, long long n_max, long long L_max, int C);
+void launch_wave_reverb(const RevArgs& a, size_t work_bytes, hipStream_t s);
 // ---- TensorBoard histograms on the device (hist.hip): for each of n <= HIST_MAX_TENSORS strided float32 views (element (r, c) at
 // x[r * ld + c * cs]; rows * cols <= 2^31 - 1; x may be null where rows * cols == 0) one record of HIST_REC doubles in out: min, max, num,
 // sum, sum_squares and the count of each of the HIST_NL buckets of TensorFlow's default limits (hist_limits(), built once on the host).

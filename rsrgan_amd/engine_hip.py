@@ -73,6 +73,86 @@ class WaveFrontEnd(OpEntries):
                                         M, _ptr(dct), ceps, _ptr(out), out.shape[0] if out_rows is None else out_rows,
                                         self._stream() if stream is None else C.c_void_p(stream.cuda_stream)))
 
+    # -- reverberation (include/rsrgan.h rsrgan_wave_reverb, csrc/reverb.hip) -------------------------------------------------------
+    def wave_reverb_work(self, B, n_max, L_max, fft):
+        """the bytes of `work` for B utterances of at most n_max samples against at most L_max taps (rsrgan_wave_reverb_work)"""
+        need = int(self.lib.rsrgan_wave_reverb_work(B, n_max, L_max, fft))
+        if need <= 0:
+            raise ValueError("wave_reverb_work: B = %d, n_max = %d, L_max = %d, fft = %d outside the entry's limits" % (B, n_max, L_max, fft))
+        return need
+
+    def op_wave_reverb(self, pcm, seg, rir, rir_seg, noise, noise_seg, noise_pow, sel, snr, B, fft, twiddle, out, out_seg, work, gains=None,
+                       shift=True, normalize=True, kind=None, stream=None):
+        """rsrgan_wave_reverb on caller-owned device tensors: pcm int16 or float32 [n], seg [B, 2] i64; rir f32 [taps], rir_seg [R, 5] i64 =
+        (first tap, L, q, e0, e1) (both None: no RIRs); noise f32, noise_seg [V, 2] i64, noise_pow [V] f32 (all None: no noises); sel
+        [B, 4] i32 = (rir index, noise index, s, m); snr [B] f32; twiddle [fft, 2] f32 = io.wave.twiddle_table(2 * fft); out f32, out_seg
+        [B, 2] i64 = (first, capacity); work uint8 (wave_reverb_work bytes); gains [B, 2] f32 or None.  On `stream` (default: the current
+        one); nothing is allocated and nothing waits for the device."""
+        if kind is None:
+            if pcm.dtype not in (torch.int16, torch.float32):
+                raise ValueError("op_wave_reverb: pcm must be int16 or float32, got %s" % pcm.dtype)
+            kind = 0 if pcm.dtype == torch.int16 else 1
+        R = 0 if rir_seg is None else int(rir_seg.shape[0])
+        V = 0 if noise_seg is None else int(noise_seg.shape[0])
+        check(self.lib.rsrgan_wave_reverb(_ptr(pcm), kind, pcm.numel(), _ptr(seg), _ptr(rir), 0 if rir is None else rir.numel(), _ptr(rir_seg),
+                                          _ptr(noise), 0 if noise is None else noise.numel(), _ptr(noise_seg), _ptr(noise_pow), _ptr(sel),
+                                          _ptr(snr), B, R, V, fft, _ptr(twiddle), (1 if shift else 0) | (2 if normalize else 0), _ptr(out),
+                                          out.numel(), _ptr(out_seg), _ptr(gains), _ptr(work), work.numel() * work.element_size(),
+                                          self._stream() if stream is None else C.c_void_p(stream.cuda_stream)))
+
+    def reverb_bank(self, bank, us=None):
+        """the packed tables of an io.reverb.ReverbSim (or anything with its rir / rir_seg / noise / noise_seg / noise_pow members) as
+        device tensors (rir, rir_seg, noise, noise_seg, noise_pow; the noise triple None without noises): uploaded once on the upload
+        stream and kept with the bank"""
+        ent = getattr(bank, "_device_tables", None)
+        if ent is None or ent[0] != self.device:
+            us = self.upload_stream() if us is None else us
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+            with torch.cuda.stream(us):
+                tabs = (up(bank.rir), up(bank.rir_seg)) if bank.rir_seg.shape[0] else (None, None)
+                tabs += (up(bank.noise), up(bank.noise_seg), up(bank.noise_pow)) if bank.noise_seg.shape[0] else (None, None, None)
+            us.synchronize()                                          # (once per bank: later calls may come on other streams)
+            ent = bank._device_tables = (self.device, tabs)
+        return ent[1]
+
+    def _reverb_twiddle(self, fft, us):
+        from .io.wave import twiddle_table
+        cache = self.__dict__.setdefault("_reverb_tw", {})
+        if fft not in cache:
+            with torch.cuda.stream(us):
+                cache[fft] = torch.from_numpy(twiddle_table(2 * fft)).to(self.device)
+        return cache[fft]
+
+    def simulate(self, wb, plan=None, stream=None, gains=None):
+        """io.WaveBatch of clean samples + an io.reverb.ReverbPlan (default: the batch's own) -> (pcm float32 [sum n_out] on the device, its
+        segment table int64 [B, 2] on the device, the same table on the host): rsrgan_wave_reverb on `stream` (default: the upload
+        stream), the uploads queued there too.  n_out is the utterance's count with the plan's shift, count + L - 1 without.  The
+        reverberant audio never exists on the host."""
+        plan = wb.plan if plan is None else plan
+        if plan is None or len(plan) != len(wb):
+            raise ValueError("simulate: the batch of %d utterances needs a plan of as many draws" % len(wb))
+        us = self.upload_stream() if stream is None else stream
+        bank, spec = plan.bank, plan.spec
+        B, counts = len(wb), wb.seg[:, 1].astype(np.int64)
+        ri = plan.sel[:, 0].astype(np.int64)
+        taps = np.where((ri >= 0) & (ri < bank.rir_seg.shape[0]), bank.rir_seg[np.clip(ri, 0, max(bank.rir_seg.shape[0] - 1, 0)), 1], 1) \
+            if bank.rir_seg.shape[0] else np.ones(B, np.int64)
+        n_out = counts if spec.shift else np.where(counts > 0, counts + taps - 1, 0)
+        first = np.zeros(B, np.int64)
+        np.cumsum(n_out[:-1], out=first[1:])
+        out_seg = np.stack([first, n_out], 1)
+        need = self.wave_reverb_work(B, max(int(counts.max()), 1), int(taps.max()), spec.fft)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=True)
+        with torch.cuda.stream(us):
+            rir, rseg, noise, nseg, npow = self.reverb_bank(bank, us)
+            tw = self._reverb_twiddle(spec.fft, us)
+            pcm, dseg, sel, snr, oseg = up(wb.samples), up(wb.seg), up(plan.sel), up(plan.snr), up(out_seg)
+            out = torch.empty(max(int(n_out.sum()), 1), dtype=torch.float32, device=self.device)
+            work = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self.op_wave_reverb(pcm, dseg, rir, rseg, noise, nseg, npow, sel, snr, B, spec.fft, tw, out, oseg, work, gains, spec.shift,
+                                spec.normalize, stream=us)
+        return out, oseg, out_seg
+
     def _wave_tables(self, spec, us):
         """the window and the twiddles of a framing as fp32 device tensors: built on the host in float64, rounded once, uploaded at first use
         and kept per engine (as _cmvn_device keeps the statistics).  For an io.wave.MfccSpec three more follow: mel_seg, mel_w and the DCT
@@ -97,18 +177,22 @@ class WaveFrontEnd(OpEntries):
         """host samples and tables -> (raw feature rows [rows, spec.bins], the offset table) on the device: LPS for a WaveSpec
         (rsrgan_feat_wave), MFCC or log-mel for an MfccSpec (rsrgan_feat_mfcc).  The uploads and the launch are queued on `us` (the caller is
         inside `with torch.cuda.stream(us)`)"""
-        tabs = self._wave_tables(spec, us)
         pcm = torch.from_numpy(np.ascontiguousarray(samples)).to(self.device, non_blocking=True)
         dseg = torch.from_numpy(np.ascontiguousarray(seg)).to(self.device, non_blocking=True)
+        return self._wave_rows(pcm, dseg, int(seg.shape[0]), offsets, rows, spec, us)
+
+    def _wave_rows(self, pcm, dseg, B, offsets, rows, spec, us):
+        """wave_features on samples and segments that are on the device already"""
+        tabs = self._wave_tables(spec, us)
         off = torch.from_numpy(np.ascontiguousarray(offsets)).to(self.device, non_blocking=True)
         raw = torch.empty(rows, spec.bins, dtype=torch.float32, device=self.device)
         if hasattr(spec, "num_mel_bins"):
             win, tw, mseg, mw, dct = tabs
-            self.op_feat_mfcc(pcm, dseg, off, int(seg.shape[0]), win, tw, mseg, mw, dct, raw, spec.frame_length, spec.frame_shift, spec.padded,
+            self.op_feat_mfcc(pcm, dseg, off, B, win, tw, mseg, mw, dct, raw, spec.frame_length, spec.frame_shift, spec.padded,
                               spec.preemph, stream=us)
         else:
             win, tw = tabs
-            self.op_feat_wave(pcm, dseg, off, int(seg.shape[0]), win, tw, raw, spec.frame_length, spec.frame_shift, spec.padded, spec.preemph,
+            self.op_feat_wave(pcm, dseg, off, B, win, tw, raw, spec.frame_length, spec.frame_shift, spec.padded, spec.preemph,
                               stream=us)
         return raw, off
 
@@ -436,7 +520,12 @@ class HipEngine(WaveFrontEnd):      # (the handle-free rsrgan_op_* wrappers and 
         us = self.upload_stream()
         dm, ds = self._cmvn_device(mean, stddev, us) if mean is not None else (None, None)
         with torch.cuda.stream(us):
-            raw, off = self.wave_features(wb.samples, wb.seg, offsets, rows, spec, us)
+            if getattr(wb, "plan", None) is not None:
+                # clean samples with a plan: reverberated on the device first (csrc/reverb.hip), float32 on the int16 scale
+                pcm, dseg, _ = self.simulate(wb, stream=us)
+                raw, off = self._wave_rows(pcm, dseg, B, offsets, rows, spec, us)
+            else:
+                raw, off = self.wave_features(wb.samples, wb.seg, offsets, rows, spec, us)
             out = torch.empty(B, T, D * (left + 1 + right), dtype=torch.float32, device=self.device)
             ln = torch.empty(B, dtype=torch.int32, device=self.device)
             self.op_feat_batch(raw, off, B, T, D, left, right, dm, ds, out, ln, stream=us)

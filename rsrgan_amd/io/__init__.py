@@ -5,5 +5,6 @@ from .features import apply_cmvn, splice_feats, PaddedBatchReader, FrameBatchRea
 from .features import PackedBatch, pack_utterances, CodedBatch, pack_coded                # noqa: F401
 from .wave import MfccSpec, WaveBatch, WaveSpec, lps_from_wave, mfcc_from_wave, num_frames, pack_wave, read_wav, read_wav_scp        # noqa: F401
 from .wave_reader import WaveBatchReader                    # noqa: F401
+from .reverb import ReverbPlan, ReverbSim, ReverbSpec, reverberate                          # noqa: F401
 from .frame_pool import FrameDraw, PoolLedger, RowAllocator                                 # noqa: F401
 from .prefetch import prefetch                                                             # noqa: F401

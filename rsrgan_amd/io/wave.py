@@ -300,16 +300,20 @@ class WaveBatch(object):
     (HipEngine.featurize, csrc/wave.hip k_feat_wave).  `samples` int16 or float32 [n]: the utterances one after the other; `seg` int64
     [B, 2] = (first sample, sample count); `offsets` int32 [B + 1]: utterance b has offsets[b + 1] - offsets[b] = num_frames(count)
     frames; `shape` = (B, T, bins * (left + 1 + right)); `left`, `right`, `mean`, `stddev` as in PackedBatch; `spec` the framing.  The
-    constructor checks what the device cannot: every segment inside the samples and the offsets the frame counts."""
+    constructor checks what the device cannot: every segment inside the samples and the offsets the frame counts.  `plan` (an
+    io.reverb.ReverbPlan of B draws, or None): the samples are CLEAN audio, to be reverberated on the device before the frames are made
+    (HipEngine.simulate, csrc/reverb.hip); the plan's spec shifts, so the frame counts are those of the clean samples."""
 
-    def __init__(self, samples, seg, offsets, shape, left=0, right=0, mean=None, stddev=None, spec=DEFAULT):
-        self.samples, self.seg, self.offsets, self.spec = samples, seg, offsets, spec
+    def __init__(self, samples, seg, offsets, shape, left=0, right=0, mean=None, stddev=None, spec=DEFAULT, plan=None):
+        self.samples, self.seg, self.offsets, self.spec, self.plan = samples, seg, offsets, spec, plan
         self.shape = tuple(int(v) for v in shape)
         self.left, self.right, self.mean, self.stddev = int(left), int(right), mean, stddev
         B, C = self.shape[0], self.left + 1 + self.right
         if self.shape[2] != spec.bins * C:
             raise ValueError("shape[2] = %d is not bins * (left + 1 + right) = %d * %d" % (self.shape[2], spec.bins, C))
         self.dim = spec.bins
+        if plan is not None and (len(plan) != B or not plan.spec.shift):
+            raise ValueError("the plan holds %d draws for %d utterances, or does not shift (the frame counts would differ)" % (len(plan), B))
         if samples.ndim != 1 or samples.dtype not in (np.int16, np.float32):
             raise ValueError("samples must be a flat int16 or float32 array, got %s %s" % (samples.dtype, samples.shape))
         if offsets.shape != (B + 1,) or offsets.dtype != np.int32:
@@ -339,7 +343,7 @@ class WaveBatch(object):
 
     def nbytes(self):
         """what travels to the device: the samples and the two tables"""
-        return int(self.samples.nbytes + self.seg.nbytes + self.offsets.nbytes)
+        return int(self.samples.nbytes + self.seg.nbytes + self.offsets.nbytes) + (self.plan.nbytes() if self.plan is not None else 0)
 
     def rows(self, lo, hi):
         """utterances [lo, hi) as a batch of their own (GAN_RNN._shard): only their samples, both tables rebased to 0, the same T"""
@@ -347,12 +351,13 @@ class WaveBatch(object):
         if not 0 <= lo <= hi <= self.shape[0]:
             raise ValueError("rows [%d, %d) outside the batch of %d" % (lo, hi, self.shape[0]))
         utts = [self.samples[int(a):int(a) + int(n)] for a, n in self.seg[lo:hi]]
-        return pack_wave(utts, self.shape[1], self.left, self.right, self.mean, self.stddev, self.spec) if utts else \
+        plan = self.plan.rows(lo, hi) if self.plan is not None else None
+        return pack_wave(utts, self.shape[1], self.left, self.right, self.mean, self.stddev, self.spec, plan=plan) if utts else \
             WaveBatch(self.samples[:0], self.seg[:0], np.zeros(1, np.int32), (0,) + self.shape[1:], self.left, self.right, self.mean,
-                      self.stddev, self.spec)
+                      self.stddev, self.spec, plan)
 
 
-def pack_wave(utts, T=None, left=0, right=0, mean=None, stddev=None, spec=DEFAULT, names=None):
+def pack_wave(utts, T=None, left=0, right=0, mean=None, stddev=None, spec=DEFAULT, names=None, plan=None):
     """sample arrays [n_i] (int16, or floats on the int16 scale) -> WaveBatch padded to T frames (default: the longest).  The samples are
     copied once, int16 if every utterance is, float32 otherwise; nothing is computed."""
     pcm = [as_pcm(u, "utterance %s" % (names[i] if names is not None else i)) for i, u in enumerate(utts)]
@@ -369,4 +374,4 @@ def pack_wave(utts, T=None, left=0, right=0, mean=None, stddev=None, spec=DEFAUL
         raise ValueError("a batch of %d frames does not fit the int32 offset table" % offsets[-1])
     samples = np.concatenate([u.astype(dtype, copy=False) for u in pcm], 0)
     return WaveBatch(samples, np.stack([first, counts], 1), offsets.astype(np.int32),
-                     (len(pcm), max(frames) if T is None else int(T), spec.bins * (left + 1 + right)), left, right, mean, stddev, spec)
+                     (len(pcm), max(frames) if T is None else int(T), spec.bins * (left + 1 + right)), left, right, mean, stddev, spec, plan)

@@ -25,12 +25,29 @@ class WaveBatchReader(object):
     device_features=True: the samples travel; the items are [utt_ids, WaveBatch(inputs), WaveBatch(labels), lengths] and the device makes
     the frames (csrc/wave.hip k_feat_wave / k_feat_mfcc), normalises, splices and pads them (HipEngine.featurize).
 
+    simulate=io.reverb.ReverbSim(rir_scp, noise_scp, spec, seed) with inputs_wav_scp=None: there is no second corpus; the inputs are the
+    LABELS' audio reverberated with the RIR (and noise) drawn for (seed, epoch, utterance index) -- set_epoch selects the epoch, the draw
+    of an utterance depends on nothing else, so materialize may run on several threads in any order.  The spec must shift, so that the
+    reverberant utterance is as long as the clean one and the frame counts agree.  Host route: io.reverb.reverberate (float64), then
+    lps_from_wave.  device_features=True: the items are [utt_ids, WaveBatch(CLEAN samples + the batch's ReverbPlan), WaveBatch(labels),
+    lengths] and the device reverberates (csrc/reverb.hip) before it makes the frames.  Without `simulate` nothing changes.
+
     ValueError at construction, naming the utterance: a pair whose two files make different frame counts, an utterance that makes no
     frame, ids that differ between the two files."""
 
     def __init__(self, inputs_wav_scp, labels_wav_scp, batch_size, left_context=0, right_context=0, cmvn=None, num_buckets=20, shuffle=True,
-                 seed=None, device_features=False, input_spec=DEFAULT, label_spec=MFCC_DEFAULT):
+                 seed=None, device_features=False, input_spec=DEFAULT, label_spec=MFCC_DEFAULT, simulate=None):
         self.device_features = bool(device_features)
+        self.simulate = simulate
+        if (simulate is None) == (inputs_wav_scp is None):
+            raise ValueError("the inputs come from inputs_wav_scp or from simulate=ReverbSim(...) on the labels' audio: give exactly one")
+        if simulate is not None:
+            if not simulate.spec.shift:
+                raise ValueError("simulate: the ReverbSpec must shift (shift=True), so that the frame counts of inputs and labels agree")
+            if simulate.spec.sample_rate != input_spec.sample_rate or input_spec.sample_rate != label_spec.sample_rate:
+                raise ValueError("simulate: the sample rates of the ReverbSpec (%d), the inputs (%d) and the labels (%d) differ" % (
+                    simulate.spec.sample_rate, input_spec.sample_rate, label_spec.sample_rate))
+            inputs_wav_scp = labels_wav_scp
         self.input_spec, self.label_spec = input_spec, label_spec
         self._stats = None
         if self.device_features and cmvn is not None:
@@ -63,7 +80,16 @@ class WaveBatchReader(object):
         for indices in self.plan():
             yield self.materialize(indices)
 
+    def set_epoch(self, epoch):
+        """simulate: the epoch of the draws from here on (cross-validation never calls it: epoch 0 every time)"""
+        if self.simulate is not None:
+            self.simulate.set_epoch(epoch)
+
     def _samples(self, i):
+        if self.simulate is not None:
+            # host route: the labels' audio through the RIR and noise drawn for (seed, epoch, i); float64, not quantised
+            sy = read_wav(self.labels[i][1], sample_rate=self.label_spec.sample_rate)
+            return self.simulate.apply(sy, self.simulate.draw(i, sy.shape[0])), sy
         return (read_wav(self.inputs[i][1], sample_rate=self.input_spec.sample_rate),
                 read_wav(self.labels[i][1], sample_rate=self.label_spec.sample_rate))
 
@@ -77,9 +103,14 @@ class WaveBatchReader(object):
 
     def _waves(self, indices):
         ids = [self.utt_ids[i] for i in indices]
-        pairs = [self._samples(i) for i in indices]
         mi, si, ml, sl = self._stats if self._stats is not None else (None,) * 4
-        X = pack_wave([p[0] for p in pairs], None, self.left, self.right, mi, si, self.input_spec, names=ids)
+        if self.simulate is not None:
+            clean = [read_wav(self.labels[i][1], sample_rate=self.label_spec.sample_rate) for i in indices]
+            pairs = [(c, c) for c in clean]
+            plan = self.simulate.plan(indices, [c.shape[0] for c in clean])
+        else:
+            pairs, plan = [self._samples(i) for i in indices], None
+        X = pack_wave([p[0] for p in pairs], None, self.left, self.right, mi, si, self.input_spec, names=ids, plan=plan)
         Y = pack_wave([p[1] for p in pairs], None, 0, 0, ml, sl, self.label_spec, names=ids)
         return [ids, X, Y, X.lengths()]
 

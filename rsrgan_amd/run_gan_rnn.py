@@ -86,6 +86,8 @@ def build_parser():
                        "of the split's *_scp archive; inputs become 257-bin log-power-spectrum frames, labels 40-dim MFCC frames "
                        "(io/wave.py MfccSpec: compute-mfcc-feats with mfcc_hires.conf), on the host, or with --device_features on the "
                        "device (csrc/wave.hip); given in pairs")
+    from .io.reverb import add_sim_flags
+    add_sim_flags(p)
     return p
 
 
@@ -137,17 +139,29 @@ def _cmvn(FLAGS):
 
 def check_wav_flags(FLAGS):
     """the *_wav_scp flags come in pairs, replace the split's archive flags and do not go with --device_decode; the two dims are the
-    specs' bins.  SystemExit with a message otherwise."""
+    specs' bins.  --{tr,cv}_rir_scp takes the place of the split's --*_inputs_wav_scp (the inputs are simulated from the labels' audio);
+    --noise_scp goes with it only.  SystemExit with a message otherwise."""
     from .io import wave as W
-    any_wav = False
+    any_wav = any_rir = False
     for split in ("tr", "cv"):
         a, b = (getattr(FLAGS, "%s_%s_wav_scp" % (split, k), None) for k in ("inputs", "labels"))
+        rir = getattr(FLAGS, split + "_rir_scp", None)
+        if rir and a:
+            raise SystemExit("--%s_rir_scp simulates the inputs from the labels' audio in place of --%s_inputs_wav_scp: give one of them" % (split, split))
+        if rir and not b:
+            raise SystemExit("--%s_rir_scp needs --%s_labels_wav_scp: the clean audio it reverberates" % (split, split))
+        any_rir = any_rir or bool(rir)
+        a = a or rir
         if bool(a) != bool(b):
             raise SystemExit("--%s_inputs_wav_scp and --%s_labels_wav_scp are given together or not at all" % (split, split))
         if a and (getattr(FLAGS, split + "_inputs_scp", None) or getattr(FLAGS, split + "_labels_scp", None)):
             raise SystemExit("--%s_*_wav_scp reads audio in place of --%s_inputs_scp / --%s_labels_scp: give one kind per split" % (
                 split, split, split))
         any_wav = any_wav or bool(a)
+    if getattr(FLAGS, "noise_scp", None) and not any_rir:
+        raise SystemExit("--noise_scp adds noise to simulated inputs: it goes with --tr_rir_scp / --cv_rir_scp")
+    if any_rir and not float(getattr(FLAGS, "snr_lower", 5.0)) <= float(getattr(FLAGS, "snr_upper", 20.0)):
+        raise SystemExit("--snr_lower %g is above --snr_upper %g" % (FLAGS.snr_lower, FLAGS.snr_upper))
     if any_wav and _device_decode(FLAGS):
         raise SystemExit("--*_wav_scp reads audio, --device_decode decodes archives: use --device_features for the device route")
     if any_wav and (int(FLAGS.input_dim) != W.DEFAULT.bins or int(FLAGS.output_dim) != W.MFCC_DEFAULT.bins):
@@ -157,12 +171,14 @@ def check_wav_flags(FLAGS):
 
 def split_reader(FLAGS, split, cmvn, shuffle, seed):
     """the reader of a split ("tr" / "cv"): over its two wav.scp files if they are given, over its two archives otherwise"""
-    wav = getattr(FLAGS, split + "_inputs_wav_scp", None)
-    if wav:
+    wav, rir = getattr(FLAGS, split + "_inputs_wav_scp", None), getattr(FLAGS, split + "_rir_scp", None)
+    if wav or rir:
+        from .io.reverb import sim_from_flags
         from .io.wave_reader import WaveBatchReader
         try:
-            return WaveBatchReader(wav, getattr(FLAGS, split + "_labels_wav_scp"), FLAGS.batch_size * FLAGS.num_gpu, FLAGS.left_context,
-                                   FLAGS.right_context, cmvn=cmvn, shuffle=shuffle, seed=seed, device_features=_device_features(FLAGS))
+            return WaveBatchReader(wav or None, getattr(FLAGS, split + "_labels_wav_scp"), FLAGS.batch_size * FLAGS.num_gpu, FLAGS.left_context,
+                                   FLAGS.right_context, cmvn=cmvn, shuffle=shuffle, seed=seed, device_features=_device_features(FLAGS),
+                                   simulate=sim_from_flags(FLAGS, split) if rir else None)
         except (OSError, EOFError, ValueError) as e:
             raise SystemExit("--%s_*_wav_scp: %s" % (split, e))
     return _reader(FLAGS, getattr(FLAGS, split + "_inputs_scp"), getattr(FLAGS, split + "_labels_scp"), cmvn, shuffle, seed)
@@ -210,6 +226,8 @@ def train(FLAGS, model_factory=None, log=print, net_overrides=None):
     for iteration in range(max_iters):
         start = datetime.datetime.now()
         # reader thread + Queue(32) as :463-478: reading, CMVN, splicing and padding overlap the GPU steps
+        if hasattr(tr_reader, "set_epoch"):
+            tr_reader.set_epoch(iteration)                # (--tr_rir_scp: other rooms every epoch; cross-validation keeps epoch 0's)
         tr = train_one_iteration(None, tr_model, train_batch_per_iter * FLAGS.num_gpu, iteration + 1, prefetch(tr_reader), FLAGS.num_gpu)
         if hasattr(tr_model, "sync_batch_norm_state"):
             tr_model.sync_batch_norm_state()           # one copy of the batch-norm statistics over the ranks, before cross-validation and the checkpoint

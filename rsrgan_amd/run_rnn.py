@@ -68,6 +68,8 @@ def build_parser():
     for n in ("tr_inputs_wav_scp", "tr_labels_wav_scp", "cv_inputs_wav_scp", "cv_labels_wav_scp"):
         p.add_argument("--" + n, type=str, default=None, help="train from audio: a wav.scp in place of the split's *_scp archive "
                        "(run_gan_rnn --%s)" % n)
+    from .io.reverb import add_sim_flags
+    add_sim_flags(p)
     return p
 
 
@@ -142,6 +144,8 @@ def train(FLAGS, model_factory=None, log=print, net_overrides=None):
     iteration = -1
     for iteration in range(max_iters):
         start = datetime.datetime.now()
+        if hasattr(tr_reader, "set_epoch"):
+            tr_reader.set_epoch(iteration)                # (--tr_rir_scp: other rooms every epoch; cross-validation keeps epoch 0's)
         tr = train_one_iteration(tr_model, train_batch_per_iter * FLAGS.num_gpu, iteration + 1, prefetch(tr_reader), FLAGS.num_gpu)
         if hasattr(tr_model, "sync_batch_norm_state"):
             tr_model.sync_batch_norm_state()           # one copy of the batch-norm statistics over the ranks, before cross-validation and the checkpoint
