@@ -802,6 +802,38 @@ int rsrgan_op_step_elem(int32_t op, const void* const* ptrs, const int64_t* dims
  * op 17 launch_pad_copy:       ptrs dense, padded;  dims rows, cols, ld, to_padded
  * op 18 launch_copy_f:         ptrs src, dst;  dims n */
 int rsrgan_op_layout(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream);
+/* the launch-per-phase LSTM step kernels (csrc/kernels.hip k_fwd_gates, k_fwd_proj, k_bwd_a2, k_bwd_b, k_bwd_bp + k_bwd_b_red) through
+ * their five launchers, without a handle (tests/test_gpu_lstm_step_ops.py, tests/test_lstm_step_op_args.py; DESIGN.md "The step-kernel
+ * entry").  A call describes n jobs of ONE launch: dims[0] = n (1 .. 8, csrc/kernels.h MAXJ), then one record per job; ptrs holds one group
+ * per job, in the order below; an argument is named "<name> of job <j>".  A pointer marked ? may be NULL and selects the optional form
+ * exactly as the job structs of csrc/kernels.h document it.  The entry fills the job struct field by field, computes nblk_c and kb_max as
+ * csrc/model.cpp does, and calls the launcher; the fragment-tiled (Wsw, WpT_sw, Wp_sw, Ksw) and transposed (WpT) weight images are the
+ * caller's (rsrgan_op_layout ops 7 and 5, with the SwizzleJob rows of Model::refresh_swizzles).  RSRGAN_ERR_INVALID before the first HIP
+ * call, rsrgan_last_error() naming the argument, for: a null table or required pointer; n outside 1 .. 8; a size below 1 (t, I, n_begin
+ * below 0); a leading dimension below its row; a pointer the kernels move float4 through that is not 16-byte aligned; and the kernels' limits:
+ * op 0: ldx, ldm multiples of 4, ldx + ldm <= 1024 (ldm alone with zx), exactly one of x and zx, bias with x, ldm >= H and np_res_in
+ *       with np_res_out where np_m_out is given, no np_* pointer without np_m_out;
+ * op 1: ldh a multiple of 4, m_prev with len, res_in with res_out, without len N <= P x ldh (the kernel reads its stand-in for len from
+ *       WpT), with drop_ctr 0 < keep <= 1 and thr in 0 .. 2^24;
+ * op 2: ldm a multiple of 4, Wp and Wp_sw both or neither, with them ldm <= 384 and dmt, without them P == H; drop as op 1;
+ * ops 3, 4: H4 a multiple of 4 (dz rows and the row-major K move as float4), n_end above n_begin, K or Ksw, dx where n_begin < I, dmst
+ *       where n_end > I, dx_accumulate 0 or 1; op 4: ws below bwd_b_plan's need, and (kpg + 1) / 2 > 12 for any job (the register slice
+ *       of k_bwd_bp, what Model::bwd_b_splitk_ok refuses for the kernel's sake).
+ * op 0 launch_fwd_gates:  ptrs x?, KxT? (unread), m, KhT? (unread), Wsw, zx?, bias?, wf, wi, wo, c_prev, c_out, gates, h, len (int32),
+ *                         np_m_out?, np_out?, np_res_in?, np_res_out?;  dims N, H, ldx, ldm, ldh, t;  fl forget_bias
+ * op 1 launch_fwd_proj:   ptrs h, WpT, WpT_sw?, m_prev?, m_out, out, res_in?, res_out?, len?, bias?, noise?, drop_ctr? (uint64);
+ *                         dims N, P, ldh, ldm, ldo, t, drop seed, drop tag, drop thr;  fl keep of job 0, of job 1, ... (read with drop_ctr)
+ * op 2 launch_bwd_a:      ptrs dout?, dmst, Wp?, Wp_sw?, dmt (? without a projection), gates, c_prev, c_cur, wf, wi, wo, dc, len, drop_ctr?;
+ *                         dims N, P, H, ldm, t, drop seed, drop tag, drop thr;  fl keep per job
+ * op 3 launch_bwd_b:      ptrs dz, K?, Ksw?, dx?, dmst?, len?;  dims N, I, n_begin, n_end, lddx, ldm, t, H4, dx_accumulate
+ * op 4 bwd_b_plan + launch_bwd_b_splitk:  as op 3, then ptrs[6 n] = ws and dims[1 + 9 n] = the floats of ws */
+int rsrgan_op_lstm_step(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream);
+/* what the calling thread's last step launch chose (host stores only): out[0] form -- 1 k_fwd_gates<18,1> (16-row blocks), 2 <18,2>,
+ * 3 <32,2>; 4 k_fwd_proj<4>, 5 <8>, 6 <4,drop>, 7 <8,drop>; 8 k_bwd_a2<4>, 9 <18>, 10 <24>, 11 .. 13 the same with dropout; 14 k_bwd_b
+ * <8,8,8,1> (16-row tiles), 15 the pipelined <8,0,6>; 16 split-K -- out[1] threads per block, out[2] grid, out[3] 1 where the job map was
+ * filled (grid <= 768), out[4], out[5] KG and kpg of job 0 (split-K), out[6] the grid of k_bwd_b_red, out[7] dynamic LDS bytes, out[8] jobs
+ * that own a group of XCD slots, out[9] 1 where job 0 of a split-K launch reads the fragment-tiled K; the rest 0 */
+int rsrgan_op_lstm_step_last_plan(int32_t out[16]);
 
 /* ---- SEGAN-style conv G/D (models/segan.py:SEGAN with generator.py:AEGenerator, discriminator.py:discriminator, utils/bnorm.py:VBN;
  * BASELINE.json configs[4]).  The reference's trainer cannot run as shipped (segan.py:136 calls an undefined variables_on_gpu0(),

@@ -35,7 +35,7 @@ SYMBOLS = ["rsrgan_default_cfg", "rsrgan_create", "rsrgan_destroy", "rsrgan_last
            "rsrgan_hist", "rsrgan_hist_limits", "rsrgan_d_logits", "rsrgan_d_logits_hist",
            "rsrgan_op_segan_sizes", "rsrgan_op_segan_conv2", "rsrgan_op_segan_conv1", "rsrgan_op_segan_colred", "rsrgan_op_segan_last_plan",
            "rsrgan_op_segan_vbn", "rsrgan_op_segan_elem", "rsrgan_op_segan_dhead",
-           "rsrgan_op_chunks", "rsrgan_op_update", "rsrgan_op_step_elem", "rsrgan_op_layout",
+           "rsrgan_op_chunks", "rsrgan_op_update", "rsrgan_op_step_elem", "rsrgan_op_layout", "rsrgan_op_lstm_step", "rsrgan_op_lstm_step_last_plan",
            "rsrgan_segan_default_cfg", "rsrgan_segan_create", "rsrgan_segan_destroy", "rsrgan_segan_set_scalar",
            "rsrgan_segan_num_tensors", "rsrgan_segan_tensor_info", "rsrgan_segan_param_count", "rsrgan_segan_get_params",
            "rsrgan_segan_set_params", "rsrgan_segan_forward_g", "rsrgan_segan_d_backward", "rsrgan_segan_g_backward",
@@ -151,9 +151,10 @@ def load():
     lib.rsrgan_op_bn_last_plan.argtypes = [C.POINTER(i32)]
     lib.rsrgan_op_segan_sizes.argtypes = [i32, C.POINTER(i64), C.POINTER(i64)]
     for f in (lib.rsrgan_op_segan_conv2, lib.rsrgan_op_segan_conv1, lib.rsrgan_op_segan_colred, lib.rsrgan_op_segan_vbn, lib.rsrgan_op_segan_elem,
-              lib.rsrgan_op_segan_dhead, lib.rsrgan_op_update, lib.rsrgan_op_step_elem, lib.rsrgan_op_layout):
+              lib.rsrgan_op_segan_dhead, lib.rsrgan_op_update, lib.rsrgan_op_step_elem, lib.rsrgan_op_layout, lib.rsrgan_op_lstm_step):
         f.argtypes = [i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_float), vp]
     lib.rsrgan_op_segan_last_plan.argtypes = [C.POINTER(i32)]
+    lib.rsrgan_op_lstm_step_last_plan.argtypes = [C.POINTER(i32)]
     lib.rsrgan_op_chunks.argtypes = [C.POINTER(i64), i32, C.POINTER(i32), i64, C.POINTER(i32)]
     lib.rsrgan_segan_default_cfg.argtypes = [C.POINTER(SeganCfg)]
     lib.rsrgan_segan_create.argtypes = [C.POINTER(SeganCfg), C.c_uint64, C.POINTER(vp)]
@@ -202,6 +203,12 @@ STEP_ELEM_OPS = ("lsgan", "dhead", "mse", "g_total", "l2_total", "adam_tick", "d
 # rsrgan_op_layout: the op codes (one per launch_* function of the layout, staging and weight-copy kernels)
 LAYOUT_OPS = ("pack_tm", "unpack_bm", "stage_inputs", "build_d_input", "add_noise_rows", "transpose", "transpose_many", "swizzle_many", "im2col",
               "col2im", "expand_c4", "gstate", "window_len", "zero_many", "fill", "build_joint", "slice_cols", "pad_copy", "copy_f")
+# rsrgan_op_lstm_step: the op codes (one per step launcher), the forms of rsrgan_op_lstm_step_last_plan and the fields of its record
+LSTM_STEP_OPS = ("fwd_gates", "fwd_proj", "bwd_a", "bwd_b", "bwd_b_splitk")
+LSTM_STEP_FORMS = {0: "none", 1: "gates<18,1>", 2: "gates<18,2>", 3: "gates<32,2>", 4: "proj<4>", 5: "proj<8>", 6: "proj<4,drop>", 7: "proj<8,drop>",
+                   8: "bwd_a<4>", 9: "bwd_a<18>", 10: "bwd_a<24>", 11: "bwd_a<4,drop>", 12: "bwd_a<18,drop>", 13: "bwd_a<24,drop>",
+                   14: "bwd_b<8,8,8,1>", 15: "bwd_b<8,0,6>", 16: "splitk"}
+LSTM_STEP_PLAN_FIELDS = ("form", "threads", "grid", "map_valid", "KG", "kpg", "grid2", "lds", "groups", "tiled")
 DYN_SLOTS = {"g_lr": 0, "d_lr": 1, "lambda": 2, "d_real": 3, "d_fake": 4, "l2": 5, "clip": 6, "beta1": 7, "beta2": 8, "eps": 9, "ema": 10,
              "adam_lrt": 11, "adam_lrt_d": 12}
 DYN_COUNT = 16

@@ -1154,4 +1154,192 @@ int rsrgan_op_layout(int32_t op, const void* const* ptrs, const int64_t* dims, c
 #undef WHO
 #undef OP_JOB_NAME
 
+// ---- unit-test entry of the launch-per-phase LSTM step kernels (kernels.hip k_fwd_gates, k_fwd_proj, k_bwd_a2, k_bwd_b, k_bwd_bp +
+// k_bwd_b_red) through their five launchers, on caller-owned buffers and without a handle (tests/test_gpu_lstm_step_ops.py,
+// test_lstm_step_op_args.py).  dims[0] = n jobs (1 .. MAXJ), then one fixed-length record per job; ptrs one fixed-length group per job; a
+// NULL pointer selects the optional forms as kernels.h documents them.  The job structs are filled field by field, nblk_c and kb_max with
+// model.cpp's expressions (fill_gate .. fill_bwd_b, kb16), and the unchanged launch_* function runs.  The refusals include the kernels' own
+// limits (their register weight slices, their float4 moves, the stand-in reads of their optional operands).
+#define SJ(name) (snprintf(nbuf, sizeof(nbuf), "%s of job %d", name, j), nbuf)
+static inline int op_kb16(int64_t ld) { return (int)((ld + 15) >> 4); }
+#define WHO "op_lstm_step"
+int rsrgan_op_lstm_step(int32_t op, const void* const* ptrs, const int64_t* dims, const float* fl, void* stream) {
+  OP_REFUSE(!ptrs || !dims, WHO ": null table (ptrs or dims)");
+  OP_REFUSE(op < 0 || op > 4, WHO ": op = %d outside 0 .. 4", op);
+  OP_REFUSE(op == 0 && !fl, WHO ": null table (fl: forget_bias)");
+  OP_REFUSE(dims[0] < 1 || dims[0] > MAXJ, WHO ": n = %lld jobs outside 1 .. %d", (long long)dims[0], MAXJ);
+  const int n = (int)dims[0];
+  const int64_t lim = (int64_t)1 << 30;
+  hipStream_t s = (hipStream_t)stream;
+  char nbuf[64];
+  switch (op) {
+    case 0: {      // fwd_gates: ptrs x?, KxT?, m, KhT?, Wsw, zx?, bias?, wf, wi, wo, c_prev, c_out, gates, h, len, np_m_out?, np_out?, np_res_in?, np_res_out?
+      FwdGateJobs jobs{};                                //            dims N, H, ldx, ldm, ldh, t;  fl forget_bias
+      jobs.n = n; jobs.forget_bias = fl[0];
+      int kb_max = 0, blocks = 0;
+      for (int j = 0; j < n; ++j) {
+        const void* const* p = ptrs + 19 * j;
+        const int64_t* q = dims + 1 + 6 * j;
+        const int64_t N = q[0], H = q[1], ldx = q[2], ldm = q[3], ldh = q[4], t = q[5];
+        OP_DIM(SJ("N"), N, 1); OP_DIM(SJ("H"), H, 1); OP_DIM(SJ("t"), t, 0);
+        OP_REFUSE(!p[0] && !p[5], WHO ": null pointer (%s): one of x and zx holds the x-part", SJ("x and zx"));
+        OP_REFUSE(p[0] && p[5], WHO ": %s both given: zx holds the x-part, or x is multiplied", SJ("x and zx"));
+        if (p[0]) { OP_LD(SJ("ldx"), ldx, 4); OP_MUL4(SJ("ldx"), ldx); OP_PTR(SJ("x"), p[0], 16); OP_PTR(SJ("bias"), p[6], 4); }
+        else OP_PTR(SJ("zx"), p[5], 4);
+        OP_LD(SJ("ldm"), ldm, 4); OP_MUL4(SJ("ldm"), ldm); OP_LD(SJ("ldh"), ldh, H);
+        const int64_t ktot = (p[0] ? ldx : 0) + ldm;
+        OP_REFUSE(ktot > 1024, WHO ": %s = %lld above 1024: a wave of k_fwd_gates holds at most 32 k-blocks of weights", SJ("ldx + ldm"), (long long)ktot);
+        OP_REFUSE(N * std::max(std::max(p[0] ? ldx : 0, ldm), std::max(ldh, 4 * H)) > lim, WHO ": %s above the entry's 2^30", SJ("N x ld"));
+        OP_OPT(SJ("KxT"), p[1], 4); OP_PTR(SJ("m"), p[2], 16); OP_OPT(SJ("KhT"), p[3], 4); OP_PTR(SJ("Wsw"), p[4], 16);
+        OP_OPT(SJ("bias"), p[6], 4); OP_PTR(SJ("wf"), p[7], 4); OP_PTR(SJ("wi"), p[8], 4); OP_PTR(SJ("wo"), p[9], 4);
+        OP_PTR(SJ("c_prev"), p[10], 4); OP_PTR(SJ("c_out"), p[11], 4); OP_PTR(SJ("gates"), p[12], 4); OP_PTR(SJ("h"), p[13], 4);
+        OP_PTR(SJ("len"), p[14], 4);
+        OP_OPT(SJ("np_m_out"), p[15], 4); OP_OPT(SJ("np_out"), p[16], 4); OP_OPT(SJ("np_res_in"), p[17], 4); OP_OPT(SJ("np_res_out"), p[18], 4);
+        if (p[15]) {
+          OP_REFUSE(ldm < H, WHO ": leading dimension %s = %lld below its row of %lld (m = h without a projection)", SJ("ldm"), (long long)ldm, (long long)H);
+          OP_REFUSE(p[18] && !p[17], WHO ": null pointer (%s): np_res_out = h + np_res_in", SJ("np_res_in"));
+        } else OP_REFUSE(p[16] || p[17] || p[18], WHO ": %s given without np_m_out", SJ("np_out, np_res_in or np_res_out"));
+        FwdGateJob& a = jobs.j[j];
+        a.x = (const float*)p[0]; a.KxT = (const float*)p[1]; a.m = (const float*)p[2]; a.KhT = (const float*)p[3]; a.Wsw = (const float*)p[4];
+        a.zx = (const float*)p[5]; a.bias = (const float*)p[6]; a.wf = (const float*)p[7]; a.wi = (const float*)p[8]; a.wo = (const float*)p[9];
+        a.c_prev = (const float*)p[10]; a.c_out = (float*)p[11]; a.gates = (float*)p[12]; a.h = (float*)p[13]; a.len = (const int*)p[14];
+        a.np_m_out = (float*)p[15]; a.np_out = (float*)p[16]; a.np_res_in = (const float*)p[17]; a.np_res_out = (float*)p[18];
+        a.ldx = p[0] ? (int)ldx : 0; a.ldm = (int)ldm; a.ldh = (int)ldh; a.t = (int)t; a.N = (int)N; a.H = (int)H;
+        a.nblk_c = (int)((H + 15) / 16);
+        kb_max = std::max(kb_max, (p[0] ? op_kb16(ldx) : 0) + op_kb16(ldm));
+        blocks += job_blocks(a.nblk_c, a.N, fwd_gates_rows());
+      }
+      launch_fwd_gates(jobs, blocks, kb_max, s);
+      break;
+    }
+    case 1: {      // fwd_proj: ptrs h, WpT, WpT_sw?, m_prev?, m_out, out, res_in?, res_out?, len?, bias?, noise?, drop_ctr?
+      FwdProjJobs jobs{};                                //           dims N, P, ldh, ldm, ldo, t, drop seed, tag, thr;  fl keep per job
+      jobs.n = n;
+      int kb_max = 0, blocks = 0;
+      for (int j = 0; j < n; ++j) {
+        const void* const* p = ptrs + 12 * j;
+        const int64_t* q = dims + 1 + 9 * j;
+        const int64_t N = q[0], P = q[1], ldh = q[2], ldm = q[3], ldo = q[4], t = q[5];
+        OP_DIM(SJ("N"), N, 1); OP_DIM(SJ("P"), P, 1); OP_DIM(SJ("t"), t, 0);
+        OP_LD(SJ("ldh"), ldh, 4); OP_MUL4(SJ("ldh"), ldh); OP_LD(SJ("ldm"), ldm, P); OP_LD(SJ("ldo"), ldo, P);
+        OP_REFUSE(N * std::max(ldh, std::max(ldm, ldo)) > lim || P * ldh > lim, WHO ": %s above the entry's 2^30", SJ("N x ld or P x ldh"));
+        OP_PTR(SJ("h"), p[0], 16); OP_PTR(SJ("WpT"), p[1], 16); OP_OPT(SJ("WpT_sw"), p[2], 16); OP_OPT(SJ("m_prev"), p[3], 4);
+        OP_PTR(SJ("m_out"), p[4], 4); OP_PTR(SJ("out"), p[5], 4); OP_OPT(SJ("res_in"), p[6], 4); OP_OPT(SJ("res_out"), p[7], 4);
+        OP_OPT(SJ("len"), p[8], 4); OP_OPT(SJ("bias"), p[9], 4); OP_OPT(SJ("noise"), p[10], 4); OP_OPT(SJ("drop_ctr"), p[11], 8);
+        OP_REFUSE(p[8] && !p[3], WHO ": null pointer (%s): masked rows keep m_prev", SJ("m_prev"));
+        OP_REFUSE(p[7] && !p[6], WHO ": null pointer (%s): res_out = out + res_in", SJ("res_in"));
+        OP_REFUSE(!p[8] && N > P * ldh, WHO ": %s = %lld above P x ldh = %lld without len: k_fwd_proj reads the stand-in of len from WpT", SJ("N"),
+                  (long long)N, (long long)(P * ldh));
+        FwdProjJob& a = jobs.j[j];
+        if (p[11]) {
+          OP_REFUSE(!fl, WHO ": null table (fl: keep of a job with drop_ctr)");
+          OP_REFUSE(!(fl[j] > 0.f && fl[j] <= 1.f), WHO ": %s = %g outside (0, 1]", SJ("keep"), (double)fl[j]);
+          OP_REFUSE(q[8] < 0 || q[8] > (1 << 24), WHO ": %s = %lld outside 0 .. 2^24", SJ("thr"), (long long)q[8]);
+          a.drop = DropSpec{(const unsigned long long*)p[11], (unsigned long long)q[6], (unsigned long long)q[7], (unsigned)q[8], fl[j]};
+        }
+        a.h = (const float*)p[0]; a.WpT = (const float*)p[1]; a.WpT_sw = (const float*)p[2]; a.m_prev = (const float*)p[3]; a.m_out = (float*)p[4];
+        a.out = (float*)p[5]; a.res_in = (const float*)p[6]; a.res_out = (float*)p[7]; a.len = (const int*)p[8]; a.bias = (const float*)p[9];
+        a.noise = (const float*)p[10];
+        a.ldh = (int)ldh; a.ldm = (int)ldm; a.ldo = (int)ldo; a.P = (int)P; a.t = (int)t; a.N = (int)N;
+        a.nblk_c = (int)((P + 15) / 16);
+        kb_max = std::max(kb_max, op_kb16(ldh));
+        blocks += job_blocks(a.nblk_c, a.N);
+      }
+      launch_fwd_proj(jobs, blocks, kb_max, s);
+      break;
+    }
+    case 2: {      // bwd_a: ptrs dout?, dmst, Wp?, Wp_sw?, dmt (NULL without a projection), gates, c_prev, c_cur, wf, wi, wo, dc, len, drop_ctr?
+      BwdAJobs jobs{};                                   //        dims N, P, H, ldm, t, drop seed, tag, thr;  fl keep per job
+      jobs.n = n;
+      int kb_max = 0, blocks = 0;
+      for (int j = 0; j < n; ++j) {
+        const void* const* p = ptrs + 14 * j;
+        const int64_t* q = dims + 1 + 8 * j;
+        const int64_t N = q[0], P = q[1], H = q[2], ldm = q[3], t = q[4];
+        OP_DIM(SJ("N"), N, 1); OP_DIM(SJ("P"), P, 1); OP_DIM(SJ("H"), H, 1); OP_DIM(SJ("t"), t, 0);
+        OP_LD(SJ("ldm"), ldm, P); OP_MUL4(SJ("ldm"), ldm);
+        OP_REFUSE(N * std::max(ldm, 4 * H) > lim, WHO ": %s above the entry's 2^30", SJ("N x ldm or N x 4H"));
+        OP_REFUSE(!p[2] != !p[3], WHO ": null pointer (%s): a projected job needs both, num_proj=None neither", SJ(p[2] ? "Wp_sw" : "Wp"));
+        if (p[2]) {
+          OP_REFUSE(ldm > 384, WHO ": %s = %lld above 384 with a projection: a wave of k_bwd_a2 holds at most 24 k-blocks of weights", SJ("ldm"), (long long)ldm);
+          OP_PTR(SJ("dmt"), p[4], 16);
+        } else {
+          OP_REFUSE(P != H, WHO ": %s = %lld is not H = %lld without a projection (m = h)", SJ("P"), (long long)P, (long long)H);
+          OP_OPT(SJ("dmt"), p[4], 16);
+        }
+        OP_OPT(SJ("dout"), p[0], 16); OP_PTR(SJ("dmst"), p[1], 16); OP_OPT(SJ("Wp"), p[2], 4); OP_OPT(SJ("Wp_sw"), p[3], 16);
+        OP_PTR(SJ("gates"), p[5], 4); OP_PTR(SJ("c_prev"), p[6], 4); OP_PTR(SJ("c_cur"), p[7], 4); OP_PTR(SJ("wf"), p[8], 4);
+        OP_PTR(SJ("wi"), p[9], 4); OP_PTR(SJ("wo"), p[10], 4); OP_PTR(SJ("dc"), p[11], 4); OP_PTR(SJ("len"), p[12], 4);
+        OP_OPT(SJ("drop_ctr"), p[13], 8);
+        BwdAJob& a = jobs.j[j];
+        if (p[13]) {
+          OP_REFUSE(!fl, WHO ": null table (fl: keep of a job with drop_ctr)");
+          OP_REFUSE(!(fl[j] > 0.f && fl[j] <= 1.f), WHO ": %s = %g outside (0, 1]", SJ("keep"), (double)fl[j]);
+          OP_REFUSE(q[7] < 0 || q[7] > (1 << 24), WHO ": %s = %lld outside 0 .. 2^24", SJ("thr"), (long long)q[7]);
+          a.drop = DropSpec{(const unsigned long long*)p[13], (unsigned long long)q[5], (unsigned long long)q[6], (unsigned)q[7], fl[j]};
+        }
+        a.dout = (const float*)p[0]; a.dmst = (const float*)p[1]; a.Wp = (const float*)p[2]; a.Wp_sw = (const float*)p[3]; a.dmt = (float*)p[4];
+        a.gates = (float*)p[5]; a.c_prev = (const float*)p[6]; a.c_cur = (const float*)p[7]; a.wf = (const float*)p[8]; a.wi = (const float*)p[9];
+        a.wo = (const float*)p[10]; a.dc = (float*)p[11]; a.len = (const int*)p[12];
+        a.ldm = (int)ldm; a.P = (int)P; a.t = (int)t; a.N = (int)N; a.H = (int)H;
+        a.nblk_c = (int)((H + bwd_a_cells() - 1) / bwd_a_cells());
+        kb_max = std::max(kb_max, op_kb16(ldm));
+        blocks += job_blocks(a.nblk_c, a.N);
+      }
+      launch_bwd_a(jobs, blocks, kb_max, s);
+      break;
+    }
+    default: {     // bwd_b, bwd_b_splitk: ptrs dz, K?, Ksw?, dx?, dmst?, len?;  dims N, I, n_begin, n_end, lddx, ldm, t, H4, dx_accumulate
+      BwdBJobs jobs{};                                   // bwd_b_splitk: ptrs[6 n] = ws, dims[1 + 9 n] = the floats of ws
+      jobs.n = n;
+      int kb_max = 0, blocks = 0;
+      for (int j = 0; j < n; ++j) {
+        const void* const* p = ptrs + 6 * j;
+        const int64_t* q = dims + 1 + 9 * j;
+        const int64_t N = q[0], I = q[1], nb = q[2], ne = q[3], lddx = q[4], ldm = q[5], t = q[6], H4 = q[7];
+        OP_DIM(SJ("N"), N, 1); OP_DIM(SJ("I"), I, 0); OP_DIM(SJ("n_begin"), nb, 0); OP_DIM(SJ("t"), t, 0); OP_FLAG(SJ("dx_accumulate"), q[8]);
+        OP_REFUSE(ne <= nb || ne > lim, WHO ": %s = %lld not above n_begin = %lld (or above 2^30)", SJ("n_end"), (long long)ne, (long long)nb);
+        OP_LD(SJ("H4"), H4, 4); OP_MUL4(SJ("H4"), H4);
+        OP_PTR(SJ("dz"), p[0], 16); OP_OPT(SJ("K"), p[1], 16); OP_OPT(SJ("Ksw"), p[2], 16); OP_OPT(SJ("dx"), p[3], 4); OP_OPT(SJ("dmst"), p[4], 4);
+        OP_OPT(SJ("len"), p[5], 4);
+        OP_REFUSE(!p[1] && !p[2], WHO ": null pointer (%s): the row-major K or its fragment-tiled copy", SJ("K and Ksw"));
+        if (nb < I) { OP_PTR(SJ("dx"), p[3], 4); OP_LD(SJ("lddx"), lddx, std::min(I, ne)); }
+        if (ne > I) { OP_PTR(SJ("dmst"), p[4], 4); OP_LD(SJ("ldm"), ldm, ne - I); }
+        OP_REFUSE(N * std::max(H4, std::max(nb < I ? lddx : 0, ne > I ? ldm : 0)) > lim || ne * H4 > lim, WHO ": %s above the entry's 2^30",
+                  SJ("N x ld or n_end x H4"));
+        BwdBJob& b = jobs.j[j];
+        b.dz = (const float*)p[0]; b.K = (const float*)p[1]; b.Ksw = (const float*)p[2]; b.dx = (float*)p[3]; b.dmst = (float*)p[4];
+        b.len = (const int*)p[5];
+        b.I = (int)I; b.n_begin = (int)nb; b.n_end = (int)ne; b.lddx = (int)lddx; b.ldm = (int)ldm; b.t = (int)t; b.N = (int)N; b.H4 = (int)H4;
+        b.dx_accumulate = (int)q[8];
+        b.nblk_c = (int)((ne - nb + 15) / 16);
+        kb_max = std::max(kb_max, op_kb16(H4));
+        blocks += job_blocks(b.nblk_c, b.N, op_kb16(H4) <= 64 ? 16 : 32);
+      }
+      if (op == 3) { launch_bwd_b(jobs, blocks, kb_max, s); break; }
+      const int64_t ws_floats = dims[1 + 9 * n];
+      OP_PTR("ws", ptrs[6 * n], 4);
+      const size_t need = bwd_b_plan(jobs, nullptr);
+      OP_REFUSE(ws_floats < 0 || (size_t)ws_floats < need, WHO ": ws of %lld floats below the plan's need of %lld", (long long)ws_floats, (long long)need);
+      for (int j = 0; j < n; ++j)
+        OP_REFUSE((jobs.j[j].kpg + 1) / 2 > 12, WHO ": %s = %d: a wave of k_bwd_bp holds at most 12 k-blocks of weights, (kpg + 1) / 2", SJ("kpg"),
+                  jobs.j[j].kpg);
+      bwd_b_plan(jobs, (float*)ptrs[6 * n]);
+      launch_bwd_b_splitk(jobs, s);
+      break;
+    }
+  }
+  OP_LAUNCHED(WHO);
+}
+#undef WHO
+#undef SJ
+
+int rsrgan_op_lstm_step_last_plan(int32_t out[16]) {
+  OP_REFUSE(!out, "op_lstm_step_last_plan: null pointer");
+  const StepPlanRecord& p = g_step_last_plan;
+  const int v[10] = {p.form, p.threads, p.grid, p.map_valid, p.KG, p.kpg, p.grid2, p.lds, p.groups, p.tiled};
+  for (int i = 0; i < 16; ++i) out[i] = i < 10 ? v[i] : 0;
+  return RSRGAN_OK;
+}
+
 }  // extern "C"

@@ -143,6 +143,19 @@ void launch_bwd_b(const BwdBJobs& jobs, int total_blocks, int kb_max, hipStream_
 // split-K phase B: fills ws/ldw/KG/... of every job (ws_base: >= bwd_b_ws_floats(jobs) floats) and launches both kernels
 size_t bwd_b_plan(BwdBJobs& jobs, float* ws_base);
 void launch_bwd_b_splitk(const BwdBJobs& jobs, hipStream_t s);
+// What the step launchers of this host thread launched last: a few host stores per launch, read back by rsrgan_op_lstm_step_last_plan so
+// a unit test can assert WHICH instantiation computed its numbers.  Host-only: no kernel sees it.  grid / threads / lds: the launch (split-K:
+// of k_bwd_bp; grid2 = k_bwd_b_red's grid); map_valid: the job map was filled (grid <= JOBMAP_MAX; split-K: both maps); groups: jobs that own
+// a group of XCD slots (Place::nx < 8); KG, kpg, tiled (1: Ksw, 0: row-major K): job 0 of a split-K launch.
+enum { STEP_FORM_NONE = 0,
+       STEP_FORM_GATES_18_1 = 1 /* k_fwd_gates<18, 1>, 16-row blocks */, STEP_FORM_GATES_18_2 = 2, STEP_FORM_GATES_32_2 = 3,
+       STEP_FORM_PROJ_4 = 4 /* k_fwd_proj<4> */, STEP_FORM_PROJ_8 = 5, STEP_FORM_PROJ_4_DROP = 6, STEP_FORM_PROJ_8_DROP = 7,
+       STEP_FORM_BWD_A_4 = 8 /* k_bwd_a2<4> */, STEP_FORM_BWD_A_18 = 9, STEP_FORM_BWD_A_24 = 10, STEP_FORM_BWD_A_4_DROP = 11,
+       STEP_FORM_BWD_A_18_DROP = 12, STEP_FORM_BWD_A_24_DROP = 13,
+       STEP_FORM_BWD_B_16 = 14 /* k_bwd_b<8, 8, 8, 1>, 16-row tiles */, STEP_FORM_BWD_B_PIPE = 15 /* k_bwd_b<8, 0, 6> */,
+       STEP_FORM_BWD_B_SPLITK = 16 /* k_bwd_bp + k_bwd_b_red */ };
+struct StepPlanRecord { int form, threads, grid, map_valid, KG, kpg, grid2, lds, groups, tiled; };
+extern thread_local StepPlanRecord g_step_last_plan;
 // ---- persistent discriminator recurrence (dpersist.hip) ----
 constexpr int DP_MAXL = 3;
 constexpr int DP_CTL_GEN = 0, DP_CTL_DONE = 1, DP_CTL_ERR = 2, DP_CTL_WORDS = 4;   // err: 0, or 1 + the first workgroup whose bounded wait expired

@@ -1010,6 +1010,13 @@ void launch_floor_chain(float* a, float* b, int n, int mode, hipStream_t s) {
   for (int i = 0; i < n; ++i) hipLaunchKernelGGL(k_floor, dim3(256), dim3(256), 0, s, (i & 1) ? b : a, (i & 1) ? a : b, mode);
 }
 long long g_chain_launches = 0;     // launches of the recurrence kernels issued by the host since the last reset (bench.py: latency bound)
+thread_local StepPlanRecord g_step_last_plan = {};       // what this host thread's step launchers launched last (host-only; rsrgan_op_lstm_step_last_plan)
+template <typename JobsT>
+static void step_record(int form, int threads, int grid, size_t lds, const JobsT& jobs) {
+  int groups = 0;
+  for (int i = 0; i < jobs.n; ++i) groups += jobs.j[i].pl.nx < 8;
+  g_step_last_plan = StepPlanRecord{form, threads, grid, jobs.map.valid, 0, 0, 0, (int)lds, groups, 0};
+}
 void launch_bwd_b_splitk(const BwdBJobs& jobs, hipStream_t s) {
   g_chain_launches += 2;
   int bp = 8, br = 8, kpg_max = 1, nbp = 0;
@@ -1026,6 +1033,12 @@ void launch_bwd_b_splitk(const BwdBJobs& jobs, hipStream_t s) {
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bwd_bp), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set = true;
+  }
+  {
+    int groups = 0;
+    for (int i = 0; i < jobs.n; ++i) groups += jobs.j[i].plp.nx < 8;
+    g_step_last_plan = StepPlanRecord{STEP_FORM_BWD_B_SPLITK, 512, bp, (jobs.map.valid && jobs.mapr.valid) ? 1 : 0, jobs.n > 0 ? jobs.j[0].KG : 0,
+                                      jobs.n > 0 ? jobs.j[0].kpg : 0, br, (int)lds, groups, (jobs.n > 0 && jobs.j[0].Ksw) ? 1 : 0};
   }
   hipLaunchKernelGGL(k_bwd_bp, dim3(bp), dim3(512), lds, s, jobs);
   hipLaunchKernelGGL(k_bwd_b_red, dim3(br), dim3(256), 0, s, jobs);
@@ -1049,6 +1062,7 @@ void launch_fwd_gates(const FwdGateJobs& jobs_in, int total_blocks, int kb_max, 
     lds = std::max(lds, (size_t)8 * 16 * 17 * sizeof(float));
     static bool attr1 = false;
     if (!attr1) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwd_gates<18, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr1 = true; }
+    step_record(STEP_FORM_GATES_18_1, 512, total_blocks, lds, jobs);
     hipLaunchKernelGGL((k_fwd_gates<18, 1>), dim3(total_blocks), dim3(512), lds, s, jobs);
     return;
   }
@@ -1071,8 +1085,12 @@ void launch_fwd_gates(const FwdGateJobs& jobs_in, int total_blocks, int kb_max, 
     if (!attr2) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwd_gates<32, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr2 = true; }
     size_t l2 = (size_t)32 * gates_sa4(ktot) * 16;
     l2 = (l2 + 8191) / 8192 * 8192;
+    step_record(STEP_FORM_GATES_32_2, 512, total_blocks, l2, jobs);
     hipLaunchKernelGGL((k_fwd_gates<32, 2>), dim3(total_blocks), dim3(512), l2, s, jobs);
-  } else hipLaunchKernelGGL((k_fwd_gates<18, 2>), dim3(total_blocks), dim3(512), lds, s, jobs);
+  } else {
+    step_record(STEP_FORM_GATES_18_2, 512, total_blocks, lds, jobs);
+    hipLaunchKernelGGL((k_fwd_gates<18, 2>), dim3(total_blocks), dim3(512), lds, s, jobs);
+  }
 }
 void launch_fwd_proj(const FwdProjJobs& jobs_in, int total_blocks, int kb_max, hipStream_t s) {
   ++g_chain_launches;
@@ -1080,6 +1098,7 @@ void launch_fwd_proj(const FwdProjJobs& jobs_in, int total_blocks, int kb_max, h
   total_blocks = place_tiles(jobs, 32, [](const FwdProjJob& j) { return (double)j.ldh; });
   bool drop = false;
   for (int i = 0; i < jobs.n; ++i) drop |= jobs.j[i].drop.ctr != nullptr;
+  step_record((kb_max <= 24 ? STEP_FORM_PROJ_4 : STEP_FORM_PROJ_8) + (drop ? 2 : 0), kb_max <= 24 ? 256 : 512, total_blocks, 0, jobs);
   if (drop) {
     if (kb_max <= 24) hipLaunchKernelGGL((k_fwd_proj<4, true>), dim3(total_blocks), dim3(256), 0, s, jobs);
     else hipLaunchKernelGGL((k_fwd_proj<8, true>), dim3(total_blocks), dim3(512), 0, s, jobs);
@@ -1100,6 +1119,7 @@ void launch_bwd_a(const BwdAJobs& jobs_in, int total_blocks, int kb_max, hipStre
   const size_t lds = (size_t)32 * sa4 * 16;
   bool drop = false;
   for (int i = 0; i < jobs.n; ++i) drop |= jobs.j[i].drop.ctr != nullptr;
+  step_record((kb_max <= 4 ? STEP_FORM_BWD_A_4 : kb_max <= 18 ? STEP_FORM_BWD_A_18 : STEP_FORM_BWD_A_24) + (drop ? 3 : 0), 256, total_blocks, lds, jobs);
   if (drop) {
     if (kb_max <= 4) hipLaunchKernelGGL((k_bwd_a2<4, true>), dim3(total_blocks), dim3(256), lds, s, jobs);
     else if (kb_max <= 18) hipLaunchKernelGGL((k_bwd_a2<18, true>), dim3(total_blocks), dim3(256), lds, s, jobs);
@@ -1112,6 +1132,7 @@ void launch_bwd_b(const BwdBJobs& jobs_in, int total_blocks, int kb_max, hipStre
   ++g_chain_launches;
   BwdBJobs jobs = jobs_in;
   total_blocks = place_tiles(jobs, kb_max <= 64 ? 16 : 32, [](const BwdBJob& j) { return (double)j.H4; });
+  step_record(kb_max <= 64 ? STEP_FORM_BWD_B_16 : STEP_FORM_BWD_B_PIPE, 512, total_blocks, 0, jobs);
   if (kb_max <= 64)  // small K (the discriminator alone): 8 waves x <= 8 k-blocks, one load round, no pipeline, 16-row tiles
     hipLaunchKernelGGL((k_bwd_b<8, 8, 8, 1>), dim3(total_blocks), dim3(512), 0, s, jobs);
   else               // 8 waves split K; each runs a double-buffered 6-k-block register pipeline

@@ -541,7 +541,9 @@ int Model::alloc_shared() {
   if (!inf) {                                               // (column sums and loss partials; the per-step FC stage of the fused training launches)
     scratch = alloc<float>(scratch_floats);
     scratch2 = alloc<float>(std::max<size_t>(4 * 64 * maxcols, 1024));
-    g_fc_out_wT = g_dnn() ? nullptr : alloc<float>((size_t)Dout * g_ldP());
+    // (at least B floats: k_fwd_proj reads the stand-in of a stage's missing `len` -- one word per row, unused -- from WpT, which a narrow
+    //  output under a large batch, Dout x ldP < B, would otherwise end before; rsrgan_op_lstm_step refuses that shape)
+    g_fc_out_wT = g_dnn() ? nullptr : alloc<float>(std::max((size_t)Dout * g_ldP(), (size_t)B));
   }
   if (inf || hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess) side = nullptr;
   if (hipEventCreateWithFlags(&ev_last, hipEventDisableTiming) != hipSuccess) ev_last = nullptr;

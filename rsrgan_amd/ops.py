@@ -10,7 +10,8 @@ import torch
 
 from . import _lib
 from ._lib import (BN_PLAN_FIELDS, BN_ROUTES, CONV_FAMILIES, CONV_FWD_BRANCHES, CONV_PLAN_FIELDS, CONV_WGRAD_BRANCHES, GEMM_CLASSES,
-                   GEMM_PLAN_FIELDS, LAYOUT_OPS, SEGAN_OPS, SEGAN_PLAN_FIELDS, STEP_ELEM_OPS, UPDATE_OPS, check, ptr_table)
+                   GEMM_PLAN_FIELDS, LAYOUT_OPS, LSTM_STEP_FORMS, LSTM_STEP_OPS, LSTM_STEP_PLAN_FIELDS, SEGAN_OPS, SEGAN_PLAN_FIELDS, STEP_ELEM_OPS,
+                   UPDATE_OPS, check, ptr_table)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -243,6 +244,18 @@ class OpEntries:
     def op_layout(self, op, ptrs, dims=(), fl=()):
         """rsrgan_op_layout, op by name (_lib.LAYOUT_OPS); ptrs: tensors or None, dims: ints, fl: floats (include/rsrgan.h)"""
         check(self.lib.rsrgan_op_layout(LAYOUT_OPS.index(op), *self._tables(ptrs, dims, fl), self._stream()))
+
+    def op_lstm_step(self, op, ptrs, dims, fl=()):
+        """rsrgan_op_lstm_step, op by name (_lib.LSTM_STEP_OPS): one launch of n jobs; ptrs: one group of tensors or None per job, dims: n, then
+        one record per job (split-K: then ws and its floats), fl: forget_bias, or keep per job (include/rsrgan.h)"""
+        check(self.lib.rsrgan_op_lstm_step(LSTM_STEP_OPS.index(op), *self._tables(ptrs, dims, fl), self._stream()))
+
+    def op_lstm_step_last_plan(self) -> dict:
+        out = (C.c_int32 * 16)()
+        check(self.lib.rsrgan_op_lstm_step_last_plan(out))
+        d = dict(zip(LSTM_STEP_PLAN_FIELDS, list(out)))
+        d["form"] = LSTM_STEP_FORMS[d["form"]]
+        return d
 
     def device_status(self) -> int:
         """the handle-free form of HipEngine.device_status: waits for the current stream; 0, or -2 (RSRGAN_ERR_HIP) where a launch or a
