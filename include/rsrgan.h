@@ -639,6 +639,50 @@ int rsrgan_wave_reverb(const void* pcm, int32_t kind, int64_t n_samples, const i
                        const int32_t* sel, const float* snr, int32_t B, int32_t R, int32_t V, int32_t C, const float* twiddle, int32_t flags,
                        float* out, int64_t out_samples, const int64_t* out_seg, float* gains, void* work, int64_t work_bytes, void* stream);
 int64_t rsrgan_wave_reverb_work(int32_t B, int64_t n_max, int64_t L_max, int32_t C);
+/* Audio out (csrc/synth.hip): enhanced LPS rows back to samples -- the magnitude of every frame is replaced by the row's, the
+ * phase of the utterance's own (reverberant) samples is kept, the frames are overlap-added with the analysis window and the pre-emphasis
+ * is undone.  Kaldi has no such tool: nothing is pinned against a Kaldi binary; the tests pin the definition below against float64.
+ * All constants and symbols are rsrgan_feat_wave's: N, S, P, H = P / 2, NB = H + 1, eps = FLT_EPSILON, a = preemph, the caller's window
+ * table w [N] and twiddle table [P / 2][2], samples of kind 0 / 1.  Utterance b is the n samples x[0 .. n) of seg[b]; its LPS rows are rows
+ * offsets[b] .. offsets[b + 1] of lps [lps_rows][NB] float32: de-normalised natural-log power on the int16 scale, what rsrgan_feat_wave
+ * itself would write.  F = min(F_b, offsets[b + 1] - offsets[b], lps_rows - offsets[b]) with rsrgan_feat_wave's frame count F_b.
+ *   per frame f < F, on v[i] = x[f S + i], row = offsets[b] + f:
+ *     1. m_f = (sum v) / N; v -= m_f; then steps 3, 4, 5 of rsrgan_feat_wave unchanged: X_k (complex) and p_k = |X_k|^2, k = 0 .. H
+ *     2. L_k = lps[row][k] clamped into [-80, 80]; a NaN counts as -80
+ *     3. g_k = exp((L_k - log max(p_k, eps)) / 2) for k = 1 .. H (not sqrt(exp(L) / p), which overflows fp32); g_0 = g_1: bin 0 of an
+ *        LPS row carries the raw energy, not a DC power, so DC follows the lowest bin
+ *     4. Y_k = g_k X_k;  y_f[i] = IDFT_P(Y)[i] for i < N (Y is Hermitian by construction: y_f is real)
+ *     5. y_f[i] += w[i] (1 - a) m_f g_1: the mean step 1 removed, restored in the pre-emphasised domain with the lowest bin's gain
+ *        (preemph(v - m) = preemph(v) - (1 - a) m at every i, the i = 0 rule included)
+ *   overlap-add; sample i = 0 of a frame enters neither sum (v'[0] = v[0] - a v[0] disagrees with every other frame on that sample):
+ *     num[t] = sum_f w[i] y_f[i],  den[t] = sum_f w[i]^2,  i = t - f S, 1 <= i < N, f ascending (at most ceil(N / S) terms)
+ *     z[t] = den[t] > 0 ? num[t] / max(den[t], 1e-3) : 0          the floor: a short fade where a window reaches zero at the utterance's
+ *                                                                ends (Povey); Hamming's smallest den is 0.0064
+ *   de-emphasis over the utterance: out[t] = z[t] + a out[t - 1], out[-1] = 0, for t < (F - 1) S + N.
+ * Samples t >= (F - 1) S + N (no frame covers them) and every sample of an utterance with F = 0 are written as +0.0.  Utterance b writes
+ * min(n, capacity_b) samples at out_seg[b] = (first, capacity): float32 on the int16 scale, not quantised; nothing else is written.  So
+ * out is linear in exp(L / 2), and with L the utterance's own LPS g = 1 and the chain gives x[t] - a^t x[0] wherever den is above the floor.
+ * Arithmetic: fp32 throughout; the inverse transform is the merge pass and the forward FFT on the conjugate; the recurrence runs in chunks
+ * of rsrgan_wave_synth_chunk() samples from a zero state (strips per lane, a scan over the lanes, the wavefronts in order), the chunks'
+ * end values are carried utterance by utterance (c_{j+1} = e_j + a^CH c_j) and added as a^(i + 1) c_j; powers of a are repeated products
+ * in a fixed order.  No sincosf, no atomics: an utterance's bits depend on its samples, its LPS rows, the tables and N, S, P, a only, not
+ * on B, its place in the batch or the sample kind.  Every segment, offset, row, sample index and capacity is clamped: the kernels read
+ * and write nothing outside their buffers, whatever the device-resident tables hold (out segments that overlap give unspecified values
+ * inside out).  work: rsrgan_wave_synth_work(B, lps_rows, out_samples, N) bytes -- lps_rows * N floats (the windowed frames) and
+ * ceil(out_samples / CH) + B carries; 0 for B outside [1, 65535], lps_rows or out_samples outside [1, 2^40], N outside [1, 2048].  No
+ * handle, no allocation, nothing synchronises with the host; four launches on `stream`.  All pointers are DEVICE pointers.
+ * RSRGAN_ERR_INVALID before the first HIP call, rsrgan_last_error() naming the argument, for: a null pcm, seg, offsets, lps, window,
+ * twiddle, out, out_seg or work; a kind other than 0 or 1; pcm not aligned to its element; lps or work not 16-byte, seg or out_seg not
+ * 8-byte, offsets, window, twiddle or out not 4-byte aligned; B outside [1, 65535]; n_samples, lps_rows or out_samples outside
+ * [1, 2^40]; P no power of two in [64, 2048]; not 1 <= S <= N <= P; preemph outside [0, 1] (or NaN); work_bytes below
+ * rsrgan_wave_synth_work(B, lps_rows, out_samples, N). */
+int rsrgan_wave_synth(const void* pcm, int32_t kind, int64_t n_samples, const int64_t* seg, const int32_t* offsets, const float* lps,
+                      int64_t lps_rows, int32_t B, int32_t N, int32_t S, int32_t P, float preemph, const float* window,
+                      const float* twiddle, float* out, int64_t out_samples, const int64_t* out_seg, void* work, int64_t work_bytes,
+                      void* stream);
+int64_t rsrgan_wave_synth_work(int32_t B, int64_t lps_rows, int64_t out_samples, int32_t N);
+/* The samples of a scan chunk of rsrgan_wave_synth (CH).  Tests place their utterance lengths around it. */
+int rsrgan_wave_synth_chunk(void);
 
 /* ---- TensorBoard histogram summaries on the device (csrc/hist.hip): what tf.summary.histogram's HistogramProto holds,
  * computed where the tensors are.  No handle.  x: a HOST table of n DEVICE pointers to float32 tensors; dims: a HOST table of n x

@@ -31,7 +31,7 @@ SYMBOLS = ["rsrgan_default_cfg", "rsrgan_create", "rsrgan_destroy", "rsrgan_last
            "rsrgan_op_bn_forward", "rsrgan_op_bn_backward", "rsrgan_op_bn_commit", "rsrgan_op_bn_last_plan",
            "rsrgan_op_bn_seq_forward", "rsrgan_op_bn_seq_backward", "rsrgan_feat_batch", "rsrgan_feat_frames",
            "rsrgan_feat_stream", "rsrgan_feat_denorm", "rsrgan_feat_decode", "rsrgan_feat_wave", "rsrgan_feat_mfcc", "rsrgan_feat_wave_frames",
-           "rsrgan_wave_reverb", "rsrgan_wave_reverb_work",
+           "rsrgan_wave_reverb", "rsrgan_wave_reverb_work", "rsrgan_wave_synth", "rsrgan_wave_synth_work", "rsrgan_wave_synth_chunk",
            "rsrgan_hist", "rsrgan_hist_limits", "rsrgan_d_logits", "rsrgan_d_logits_hist",
            "rsrgan_op_segan_sizes", "rsrgan_op_segan_conv2", "rsrgan_op_segan_conv1", "rsrgan_op_segan_colred", "rsrgan_op_segan_last_plan",
            "rsrgan_op_segan_vbn", "rsrgan_op_segan_elem", "rsrgan_op_segan_dhead",
@@ -143,6 +143,10 @@ def load():
     lib.rsrgan_wave_reverb.argtypes = [p, i32, i64, p, p, i64, p, p, i64, p, p, p, p, i32, i32, i32, i32, p, i32, p, i64, p, p, p, i64, vp]
     lib.rsrgan_wave_reverb_work.argtypes = [i32, i64, i64, i32]
     lib.rsrgan_wave_reverb_work.restype = i64
+    lib.rsrgan_wave_synth.argtypes = [p, i32, i64, p, p, p, i64, i32, i32, i32, i32, f32, p, p, p, i64, p, p, i64, vp]
+    lib.rsrgan_wave_synth_work.argtypes = [i32, i64, i64, i32]
+    lib.rsrgan_wave_synth_work.restype = i64
+    lib.rsrgan_wave_synth_chunk.argtypes = []
     lib.rsrgan_hist.argtypes = [i32, pp, C.POINTER(i64), p, vp]
     lib.rsrgan_hist_limits.argtypes = [C.POINTER(C.c_double), C.POINTER(i32)]
     lib.rsrgan_d_logits.argtypes = [vp, p, p, C.POINTER(i32), vp]

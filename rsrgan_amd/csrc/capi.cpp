@@ -699,6 +699,45 @@ int rsrgan_wave_reverb(const void* pcm, int32_t kind, int64_t n_samples, const i
   OP_LAUNCHED("wave_reverb");
 }
 
+// ---- audio out on the device (synth.hip): no handle, no allocation; four launches on the caller's stream
+int rsrgan_wave_synth_chunk(void) { return synth_chunk(); }
+
+int64_t rsrgan_wave_synth_work(int32_t B, int64_t lps_rows, int64_t out_samples, int32_t N) {
+  const int64_t lim = (int64_t)1 << 40;
+  if (B < 1 || B > 65535 || lps_rows < 1 || lps_rows > lim || out_samples < 1 || out_samples > lim || N < 1 || N > 2048) return 0;
+  return (int64_t)sizeof(float) * (int64_t)synth_work_floats(B, (long long)lps_rows, (long long)out_samples, N);
+}
+
+int rsrgan_wave_synth(const void* pcm, int32_t kind, int64_t n_samples, const int64_t* seg, const int32_t* offsets, const float* lps,
+                      int64_t lps_rows, int32_t B, int32_t N, int32_t S, int32_t P, float preemph, const float* window, const float* twiddle,
+                      float* out, int64_t out_samples, const int64_t* out_seg, void* work, int64_t work_bytes, void* stream) {
+  OP_REFUSE(!pcm || !seg || !offsets || !out, "wave_synth: null pointer (pcm, seg, offsets or out)");
+  OP_REFUSE(!window || !twiddle, "wave_synth: null pointer (window or twiddle)");
+  OP_REFUSE(!lps || !out_seg || !work, "wave_synth: null pointer (lps, out_seg or work)");
+  OP_REFUSE(kind != 0 && kind != 1, "wave_synth: kind = %d is neither 0 (int16) nor 1 (float32)", kind);
+  OP_REFUSE((size_t)pcm & (kind ? 3 : 1), "wave_synth: pcm not aligned to its %d-byte samples", kind ? 4 : 2);
+  OP_REFUSE(((size_t)lps & 15) || ((size_t)work & 15), "wave_synth: lps or work not 16-byte aligned");
+  OP_REFUSE(((size_t)seg & 7) || ((size_t)out_seg & 7), "wave_synth: seg or out_seg not 8-byte aligned");
+  OP_REFUSE(((size_t)offsets & 3) || ((size_t)window & 3) || ((size_t)twiddle & 3) || ((size_t)out & 3),
+            "wave_synth: offsets, window, twiddle or out not 4-byte aligned");
+  OP_REFUSE(B < 1 || B > 65535, "wave_synth: B = %d outside [1, 65535]", B);
+  OP_REFUSE(n_samples < 1, "wave_synth: n_samples must be positive (got %lld)", (long long)n_samples);
+  OP_REFUSE(n_samples > ((int64_t)1 << 40), "wave_synth: n_samples = %lld above the entry's 2^40", (long long)n_samples);
+  OP_REFUSE(lps_rows < 1 || lps_rows > ((int64_t)1 << 40), "wave_synth: lps_rows = %lld outside [1, 2^40]", (long long)lps_rows);
+  OP_REFUSE(out_samples < 1 || out_samples > ((int64_t)1 << 40), "wave_synth: out_samples = %lld outside [1, 2^40]", (long long)out_samples);
+  OP_REFUSE(P < 64 || P > 2048 || (P & (P - 1)), "wave_synth: P = %d is no power of two in [64, 2048]", P);
+  OP_REFUSE(S < 1 || N < S || P < N, "wave_synth: N = %d, S = %d, P = %d outside 1 <= S <= N <= P", N, S, P);
+  OP_REFUSE(!(preemph >= 0.f && preemph <= 1.f), "wave_synth: preemph = %g outside [0, 1]", (double)preemph);
+  const int64_t need = rsrgan_wave_synth_work(B, lps_rows, out_samples, N);
+  OP_REFUSE(work_bytes < need, "wave_synth: work_bytes = %lld below the %lld bytes rsrgan_wave_synth_work(%d, %lld, %lld, %d) gives",
+            (long long)work_bytes, (long long)need, B, (long long)lps_rows, (long long)out_samples, N);
+  SynArgs a{pcm, kind, (long long)n_samples, reinterpret_cast<const long long*>(seg), offsets, lps, (long long)lps_rows, B, (uint32_t)N, (uint32_t)S,
+            (uint32_t)P, preemph, window, twiddle, out, (long long)out_samples, reinterpret_cast<const long long*>(out_seg),
+            static_cast<float*>(work), 0ll, 0u};
+  launch_wave_synth(a, (hipStream_t)stream);
+  OP_LAUNCHED("wave_synth");
+}
+
 // ---- TensorBoard histograms on the device (hist.hip): no handle; two launches on the caller's stream
 int rsrgan_hist_limits(double* out, int32_t* n) {
   OP_REFUSE(!n, "hist_limits: null pointer (n)");

@@ -519,6 +519,17 @@ struct RevArgs {
 };
 size_t reverb_work_bytes(int B, long long n_max, long long L_max, int C);
 void launch_wave_reverb(const RevArgs& a, size_t work_bytes, hipStream_t s);
+// ---- audio out on the device (synth.hip): the arguments of rsrgan_wave_synth (include/rsrgan.h) as the four kernels take them; slots (the
+// carries behind the lps_rows * N frame floats of work) and F (the frames of a run) are filled by the launch.  synth_work_floats: the
+// floats of work; synth_chunk: the samples of a scan chunk.
+struct SynArgs {
+  const void* pcm; int kind; long long n_samples; const long long* seg; const int* offsets;
+  const float* lps; long long lps_rows; int B; uint32_t N, S, P; float preemph; const float* window; const float* twiddle;
+  float* out; long long out_samples; const long long* out_seg; float* work; long long slots; uint32_t F;
+};
+int synth_chunk();
+long long synth_work_floats(int B, long long lps_rows, long long out_samples, int N);
+void launch_wave_synth(const SynArgs& a, hipStream_t s);
 // ---- TensorBoard histograms on the device (hist.hip): for each of n <= HIST_MAX_TENSORS strided float32 views (element (r, c) at
 // x[r * ld + c * cs]; rows * cols <= 2^31 - 1; x may be null where rows * cols == 0) one record of HIST_REC doubles in out: min, max, num,
 // sum, sum_squares and the count of each of the HIST_NL buckets of TensorFlow's default limits (hist_limits(), built once on the host).

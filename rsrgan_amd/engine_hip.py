@@ -153,6 +153,63 @@ class WaveFrontEnd(OpEntries):
                                 spec.normalize, stream=us)
         return out, oseg, out_seg
 
+    # -- audio out (include/rsrgan.h rsrgan_wave_synth, csrc/synth.hip) ---------------------------------------------------------------
+    def wave_synth_chunk(self):
+        """the samples of a scan chunk of the synthesis kernels (rsrgan_wave_synth_chunk)"""
+        return int(self.lib.rsrgan_wave_synth_chunk())
+
+    def wave_synth_work(self, B, lps_rows, out_samples, N=400):
+        """the bytes of `work` for B utterances, lps_rows LPS rows and out_samples output samples (rsrgan_wave_synth_work)"""
+        need = int(self.lib.rsrgan_wave_synth_work(B, lps_rows, out_samples, N))
+        if need <= 0:
+            raise ValueError("wave_synth_work: B = %d, lps_rows = %d, out_samples = %d, N = %d outside the entry's limits" % (
+                B, lps_rows, out_samples, N))
+        return need
+
+    def op_wave_synth(self, pcm, seg, offsets, lps, B, window, twiddle, out, out_seg, work, N=400, S=160, P=512, preemph=0.97, kind=None,
+                      lps_rows=None, stream=None):
+        """rsrgan_wave_synth on caller-owned device tensors (pcm, seg, offsets, window, twiddle as op_feat_wave takes them; lps [rows,
+        P / 2 + 1] f32; out f32 [samples], out_seg [B, 2] i64 = (first, capacity); work uint8 (wave_synth_work bytes)), on `stream`
+        (default: the current one); nothing is allocated and nothing waits for the device."""
+        if kind is None:
+            if pcm.dtype not in (torch.int16, torch.float32):
+                raise ValueError("op_wave_synth: pcm must be int16 or float32, got %s" % pcm.dtype)
+            kind = 0 if pcm.dtype == torch.int16 else 1
+        check(self.lib.rsrgan_wave_synth(_ptr(pcm), kind, pcm.numel(), _ptr(seg), _ptr(offsets), _ptr(lps),
+                                         lps.shape[0] if lps_rows is None else lps_rows, B, N, S, P, preemph, _ptr(window), _ptr(twiddle),
+                                         _ptr(out), out.numel(), _ptr(out_seg), _ptr(work), work.numel() * work.element_size(),
+                                         self._stream() if stream is None else C.c_void_p(stream.cuda_stream)))
+
+    def synthesize(self, wb, lps, stream=None):
+        """io.WaveBatch (the samples the frames came from) + LPS rows [rows, bins] (a device or host tensor, or an array; de-normalised,
+        utterance b at rows wb.offsets[b] .. wb.offsets[b + 1]) -> (samples float32 [sum n] on the device, their segment table int64
+        [B, 2] on the host): rsrgan_wave_synth on `stream` (default: the upload stream), the uploads queued there too.  The window and
+        twiddle tables are the engine's cached ones; `work` is kept and grown."""
+        spec = wb.spec
+        if hasattr(spec, "num_mel_bins"):
+            raise ValueError("synthesize: the batch's spec makes MFCC / log-mel frames; only an LPS framing (io.wave.WaveSpec) can be inverted")
+        us = self.upload_stream() if stream is None else stream
+        if not torch.is_tensor(lps):
+            lps = torch.from_numpy(np.ascontiguousarray(lps, np.float32))
+        if lps.dim() != 2 or lps.shape[1] != spec.bins or lps.shape[0] < 1:
+            raise ValueError("synthesize: lps must be [rows >= 1, %d], got %s" % (spec.bins, tuple(lps.shape)))
+        B, total = len(wb), max(int(wb.samples.shape[0]), 1)
+        need = self.wave_synth_work(B, int(lps.shape[0]), total, spec.frame_length)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=True)
+        if lps.is_cuda:
+            us.wait_stream(torch.cuda.current_stream(self.device))           # (the rows were made on the caller's stream)
+            lps.record_stream(us)
+        with torch.cuda.stream(us):
+            win, tw = self._wave_tables(spec, us)
+            work = self.__dict__.get("_synth_work")
+            if work is None or work.numel() < need:
+                work = self._synth_work = torch.empty(need, dtype=torch.uint8, device=self.device)
+            lps = lps.to(self.device, torch.float32, non_blocking=True).contiguous()
+            out = torch.empty(total, dtype=torch.float32, device=self.device)
+            self.op_wave_synth(up(wb.samples), up(wb.seg), up(wb.offsets), lps, B, win, tw, out, up(wb.seg), work, spec.frame_length,
+                               spec.frame_shift, spec.padded, spec.preemph, stream=us)
+        return out, wb.seg
+
     def _wave_tables(self, spec, us):
         """the window and the twiddles of a framing as fp32 device tensors: built on the host in float64, rounded once, uploaded at first use
         and kept per engine (as _cmvn_device keeps the statistics).  For an io.wave.MfccSpec three more follow: mel_seg, mel_w and the DCT

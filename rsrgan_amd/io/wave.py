@@ -14,7 +14,11 @@ window and the twiddles as tables built here in float64 and rounded once.
 The labels of the recipes are another feature of the same audio: 40-dim MFCC (Kaldi's compute-mfcc-feats with the WSJ mfcc_hires.conf),
 stated at rsrgan_feat_mfcc in include/rsrgan.h.  MfccSpec holds its parameters, mel_table / dct_table build the filterbank and the
 liftered DCT the kernel takes as tables, mfcc_from_wave is the host route; the device route is HipEngine.op_feat_mfcc /
-featurize(WaveBatch with an MfccSpec) (csrc/wave.hip k_feat_mfcc).  io/wave_reader.py reads training batches from two wav.scp files."""
+featurize(WaveBatch with an MfccSpec) (csrc/wave.hip k_feat_mfcc).  io/wave_reader.py reads training batches from two wav.scp files.
+
+The way back is wave_from_lps: enhanced LPS rows and the samples they came from -> samples (the row's magnitude, the samples' phase,
+weighted overlap-add, de-emphasis), stated at rsrgan_wave_synth in include/rsrgan.h; the device route is HipEngine.op_wave_synth /
+synthesize (csrc/synth.hip).  quantize_pcm and write_wav take the result to a 16-bit RIFF file, read_wav's inverse."""
 from __future__ import annotations
 
 import wave as _wave
@@ -259,6 +263,64 @@ def lps_from_wave(x, window="hamming", spec=None):
     out = np.log(np.maximum(X.real ** 2 + X.imag ** 2, EPS))
     out[:, 0] = energy
     return out.astype(np.float32)
+
+
+def wave_from_lps(lps, samples, spec=DEFAULT):
+    """the host route of audio out: LPS rows [rows, P / 2 + 1] (de-normalised, what lps_from_wave gives) and the samples [n] the frames
+    came from -> float64 samples [n] on the int16 scale, the definition of rsrgan_wave_synth in float64 (np.fft, sequential de-emphasis).
+    F = min(num_frames(n), rows); samples no frame covers are 0."""
+    N, S, P, a = spec.frame_length, spec.frame_shift, spec.padded, spec.preemph
+    x, lps = np.asarray(samples), np.asarray(lps)
+    if x.ndim != 1:
+        raise ValueError("samples must be a 1-D array, got shape %s" % (x.shape,))
+    if lps.ndim != 2 or lps.shape[1] != P // 2 + 1:
+        raise ValueError("lps must be [rows, %d], got shape %s" % (P // 2 + 1, lps.shape))
+    n = x.shape[0]
+    F = min(num_frames(n, spec), lps.shape[0])
+    out = np.zeros(n, np.float64)
+    if F == 0:
+        return out
+    w = window_table(spec.window, N)
+    v = x[np.arange(F)[:, None] * S + np.arange(N)[None, :]].astype(np.float64)
+    m = v.sum(1, keepdims=True) / N
+    v -= m
+    v = (v - a * np.concatenate([v[:, :1], v[:, :-1]], 1)) * w
+    X = np.fft.rfft(v, n=P, axis=1)
+    L = lps[:F].astype(np.float64)
+    L = np.clip(np.where(np.isnan(L), -80.0, L), -80.0, 80.0)
+    g = np.exp(0.5 * (L - np.log(np.maximum(X.real ** 2 + X.imag ** 2, EPS))))
+    g[:, 0] = g[:, 1]
+    y = np.fft.irfft(g * X, n=P, axis=1)[:, :N] + w * (1.0 - a) * m * g[:, 1:2]
+    cov = (F - 1) * S + N
+    num, den = np.zeros(cov, np.float64), np.zeros(cov, np.float64)
+    w2 = w * w
+    for f in range(F):                                                # (f ascending; sample 0 of a frame enters neither sum)
+        num[f * S + 1:f * S + N] += w[1:] * y[f, 1:]
+        den[f * S + 1:f * S + N] += w2[1:]
+    z = np.where(den > 0.0, num / np.maximum(den, 1e-3), 0.0)
+    prev = 0.0
+    for t in range(cov):
+        prev = out[t] = z[t] + a * prev
+    return out
+
+
+def quantize_pcm(y):
+    """float samples on the int16 scale -> int16: rint, saturated to [-32768, 32767]"""
+    return np.clip(np.rint(np.asarray(y, np.float64)), -32768.0, 32767.0).astype(np.int16)
+
+
+def write_wav(path, samples, sample_rate=16000):
+    """int16 samples [n] (anything else goes through quantize_pcm) -> a mono RIFF file of 16-bit PCM (stdlib `wave`): read_wav's inverse"""
+    samples = np.asarray(samples)
+    if samples.ndim != 1:
+        raise ValueError("samples must be a 1-D array, got shape %s" % (samples.shape,))
+    if samples.dtype != np.int16:
+        samples = quantize_pcm(samples)
+    with _wave.open(str(path), "wb") as f:
+        f.setnchannels(1)
+        f.setsampwidth(2)
+        f.setframerate(int(sample_rate))
+        f.writeframes(samples.astype("<i2").tobytes())
 
 
 def read_wav(path, channel=0, sample_rate=16000):

@@ -2,7 +2,8 @@
 
     python -m rsrgan_amd.io.wave_cmvn --inputs_wav_scp tr/inputs_wav.scp --labels_wav_scp tr/labels_wav.scp --out data/train/train_cmvn.npz [--device]
 
-Inputs become log-power-spectrum frames (io.wave.DEFAULT), labels MFCC frames (io.wave.MFCC_DEFAULT).  Per dimension, sum x and sum x^2
+Inputs become log-power-spectrum frames (io.wave.DEFAULT), labels MFCC frames (io.wave.MFCC_DEFAULT) or, with --label_kind lps, LPS
+frames too.  Per dimension, sum x and sum x^2
 over all frames are accumulated in float64; mean = sum x / n, stddev = sqrt(sum x^2 / n - mean^2), as the reference's
 convert_cmvn_to_numpy.py computes them from Kaldi's statistics.  --device: the frames come from the two kernels of csrc/wave.hip and are
 summed with float64 torch reductions on the device.  A dimension with zero variance is an error here, not a division by zero later.
@@ -82,7 +83,9 @@ def wave_cmvn(inputs_wav_scp, labels_wav_scp, engine=None, input_spec=W.DEFAULT,
     xs = ys if simulate is not None else W.read_wav_scp(inputs_wav_scp)
     if engine is None:
         si = _host_sums(xs, input_spec, lambda s: W.lps_from_wave(s, spec=input_spec), simulate)
-        sl = _host_sums(ys, label_spec, lambda s: W.mfcc_from_wave(s, label_spec))
+        label = (lambda s: W.mfcc_from_wave(s, label_spec)) if isinstance(label_spec, W.MfccSpec) else \
+            (lambda s: W.lps_from_wave(s, spec=label_spec))
+        sl = _host_sums(ys, label_spec, label)
     else:
         si, sl = _device_sums(xs, input_spec, engine, simulate=simulate), _device_sums(ys, label_spec, engine)
     mi, di = _finish("inputs", *si)
@@ -100,6 +103,7 @@ def main(argv=None):
     p.add_argument("--sim_seed", type=int, default=0)
     p.add_argument("--labels_wav_scp", required=True)
     p.add_argument("--out", required=True, help="the .npz to write (the recipes read <data_dir>/train_cmvn.npz)")
+    p.add_argument("--label_kind", default="mfcc", choices=("mfcc", "lps"), help="the labels' features: MFCC (default) or LPS (audio out)")
     p.add_argument("--device", default=False, action="store_true", help="make and sum the frames on the device")
     a = p.parse_args(argv)
     if bool(a.inputs_wav_scp) == bool(a.rir_scp):
@@ -112,7 +116,8 @@ def main(argv=None):
         if a.rir_scp:
             from .reverb import ReverbSim, ReverbSpec
             sim = ReverbSim(a.rir_scp, a.noise_scp, ReverbSpec(snr=(a.snr_lower, a.snr_upper)), a.sim_seed)
-        stats = wave_cmvn(a.inputs_wav_scp, a.labels_wav_scp, engine, simulate=sim)
+        stats = wave_cmvn(a.inputs_wav_scp, a.labels_wav_scp, engine, label_spec=W.MFCC_DEFAULT if a.label_kind == "mfcc" else W.DEFAULT,
+                          simulate=sim)
     except (OSError, EOFError, ValueError) as e:
         raise SystemExit("wave_cmvn: %s" % e)
     np.savez(a.out, **stats)

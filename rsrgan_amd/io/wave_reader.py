@@ -1,6 +1,6 @@
 """Training batches from audio: PaddedBatchReader's sibling over two wav.scp files (reverberant inputs, clean labels) instead of two feature
 archives.  Inputs become log-power-spectrum frames (io.wave.WaveSpec), labels MFCC frames (io.wave.MfccSpec: compute-mfcc-feats with
-mfcc_hires.conf), on the host or on the device."""
+mfcc_hires.conf) or, with a plain WaveSpec as label_spec, LPS frames, on the host or on the device."""
 from __future__ import annotations
 
 import random
@@ -10,7 +10,7 @@ from typing import Iterator, List
 import numpy as np
 
 from .features import apply_cmvn, pad_items, plan_batches, splice_feats
-from .wave import DEFAULT, MFCC_DEFAULT, lps_from_wave, mfcc_from_wave, num_frames, pack_wave, read_wav, read_wav_scp
+from .wave import DEFAULT, MFCC_DEFAULT, MfccSpec, lps_from_wave, mfcc_from_wave, num_frames, pack_wave, read_wav, read_wav_scp
 
 
 class WaveBatchReader(object):
@@ -19,7 +19,7 @@ class WaveBatchReader(object):
     (start 200 frames, width 50, ids clipped at num_buckets), partial windows at the end.  The frame counts come from the wav headers
     alone (no sample is read before materialize), so io.prefetch can run materialize on several threads.
 
-    Default route: lps_from_wave / mfcc_from_wave on the host (float64, one rounding), then PaddedBatchReader's float64 CMVN, splice and
+    Default route: lps_from_wave / mfcc_from_wave (lps_from_wave for an LPS label_spec) on the host (float64, one rounding), then PaddedBatchReader's float64 CMVN, splice and
     zero padding: the items are ordinary padded batches [utt_ids, inputs [B, T, bins * (L + 1 + R)] f32, labels [B, T, label bins] f32,
     lengths [B] i32].
     device_features=True: the samples travel; the items are [utt_ids, WaveBatch(inputs), WaveBatch(labels), lengths] and the device makes
@@ -96,7 +96,7 @@ class WaveBatchReader(object):
     def _utt(self, i):
         sx, sy = self._samples(i)
         x = lps_from_wave(sx, spec=self.input_spec).astype(np.float64)
-        y = mfcc_from_wave(sy, self.label_spec).astype(np.float64)
+        y = _label_frames(sy, self.label_spec).astype(np.float64)
         if self.cmvn is not None:
             x, y = apply_cmvn(x, y, self.cmvn)
         return self.utt_ids[i], splice_feats(x, self.left, self.right).astype(np.float32), y.astype(np.float32)
@@ -118,6 +118,12 @@ class WaveBatchReader(object):
         if self.device_features:
             return self._waves(indices)
         return pad_items([self._utt(i) for i in indices])
+
+
+def _label_frames(samples, spec):
+    """the host route of the labels dispatches on the spec, as the device route does (HipEngine.wave_features): MFCC / log-mel for an
+    MfccSpec, LPS for a plain WaveSpec (the targets a model must have for audio out)"""
+    return mfcc_from_wave(samples, spec) if isinstance(spec, MfccSpec) else lps_from_wave(samples, spec=spec)
 
 
 def _header_samples(path):

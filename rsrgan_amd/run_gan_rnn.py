@@ -86,9 +86,54 @@ def build_parser():
                        "of the split's *_scp archive; inputs become 257-bin log-power-spectrum frames, labels 40-dim MFCC frames "
                        "(io/wave.py MfccSpec: compute-mfcc-feats with mfcc_hires.conf), on the host, or with --device_features on the "
                        "device (csrc/wave.hip); given in pairs")
+    add_audio_out_flags(p)
     from .io.reverb import add_sim_flags
     add_sim_flags(p)
     return p
+
+
+def add_audio_out_flags(p):
+    """--label_kind and --wav_out, shared by the two sequence recipes"""
+    p.add_argument("--label_kind", type=str, default="mfcc", choices=("mfcc", "lps"), help="train from AUDIO: the labels' features -- mfcc "
+                   "(40-dim MFCC, io/wave.py MfccSpec) or lps (the inputs' 257-bin log-power-spectrum framing: the targets a model needs "
+                   "for --wav_out); --output_dim must be the kind's bins")
+    p.add_argument("--wav_out", type=str, default=None, help="decode with --wav_scp and --output_dim 257: besides feats.ark, every utterance's "
+                   "de-normalised output goes back to samples against its own input audio (the enhanced magnitude, the input's phase, "
+                   "overlap-add, de-emphasis: io/wave.py wave_from_lps; with --device_features on the device, csrc/synth.hip) and is "
+                   "written as DIR/<utt>.wav, listed in DIR/wav.scp")
+
+
+def label_spec(FLAGS):
+    """the framing of the labels made from audio: --label_kind"""
+    from .io import wave as W
+    return W.DEFAULT if getattr(FLAGS, "label_kind", "mfcc") == "lps" else W.MFCC_DEFAULT
+
+
+class _WavSink(object):
+    """--wav_out: every utterance's de-normalised output matrix -> DIR/<utt>.wav and a line of DIR/wav.scp.  engine: a HipEngine for
+    the device route (HipEngine.synthesize), None for the host route (io.wave.wave_from_lps)."""
+
+    def __init__(self, out_dir, source, engine=None):
+        self.dir, self.source, self.engine = out_dir, source, engine
+        os.makedirs(out_dir, exist_ok=True)
+        self.scp = open(os.path.join(out_dir, "wav.scp"), "w")
+
+    def write(self, i, lps):
+        """lps: utterance i's [T, bins] matrix, a host array or a device tensor"""
+        W, utt = self.source.W, self.source.utt_ids[i]
+        x = self.source.read_samples(i)
+        if self.engine is not None:
+            out, _ = self.engine.synthesize(W.pack_wave([x], spec=self.source.spec, names=[utt]), lps)
+            self.engine.upload_stream().synchronize()
+            y = out.cpu().numpy()
+        else:
+            y = W.wave_from_lps(lps.detach().cpu().numpy() if hasattr(lps, "detach") else np.asarray(lps), x, self.source.spec)
+        path = os.path.join(self.dir, utt + ".wav")
+        W.write_wav(path, W.quantize_pcm(y), self.source.spec.sample_rate)
+        self.scp.write("%s %s\n" % (utt, path))
+
+    def close(self):
+        self.scp.close()
 
 
 class _WavSource(object):
@@ -164,9 +209,10 @@ def check_wav_flags(FLAGS):
         raise SystemExit("--snr_lower %g is above --snr_upper %g" % (FLAGS.snr_lower, FLAGS.snr_upper))
     if any_wav and _device_decode(FLAGS):
         raise SystemExit("--*_wav_scp reads audio, --device_decode decodes archives: use --device_features for the device route")
-    if any_wav and (int(FLAGS.input_dim) != W.DEFAULT.bins or int(FLAGS.output_dim) != W.MFCC_DEFAULT.bins):
+    labels = label_spec(FLAGS)                                              # (--label_kind: MFCC_DEFAULT unless it says lps)
+    if any_wav and (int(FLAGS.input_dim) != W.DEFAULT.bins or int(FLAGS.output_dim) != labels.bins):
         raise SystemExit("--*_wav_scp makes input frames of %d bins and label frames of %d; --input_dim is %d, --output_dim is %d" % (
-            W.DEFAULT.bins, W.MFCC_DEFAULT.bins, int(FLAGS.input_dim), int(FLAGS.output_dim)))
+            W.DEFAULT.bins, labels.bins, int(FLAGS.input_dim), int(FLAGS.output_dim)))
 
 
 def split_reader(FLAGS, split, cmvn, shuffle, seed):
@@ -178,7 +224,7 @@ def split_reader(FLAGS, split, cmvn, shuffle, seed):
         try:
             return WaveBatchReader(wav or None, getattr(FLAGS, split + "_labels_wav_scp"), FLAGS.batch_size * FLAGS.num_gpu, FLAGS.left_context,
                                    FLAGS.right_context, cmvn=cmvn, shuffle=shuffle, seed=seed, device_features=_device_features(FLAGS),
-                                   simulate=sim_from_flags(FLAGS, split) if rir else None)
+                                   label_spec=label_spec(FLAGS), simulate=sim_from_flags(FLAGS, split) if rir else None)
         except (OSError, EOFError, ValueError) as e:
             raise SystemExit("--%s_*_wav_scp: %s" % (split, e))
     return _reader(FLAGS, getattr(FLAGS, split + "_inputs_scp"), getattr(FLAGS, split + "_labels_scp"), cmvn, shuffle, seed)
@@ -284,6 +330,14 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
                                            ["gpu:%d" % rdist.rank()], cross_validation=True, infer=True,
                                            max_frames=chunk if chunk > 0 else FLAGS.max_frames, net_overrides=net_overrides,
                                            **({"inference_only": True} if getattr(FLAGS, "decode_lean", False) else {})))
+    wav, wav_out = getattr(FLAGS, "wav_scp", None), getattr(FLAGS, "wav_out", None)
+    if wav_out:
+        from .io import wave as W
+        if not wav or int(FLAGS.output_dim) != W.DEFAULT.bins:
+            raise SystemExit("--wav_out needs --wav_scp (the audio whose phase it keeps) and --output_dim %d (LPS rows to synthesise from); "
+                             "--wav_scp is %s, --output_dim is %d" % (W.DEFAULT.bins, wav or "not given", int(FLAGS.output_dim)))
+        if push > 0:
+            raise SystemExit("--wav_out does not go with --decode_push: the live path has no synthesis")
     model = mk()
     if model.load(model.save_dir, moving_average=False):
         log("[*] Load SUCCESS")
@@ -296,7 +350,6 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
     if os.path.exists(write_ark_path):
         os.remove(write_ark_path)
     writer = ArkWriter(write_scp_path)
-    wav = getattr(FLAGS, "wav_scp", None)
     if wav:
         # --wav_scp: audio instead of an archive of frames (training from audio: the --tr_*_wav_scp / --cv_*_wav_scp flags)
         if _device_decode(FLAGS):
@@ -307,13 +360,24 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
         reader(FLAGS.test_inputs_scp)
     start = datetime.datetime.now()
     denorm = lambda a: a * cmvn["stddev_labels"] + cmvn["mean_labels"] if cmvn is not None else a
+    sink = None
+    if wav_out:
+        engine = getattr(model, "engine", None) if _device_features(FLAGS) else None
+        if _device_features(FLAGS) and getattr(engine, "synthesize", None) is None:
+            raise SystemExit("--wav_out with --device_features needs an engine with device-side synthesis (HipEngine.synthesize)")
+        sink = _WavSink(wav_out, reader, engine)
 
     def write_all(outs, post):
         """one matrix per utterance, in scp order"""
         for i, (utt, activations) in enumerate(zip(reader.utt_ids, outs)):
-            writer.write_next_utt(write_ark_path, utt, post(np.asarray(activations)))
+            matrix = post(np.asarray(activations))
+            writer.write_next_utt(write_ark_path, utt, matrix)
+            if sink is not None:
+                sink.write(i, matrix)
             log("[{}/{}] Write inferred {} to {}".format(i + 1, len(reader.utt_ids), utt, write_ark_path))
         writer.close()
+        if sink is not None:
+            sink.close()
         log("Decoding time is {}s".format((datetime.datetime.now() - start).total_seconds()))
         return write_scp_path
 
@@ -373,10 +437,18 @@ def decode(FLAGS, model_factory=None, log=print, net_overrides=None):
     for i, utt in enumerate(reader.utt_ids):
         x = features(i)[None]
         activations = model.forward(x, np.array([x.shape[1]], np.int32))
-        sequence = denorm(host(finish(activations) if finish is not None else activations))
+        activations = finish(activations) if finish is not None else activations
+        on_device = sink is not None and sink.engine is not None and hasattr(activations, "detach")
+        if on_device:
+            sink.write(i, activations[0])                                    # (the de-normalised device tensor, before it comes back)
+        sequence = denorm(host(activations))
+        if sink is not None and not on_device:
+            sink.write(i, np.vstack(sequence))
         writer.write_next_utt(write_ark_path, utt, np.vstack(sequence))
         log("[{}/{}] Write inferred {} to {}".format(i + 1, len(reader.utt_ids), utt, write_ark_path))
     writer.close()
+    if sink is not None:
+        sink.close()
     log("Decoding time is {}s".format((datetime.datetime.now() - start).total_seconds()))
     return write_scp_path
 

@@ -68,6 +68,7 @@ def build_parser():
     for n in ("tr_inputs_wav_scp", "tr_labels_wav_scp", "cv_inputs_wav_scp", "cv_labels_wav_scp"):
         p.add_argument("--" + n, type=str, default=None, help="train from audio: a wav.scp in place of the split's *_scp archive "
                        "(run_gan_rnn --%s)" % n)
+    gan_loop.add_audio_out_flags(p)
     from .io.reverb import add_sim_flags
     add_sim_flags(p)
     return p
