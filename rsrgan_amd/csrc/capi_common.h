@@ -1,5 +1,5 @@
-// capi_common.h -- what the files behind include/rsrgan.h share: capi.cpp (the handle ABI and the rsrgan_feat_* front end) and
-// capi_ops.cpp (the unit-test operator entries, rsrgan_op_*).  set_error / get_error / HIPC are model.h's.
+// capi_common.h -- what the files behind include/rsrgan.h share: capi.cpp (the handle ABI), capi_front.cpp (the handle-free front end and
+// histograms) and capi_ops.cpp (the unit-test operator entries, rsrgan_op_*).  set_error / get_error / HIPC are model.h's.
 #pragma once
 #include <cstring>
 #include <exception>

@@ -1,6 +1,6 @@
 // capi_ops.cpp -- the unit-test operator entries of include/rsrgan.h (rsrgan_op_*): the model's own host launch functions on
 // caller-owned buffers, no handle.  First the positional-argument entries (launch floor, gemm, column sums, bnl_fold, conv, bn), then
-// the table-form ones (op, ptrs, dims, fl: segan, chunks, update, step_elem, layout).  The product's entries are capi.cpp's.
+// the table-form ones (op, ptrs, dims, fl: segan, chunks, update, step_elem, layout).  The product's entries are capi.cpp's and capi_front.cpp's.
 #include "capi_common.h"
 
 extern "C" {

@@ -55,7 +55,7 @@ def _device_sums(items, spec, engine, batch=64, simulate=None):
         with torch.cuda.stream(us):
             if plan is not None:
                 pcm, dseg, _ = engine.simulate(wb, stream=us)
-                f = engine._wave_rows(pcm, dseg, len(wb), wb.offsets, rows, spec, us)[0].double()
+                f = engine.wave_rows(pcm, dseg, len(wb), wb.offsets, rows, spec, us)[0].double()
             else:
                 f = engine.wave_features(wb.samples, wb.seg, wb.offsets, rows, spec, us)[0].double()
             a, b = f.sum(0), (f * f).sum(0)
@@ -69,8 +69,8 @@ def _device_sums(items, spec, engine, batch=64, simulate=None):
 
 def wave_ops():
     """the waveform front end without a model: the handle-free entries on the current device (HipEngine's base class)"""
-    from ..engine_hip import WaveFrontEnd
-    return WaveFrontEnd()
+    from ..frontend import FrontEnd
+    return FrontEnd()
 
 
 def wave_cmvn(inputs_wav_scp, labels_wav_scp, engine=None, input_spec=W.DEFAULT, label_spec=W.MFCC_DEFAULT, simulate=None):

@@ -1,6 +1,6 @@
 """OpEntries -- the unit-test operator entries of the C ABI (include/rsrgan.h rsrgan_op_*, csrc/capi_ops.cpp): the library's own host
 launch code on caller-owned device tensors.  No handle: a loaded library, a device and the current stream are all they need, so the
-operator tests and tools/gemm_bench.py build an OpEntries() and no model.  HipEngine derives from it."""
+operator tests and tools/gemm_bench.py build an OpEntries() and no model.  FrontEnd (frontend.py), and through it HipEngine, derives from it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -26,8 +26,9 @@ class OpEntries:
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         torch.cuda.set_device(self.device)
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def _stream(self, stream=None):
+        """the entries' stream argument: `stream`, or the current one"""
+        return C.c_void_p((torch.cuda.current_stream(self.device) if stream is None else stream).cuda_stream)
 
     @staticmethod
     def _table(ts):

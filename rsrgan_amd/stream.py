@@ -297,7 +297,7 @@ class StreamBank(object):
         spec = self.wave
         if self.dim is not None and self.dim != spec.bins:
             raise ValueError("push_audio makes frames of %d bins, the bank's frames have %d" % (spec.bins, self.dim))
-        if self.device_features and not hasattr(self.model.engine, "wave_lps"):
+        if self.device_features and not hasattr(self.model.engine, "wave_features"):
             raise ValueError("push_audio with device_features=True needs an engine with a device-side waveform front end (HipEngine.op_feat_wave)")
         taken = {}
         for r, x in samples_by_row.items():
@@ -329,7 +329,7 @@ class StreamBank(object):
         eng = self.model.engine
         us = eng.upload_stream()
         with torch.cuda.stream(us):                                        # (the rounds read `lps` on this stream too: no other order is needed)
-            lps, _ = eng.wave_lps(blob, seg, offsets, int(offsets[-1]), spec, us)
+            lps, _ = eng.wave_features(blob, seg, offsets, int(offsets[-1]), spec, us)
         self.counters["bytes_up"] += blob.nbytes + seg.nbytes + offsets.nbytes
         return self._rounds(count, lambda r, lo, n: _DeviceRows(base[r] + lo, n), dev=lps)
 
@@ -443,10 +443,10 @@ class StreamBank(object):
         B, H, D = self.batch, self.ring_frames, self.dim
         us = eng.upload_stream()
         st = self._stats
-        dm, ds = eng._cmvn_device(st["mean_inputs"], st["stddev_inputs"], us) if st is not None else (None, None)
+        dm, ds = eng.cmvn_device(st["mean_inputs"], st["stddev_inputs"], us) if st is not None else (None, None)
         # everything that touches the ring is queued on the upload stream, round after round: that order alone is what lets a round overwrite
         # the slots of frames the round before still read
-        with torch.cuda.stream(us):
+        with eng.handoff(False) as res:
             if self._ring is None:
                 self._ring = torch.zeros(B, H, D, dtype=torch.float32, device=eng.device)
             if _on_device(fresh):                                          # (push_audio: the frames were made on the device, on this stream)
@@ -457,11 +457,7 @@ class StreamBank(object):
             out = torch.empty(B, T, D * (self.left + 1 + self.right), dtype=torch.float32, device=eng.device)
             ln = torch.empty(B, dtype=torch.int32, device=eng.device)
             eng.op_feat_stream(fr, tb, self._ring, B, H, T, D, self.left, self.right, dm, ds, out, ln, stream=us)
-            ev = torch.cuda.Event()
-            ev.record(us)
-        cur = torch.cuda.current_stream(eng.device)
-        cur.wait_event(ev)
-        out.record_stream(cur); ln.record_stream(cur)
+            res += [out, ln]
         self.counters["bytes_up"] += up + table.nbytes
         return out, ln
 

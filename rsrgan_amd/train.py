@@ -88,7 +88,7 @@ def device_frames(model, reader):
         x, lab = f(item, ready=ready)
         x, lab = x[:, None, :], lab[:, None, :]
         if ready:
-            model.engine._vouch(lab)              # (the view d_backward will see: upload_ready knows tensor objects, not storages)
+            model.engine.vouch(lab)              # (the view d_backward will see: upload_ready knows tensor objects, not storages)
         yield x, lab
 
 

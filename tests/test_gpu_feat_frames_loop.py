@@ -143,8 +143,8 @@ def test_training_and_decode_are_equal_on_both_paths(tmp_path, counted):
         tr_b, cv_b = (int(v) for v in open(tmp_path / "batch_num.txt").read().split()[1::-1])
         assert used == (3 * (tr_b // 3) + 2 * 3 * (cv_b // 3) if flag else 0) and tr_b >= 6 and cv_b >= 3
         if flag:
-            pools = model.engine.__dict__["_frame_pools"]
-            assert len(pools) == 2 and all(p["items"] > 0 for p in pools.values())          # training and cross-validation reader: two pools
+            pools = [model.engine.frame_pool_stats(r) for r in model.engine.frame_pool_readers()]
+            assert len(pools) == 2 and all(p["items"] > 0 for p in pools)                   # training and cross-validation reader: two pools
         model.save(save, 7)                                      # (whatever the accept / reject rule did: decode needs a checkpoint)
         g, d = model.get_vars()
         events = {sub: S.read_events(glob.glob(os.path.join(save, sub, "events.out.tfevents.*"))[0]) for sub in ("train", "eval")}

@@ -48,7 +48,7 @@ def _raw(eng, wb):
     """the kernel's raw rows of a WaveBatch through the op entries, and its device offset table"""
     dev = eng.device
     us = eng.upload_stream()
-    tabs = eng._wave_tables(wb.spec, us)
+    tabs = eng.wave_tables(wb.spec, us)
     us.synchronize()
     pcm, seg, off = (torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (wb.samples, wb.seg, wb.offsets))
     s = wb.spec

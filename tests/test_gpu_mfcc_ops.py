@@ -62,7 +62,7 @@ def run(eng, blob, seg, offsets, out_rows, spec, extra=0, mel_seg=None):
     """one launch into a banded canary buffer -> (the whole buffer's bits, out [out_rows + extra, spec.bins] on the host)"""
     dev = eng.device
     us = eng.upload_stream()
-    tabs = list(eng._wave_tables(spec, us))
+    tabs = list(eng.wave_tables(spec, us))
     us.synchronize()
     if mel_seg is not None:
         tabs[2] = torch.from_numpy(np.ascontiguousarray(mel_seg, np.int32)).to(dev)

@@ -42,7 +42,7 @@ def _device_lps(eng, utts):
     wb = W.pack_wave(utts)
     us = eng.upload_stream()
     with torch.cuda.stream(us):
-        raw, _ = eng.wave_lps(wb.samples, wb.seg, wb.offsets, int(wb.offsets[-1]), wb.spec, us)
+        raw, _ = eng.wave_features(wb.samples, wb.seg, wb.offsets, int(wb.offsets[-1]), wb.spec, us)
     us.synchronize()
     raw = raw.cpu().numpy()
     return [raw[a:b] for a, b in zip(wb.offsets[:-1], wb.offsets[1:])], wb

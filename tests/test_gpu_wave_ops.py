@@ -105,7 +105,7 @@ def run(eng, blob, seg, offsets, out_rows, spec=W.DEFAULT, extra=0):
     """one launch into a banded canary buffer -> (the whole buffer's bits, out [out_rows + extra, bins] on the host)"""
     dev = eng.device
     us = eng.upload_stream()
-    win, tw = eng._wave_tables(spec, us)
+    win, tw = eng.wave_tables(spec, us)
     us.synchronize()
     t = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (blob, seg, offsets)]
     keep = [a.clone() for a in t]

@@ -78,7 +78,7 @@ def run(eng, blob, seg, offsets, lps, oseg, out_len, spec=W.DEFAULT):
     """one call into a banded canary buffer -> out [out_len] on the host"""
     dev = eng.device
     us = eng.upload_stream()
-    win, tw = eng._wave_tables(spec, us)
+    win, tw = eng.wave_tables(spec, us)
     us.synchronize()
     t = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (blob, seg, offsets, lps, oseg)]
     keep = [a.clone() for a in t]

@@ -64,8 +64,8 @@ def main(argv=None):
         sys.stdout.write(json.dumps(banks_line(mspec)) + "\n")
         return
     import torch
-    from rsrgan_amd.engine_hip import WaveFrontEnd
-    ops = WaveFrontEnd()
+    from rsrgan_amd.frontend import FrontEnd
+    ops = FrontEnd()
     dev = ops.device
     up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)
     tw = up(W.twiddle_table(512))

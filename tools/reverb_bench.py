@@ -35,10 +35,10 @@ def main(argv=None):
     ap.add_argument("--bench", default=False, action="store_true")
     a = ap.parse_args(argv)
     import torch
-    from rsrgan_amd.engine_hip import WaveFrontEnd
+    from rsrgan_amd.frontend import FrontEnd
     from rsrgan_amd.io import reverb as RV
     from rsrgan_amd.io import wave as W
-    ops = WaveFrontEnd()
+    ops = FrontEnd()
     dev = ops.device
     up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)
     rng = np.random.default_rng(1)

@@ -33,9 +33,9 @@ def main(argv=None):
     ap.add_argument("--bench", default=False, action="store_true")
     a = ap.parse_args(argv)
     import torch
-    from rsrgan_amd.engine_hip import WaveFrontEnd
+    from rsrgan_amd.frontend import FrontEnd
     from rsrgan_amd.io import wave as W
-    ops = WaveFrontEnd()
+    ops = FrontEnd()
     dev = ops.device
     up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)
     rng = np.random.default_rng(1)
@@ -56,7 +56,7 @@ def main(argv=None):
     lps = up(np.concatenate(rows, 0))
     pcm, seg, off = up(wb.samples), up(wb.seg), up(wb.offsets)
     us = ops.upload_stream()
-    win, tw = ops._wave_tables(spec, us)
+    win, tw = ops.wave_tables(spec, us)
     us.synchronize()
     out = torch.empty(B * n, dtype=torch.float32, device=dev)
     work = torch.empty(ops.wave_synth_work(B, int(lps.shape[0]), B * n, spec.frame_length), dtype=torch.uint8, device=dev)

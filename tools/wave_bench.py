@@ -33,9 +33,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     import torch
     from rsrgan_amd.io import wave as W
-    from rsrgan_amd.ops import OpEntries
-    from rsrgan_amd.engine_hip import HipEngine
-    ops = OpEntries()
+    from rsrgan_amd.frontend import FrontEnd
+    ops = FrontEnd()
     dev, spec = ops.device, W.DEFAULT
     lines = []
     for frames in a.frames:
@@ -56,7 +55,7 @@ def main(argv=None):
         tw = torch.from_numpy(W.twiddle_table(spec.padded)).to(dev)
         pcm, seg, off = (torch.from_numpy(v).to(dev) for v in (wb.samples, wb.seg, wb.offsets))
         out = torch.empty(total, spec.bins, dtype=torch.float32, device=dev)
-        launch = lambda: HipEngine.op_feat_wave(ops, pcm, seg, off, a.batch, win, tw, out)
+        launch = lambda: ops.op_feat_wave(pcm, seg, off, a.batch, win, tw, out)
         for _ in range(3):
             launch()
         torch.cuda.synchronize()
